@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- input MB/s tokenized, tokenizer_de.matok (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A step is one pass of the hot path (symbolise -> walk -> compact, i.e. one data-parallel
 TransduceTokenWriter) over one batch of synthetic German documents that is already resident in HBM,
@@ -16,8 +16,15 @@ no data-path collective: documents are independent).  After the timed region the
 arrays (tok_rstart, tok_rend, sent) are gathered to rank 0 over RCCL once, outside the clock
 (gather_ms).
 
-Rank 0 prints one JSON line.  `value` is whole-job MB/s (1e6 bytes/s) with inputs resident in HBM;
-`end_to_end` is the same work fed from pinned host memory through dtk_batch_set_input (PCIe inclusive).
+Rank 0 prints one JSON line.  `value` is whole-job MB/s (1e6 bytes/s) with inputs resident in HBM.
+
+A plain run sets up (inputs, one first run of each batch), runs the W warm-up steps and the K timed steps, and prints
+the line; the fields that need runs of their own are null.  --full adds them: the parity gate against the CPU oracle,
+the per-kernel times (`stages_ms`, `streams_1`) and the roofline object, `end_to_end` (the same work fed from pinned
+host memory through dtk_pipeline_run, PCIe inclusive), the CPU baseline and, at N > 1, the offset gather.
+
+--dump-outputs DIR writes what the last timed step computed -- the result arrays of its batch as a caller of
+dtk_batch_result_host receives them -- as DIR/<name>.npy in float64 (rank 0's shard at N > 1).
 """
 import argparse
 import json
@@ -54,12 +61,19 @@ def parse():
     ap.add_argument("--streams", type=int, default=0,
                     help="batches in flight (default 3 at N = 1, 1 at N > 1): consecutive steps alternate between "
                          "this many dtk_batch objects, each with its own input (seeds 2, 3, ...), HIP stream and buffers")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity gate, per-kernel times and roofline, the PCIe-inclusive block, the CPU baseline "
+                         "and (N > 1) the offset gather")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's result arrays as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--parity-docs", type=int, default=256, help="documents checked against the oracle before timing")
+    ap.add_argument("--parity-docs", type=int, default=256, help="(--full) documents checked against the oracle before timing")
     ap.add_argument("--e2e-only", action="store_true", help="(internal) the PCIe-inclusive block in a process of its own")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive block (profiling runs: no child process)")
-    return ap.parse_args()
+    ap.add_argument("--no-e2e", action="store_true", help="(--full) skip the PCIe-inclusive block (profiling runs: no child process)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def walk_kernel_name(info, chunked):
@@ -119,6 +133,33 @@ def stage_times(batches, tok, steps):
     for bb in batches:
         bb.set_profiling(False)
     return {k: v / n for k, v in acc.items()}
+
+
+DUMP_FIELDS = ("tok_off", "sent_off", "text_off", "status") + RUNE_FIELDS
+DUMP_TOTALS = ("n_docs", "n_bytes", "n_tokens", "n_sent", "n_texts", "n_flagged")
+DUMP_VALUES = 60 * 2**20 // 8  # float64 values in all: under 64 MB with the .npy headers
+
+
+def dump_outputs(bb, out_dir):
+    """The result arrays of batch bb's last run (the CSR row offsets, the status words and the rune offset arrays that
+    RUN_FLAGS selects) and its totals as out_dir/<name>.npy, float64 (exact for every integer here).  Past DUMP_VALUES
+    values in all, the shorter arrays are kept whole and the longer ones share the rest equally, each cut to its share
+    at sorted positions drawn by a generator seeded with 0: the same positions for the same lengths (tok_rstart[i] and
+    tok_rend[i] stay one token)."""
+    res, tot = bb.result(), bb.totals()
+    arrays = {f: getattr(res, f) for f in DUMP_FIELDS}
+    arrays["totals"] = np.array([tot[k] for k in DUMP_TOTALS])
+    os.makedirs(out_dir, exist_ok=True)
+    budget, share = DUMP_VALUES, None
+    for i, name in enumerate(sorted(arrays, key=lambda f: (len(arrays[f]), f))):
+        a = arrays[name]
+        if share is None and len(a) * (len(arrays) - i) > budget:
+            share = budget // (len(arrays) - i)
+        if share is None:
+            budget -= len(a)
+        else:
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), share, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
 
 
 def e2e_only(args):
@@ -263,13 +304,14 @@ def main():
     batch = batches[0]
     text, doc_off = inputs[0]
 
-    # ---- parity gate (oracle is the checker, never the thing measured): every batch in flight, sampled documents
+    # ---- first run of every batch in flight; --full: parity gate (oracle is the checker, never the thing measured),
+    #      sampled documents
     tot = None
     for k, bb in enumerate(batches):
         bb.run(tok, RUN_FLAGS)
         tk = bb.totals()
         tot = tot or tk
-        if args.parity_docs:
+        if args.full and args.parity_docs:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             from parity import assert_batch_equals_oracle
             from oracle import oracle as O
@@ -285,22 +327,23 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- per-kernel times (HIP events on the batches' streams): one batch alone on the GPU, then the regime of the
-    #      timed region.  They run BEFORE the timed region, not behind it: the oracle's parity check above leaves the GPU
-    #      idle for seconds, and W = 5 warm-up steps (half a millisecond) do not bring its clocks and caches back --
+    # ---- --full: per-kernel times (HIP events on the batches' streams): one batch alone on the GPU, then the regime of
+    #      the timed region.  They run BEFORE the timed region, not behind it: the oracle's parity check above leaves the
+    #      GPU idle for seconds, and W = 5 warm-up steps (half a millisecond) do not bring its clocks and caches back --
     #      K = 20 steps then read 148-151 GB/s where the same 20 steps behind 200 warm-up steps read 157-158.  After
     #      these measurements the timed region finds the GPU as a running service has it.
-    one = None
-    pre_steps = len(batches)  # (the parity gate's runs)
-    if len(batches) > 1:
+    one, stage_avg = None, None
+    pre_steps = len(batches)  # (the first runs)
+    if args.full and len(batches) > 1:
         timed_steps(batches[:1], tok, max(args.steps, 30), barrier)  # (untimed: the first launches after the idle phase)
         e1 = timed_steps(batches[:1], tok, args.steps, barrier)
         s1 = stage_times(batches[:1], tok, args.steps)
         pre_steps += max(args.steps, 30) + args.steps + 4 * max(args.steps // 4, 2)
         one = {"value": round(total * args.steps / e1 / 1e6, 1), "ms_per_step": round(e1 / args.steps * 1e3, 4),
                "kernel_ms": round(s1["walk"], 4), "stages_ms": {k: round(v, 4) for k, v in s1.items()}}
-    stage_avg = stage_times(batches, tok, args.steps)
-    pre_steps += 4 * max(args.steps // 4, 2 * len(batches))
+    if args.full:
+        stage_avg = stage_times(batches, tok, args.steps)
+        pre_steps += 4 * max(args.steps // 4, 2 * len(batches))
 
     # ---- warmup
     ran = [False] * len(batches)
@@ -320,12 +363,14 @@ def main():
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
     repair_rounds = max(int(bb.totals()["repair_rounds"]) for bb in batches)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(batches[(args.steps - 1) % len(batches)], args.dump_outputs)
 
-    # ---- PCIe inclusive: the same inputs as one corpus in page-locked host memory, through dtk_pipeline.  In a process
-    #      of its own, without torch: a Go caller has none, and with torch initialised in the process the same pipeline's
-    #      downloads ran at two thirds of the rate (scripts/e2e_diag2.py WITH_TORCH=1: 24 against 36.7 GB/s).
+    # ---- --full, PCIe inclusive: the same inputs as one corpus in page-locked host memory, through dtk_pipeline.  In a
+    #      process of its own, without torch: a Go caller has none, and with torch initialised in the process the same
+    #      pipeline's downloads ran at two thirds of the rate (scripts/e2e_diag2.py WITH_TORCH=1: 24 against 36.7 GB/s).
     h2d = None
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         for bb in batches:   # (their HIP streams: the runtime has four hardware queues)
             bb.close()
         import subprocess
@@ -338,9 +383,9 @@ def main():
         if h2d is None:
             print("bench.py: end-to-end block failed: %s" % r.stderr[-400:], file=sys.stderr)
 
-    # ---- offset gather to rank 0 over RCCL (config 5's exchange), outside the clock
+    # ---- --full: offset gather to rank 0 over RCCL (config 5's exchange), outside the clock
     gather_ms, gather_hung, gather_err = None, False, None
-    if world > 1:
+    if args.full and world > 1:
         from datok_amd import shard
         v = batch.result_device()
         ntok, nsent = tot["n_tokens"], tot["n_sent"]
@@ -387,9 +432,9 @@ def main():
         gather_bytes = box.get("bytes")
         # no barrier behind the gather: a rank whose peer is stuck must still get to its output
 
-    # ---- CPU baseline: the C restatement of the Go algorithm, rank 0, N = 1 only, on the first batch's input
+    # ---- --full: CPU baseline: the C restatement of the Go algorithm, rank 0, N = 1 only, on the first batch's input
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as O
         om = O.Model(args.model)
         cores = os.cpu_count() or 1
@@ -412,21 +457,36 @@ def main():
     if rank == 0:
         ms_step = elapsed / args.steps * 1e3
         value = world * total * args.steps / elapsed / 1e6
-        # algorithmic bytes of one launch: input + doc offsets + i32 offsets out + counts
-        b_alg = total + 4 * (n_docs + 1) + 4 * (2 * tot["n_tokens"] + tot["n_sent"]) + 8 * n_docs
-        walk_s = stage_avg["walk"] * 1e-3
-        achieved = b_alg / walk_s / 1e9
-        split = os.environ.get("DATOK_SPLIT_START", "0") not in ("", "0")
-        both_s = (stage_avg["walk"] + (stage_avg["spec_start"] if split else 0.0)) * 1e-3
-        # HBM bytes of that kernel from the last committed rocprofv3 --pmc passes (profiles/)
-        traffic = None
-        try:
-            tr = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
-            if tr.get("docs") == n_docs and tr.get("doc_bytes") == args.doc_bytes and \
-                    tr.get("chunk_bytes") == tot["chunk_bytes"]:
-                traffic = tr["walk_kernel_hbm_bytes"]
-        except (OSError, ValueError, KeyError):
-            pass
+        roofline = None
+        if stage_avg is not None:
+            # algorithmic bytes of one launch: input + doc offsets + i32 offsets out + counts
+            b_alg = total + 4 * (n_docs + 1) + 4 * (2 * tot["n_tokens"] + tot["n_sent"]) + 8 * n_docs
+            walk_s = stage_avg["walk"] * 1e-3
+            achieved = b_alg / walk_s / 1e9
+            split = os.environ.get("DATOK_SPLIT_START", "0") not in ("", "0")
+            both_s = (stage_avg["walk"] + (stage_avg["spec_start"] if split else 0.0)) * 1e-3
+            # HBM bytes of that kernel from the last committed rocprofv3 --pmc passes (profiles/)
+            traffic = None
+            try:
+                tr = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
+                if tr.get("docs") == n_docs and tr.get("doc_bytes") == args.doc_bytes and \
+                        tr.get("chunk_bytes") == tot["chunk_bytes"]:
+                    traffic = tr["walk_kernel_hbm_bytes"]
+            except (OSError, ValueError, KeyError):
+                pass
+            roofline = {"bound": "hbm",
+                        "kernel": walk_kernel_name(tok.info, bool(tot["chunk_bytes"])),
+                        "achieved": round(achieved, 2),
+                        "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": round(achieved * 1e9 / HBM_PEAK, 6),
+                        "traffic": traffic,
+                        "traffic_source": None if traffic is None else "profiles/traffic.json (rocprofv3 --pmc passes of "
+                                          "this workload, %s)" % tr.get("measured", "committed with the round's profiles"),
+                        "algorithmic_bytes": int(b_alg),
+                        "kernel_ms": round(stage_avg["walk"], 4),
+                        "kernel_ms_note": "average launch duration with %d batches in flight (kernels of different "
+                                          "batches share the CUs); one batch alone: streams_1.kernel_ms" % len(batches),
+                        "lookups_per_launch": int(tot["walk_steps"]),
+                        "Glookups_per_s_start_plus_walk": round(tot["walk_steps"] / both_s / 1e9, 3)}
         mname = os.path.basename(args.model)
         cfg_no = "configs[3]" if mname.endswith(".datok") else "configs[1]"
         workload = (mname + ", %d equal-length %d B synthetic German docs per batch (BASELINE.json " + cfg_no + ")"
@@ -442,9 +502,11 @@ def main():
             "metric": "input MB/s tokenized, %s" % os.path.basename(args.model),
             "value": round(value, 1), "unit": "MB/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "pre_timed_steps": pre_steps + args.warmup,
-            "pre_timed_steps_note": "untimed launches before the K timed steps: parity gate, the per-kernel measurements "
-                                    "(streams_1, stages_ms) and the W warm-up steps -- the GPU's clocks come up during them "
-                                    "(DESIGN.md section 4)",
+            "pre_timed_steps_note": ("untimed launches before the K timed steps: parity gate, the per-kernel measurements "
+                                     "(streams_1, stages_ms) and the W warm-up steps -- the GPU's clocks come up during them "
+                                     "(DESIGN.md section 4)" if args.full else
+                                     "untimed launches before the K timed steps: the first run of each batch in flight and "
+                                     "the W warm-up steps"),
             "ms_per_step": round(ms_step, 4), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "u32 table cells, u8 symbol codes", "data": "synthetic",
             "config": {"workload": workload % (n_docs, args.doc_bytes),
@@ -454,20 +516,8 @@ def main():
                        "batches_in_flight": len(batches),
                        "inputs": "one per batch in flight (generator seeds %s on rank 0)" % ", ".join(map(str, seeds)),
                        "step": "dtk_batch_run + dtk_batch_totals (speculation check, repairs, capacity check) per batch"},
-            "roofline": {"bound": "hbm",
-                         "kernel": walk_kernel_name(tok.info, bool(tot["chunk_bytes"])),
-                         "achieved": round(achieved, 2),
-                         "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": round(achieved * 1e9 / HBM_PEAK, 6),
-                         "traffic": traffic,
-                         "traffic_source": None if traffic is None else "profiles/traffic.json (rocprofv3 --pmc passes of "
-                                           "this workload, %s)" % tr.get("measured", "committed with the round's profiles"),
-                         "algorithmic_bytes": int(b_alg),
-                         "kernel_ms": round(stage_avg["walk"], 4),
-                         "kernel_ms_note": "average launch duration with %d batches in flight (kernels of different "
-                                           "batches share the CUs); one batch alone: streams_1.kernel_ms" % len(batches),
-                         "lookups_per_launch": int(tot["walk_steps"]),
-                         "Glookups_per_s_start_plus_walk": round(tot["walk_steps"] / both_s / 1e9, 3)},
-            "stages_ms": {k: round(v, 4) for k, v in stage_avg.items()},
+            "roofline": roofline,
+            "stages_ms": None if stage_avg is None else {k: round(v, 4) for k, v in stage_avg.items()},
             "streams_1": one,
             "end_to_end": h2d,
             "tokens_per_launch": int(tot["n_tokens"]),

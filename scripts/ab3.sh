@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 libs=$1; shift
 for r in 1 2; do
   for v in $libs; do
-    DATOK_GPU_LIB=$PWD/ab/lib$v.so python bench.py --steps 40 --warmup 5 --no-cpu-baseline --parity-docs 0 "$@" 2>/dev/null | python -c "
+    DATOK_GPU_LIB=$PWD/ab/lib$v.so python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --parity-docs 0 "$@" 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

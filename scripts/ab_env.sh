@@ -6,7 +6,7 @@ kv=$1; shift
 for r in 1 2 3; do
   for v in A B; do
     if [ $v = A ]; then pre="env $kv"; else pre="env"; fi
-    $pre python bench.py --steps 40 --warmup 5 --no-cpu-baseline --parity-docs 32 "$@" 2>/dev/null | python -c "
+    $pre python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --parity-docs 32 "$@" 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

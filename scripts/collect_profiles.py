@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Copies what scripts/r02_final.sh left under gpurun_out/<tag>/ into profiles/ and rebuilds profiles/traffic.json from
-the FETCH_SIZE / WRITE_SIZE passes (per kernel, per launch; bench.py reads the walk's figure for its roofline object).
-usage: collect_profiles.py [tag]      (here, after the gpurun call has merged gpurun_out/)"""
+"""Copies what scripts/r02_final.sh left under $OUT/<tag>/ (OUT defaults to out) into profiles/ and rebuilds
+profiles/traffic.json from the FETCH_SIZE / WRITE_SIZE passes (per kernel, per launch; bench.py --full reads the walk's
+figure for its roofline object).
+usage: collect_profiles.py [tag]      (with that directory in the working tree)"""
 import json
 import os
 import re
@@ -10,7 +11,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
-src, dst = os.path.join(ROOT, "gpurun_out", tag), os.path.join(ROOT, "profiles")
+src, dst = os.path.join(ROOT, os.environ.get("OUT", "out"), tag), os.path.join(ROOT, "profiles")
 for f in ("bench_line.json", "bench_line_under_rocprof.json", "kernel_stats.csv", "pmc_traffic.txt", "pmc_sq.txt", "pmc_tcp.txt"):
     shutil.copy(os.path.join(src, f), os.path.join(dst, "%s_%s" % (tag, f)))
 with open(os.path.join(dst, tag + "_other_workloads.txt"), "w") as out:

@@ -3,7 +3,7 @@
 # skip mask: 1 symbolize, 2 start+link, 4 walk+memset, 8 compact (from the second run of a batch on)
 cd $GRAFT_REPO_ROOT
 for sk in 0 1 2 4 8 6 7 15 0; do
-  DATOK_EXP_SKIP=$sk python bench.py --streams ${STREAMS:-3} --steps 60 --warmup 6 --no-cpu-baseline --parity-docs 0 2>/dev/null | python -c "
+  DATOK_EXP_SKIP=$sk python bench.py --full --streams ${STREAMS:-3} --steps 60 --warmup 6 --no-cpu-baseline --parity-docs 0 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,7 +2,7 @@
 # chunk size against one batch alone / three in flight (bench corpus)
 cd $GRAFT_REPO_ROOT
 for c in 48 64 80 96 128; do
-python bench.py --chunk $c --steps 40 --warmup 5 --no-cpu-baseline --no-e2e --parity-docs 16 2>/dev/null | python -c "
+python bench.py --full --chunk $c --steps 40 --warmup 5 --no-cpu-baseline --no-e2e --parity-docs 16 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

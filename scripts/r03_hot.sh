@@ -11,7 +11,7 @@ done
 for r in 1 2; do
   for v in 1 0; do
     echo "== NO_HOT=$v bench"
-    DATOK_NO_HOT=$v python bench.py --steps 40 --warmup 5 --no-cpu-baseline --parity-docs 32 2>/dev/null | python -c "
+    DATOK_NO_HOT=$v python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --parity-docs 32 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

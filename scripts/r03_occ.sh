@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 for r in 1 2; do
   for v in O0 O7w32 O7w16 O8w16; do
     echo "== $v"; DATOK_GPU_LIB=$PWD/ab/lib$v.so python scripts/big_stages.py 32 2>&1 | tail -1 | sed 's/.*per 16 MiB, us: //'
-    DATOK_GPU_LIB=$PWD/ab/lib$v.so python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-e2e --parity-docs 32 2>/dev/null | python -c "
+    DATOK_GPU_LIB=$PWD/ab/lib$v.so python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-e2e --parity-docs 32 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,7 +1,7 @@
 cd $GRAFT_REPO_ROOT
 for cfg in "0 0" "1 0" "1 8" "1 16" "1 24" "2 8"; do
   set -- $cfg
-  DATOK_WARM_WS=$1 DATOK_WARM_MIN=$2 python bench.py --streams ${STREAMS:-3} --steps 60 --warmup 6 --no-cpu-baseline --parity-docs 32 2>/dev/null | python -c "
+  DATOK_WARM_WS=$1 DATOK_WARM_MIN=$2 python bench.py --full --streams ${STREAMS:-3} --steps 60 --warmup 6 --no-cpu-baseline --parity-docs 32 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -12,10 +12,6 @@
 #ifndef DTK_WARM_TAG
 #define DTK_WARM_TAG 64u
 #endif  // how far behind a warm-up start an opening angle bracket is looked for
-// knock-out builds for cost measurements (scripts/ko.sh): results are wrong, only timings mean something
-#ifndef DTK_KO
-#define DTK_KO 0
-#endif
 
 // ------------------------------------------------------------------ helpers
 

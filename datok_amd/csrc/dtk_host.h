@@ -1,0 +1,239 @@
+// dtk_host.h -- what the host units of libdatok_gpu.so (dtk_model, dtk_foma, dtk_batch, dtk_results .cpp) share: the
+// model and batch objects, the error state, the test hooks, and helpers (hidden, not exported).  No .hip unit includes it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/datok_gpu.h"
+#include "dtk_internal.h"
+
+#pragma GCC visibility push(hidden)
+
+// --------------------------------------------------------------- error state
+
+int hip_fail(hipError_t e, const char *what);
+#define HIP_TRY(call)                                   \
+  do {                                                  \
+    hipError_t e_ = (call);                             \
+    if (e_ != hipSuccess) return hip_fail(e_, #call);   \
+  } while (0)
+
+// ---------------------------------------------------------------- test hooks
+//
+// The library's behaviour does not depend on the caller's environment: nothing here reads it.  The switches
+// below select code paths that the library otherwise picks by model, shape or history, so that the tests can run the
+// whole suite over each of them; only dtk_debug_configure sets them (the Python harness forwards DATOK_* variables
+// to it, datok_amd/_lib.py -- the shipped entry points never look).  None of them changes a result.
+struct DtkDebug {
+  int sym16 = 0;         // 16-bit stream entries (and the general loop) although the model's entries fit a code table
+  int force_wide = 0;    // 32-bit plain cells for any model (MatrixTrans<uint32_t>)
+  int file_columns = 0;  // keep the file's column order
+  int no_fused = 0;      // plain uint16 cells: no fused epsilon + rune cells
+  int no_dense = 0;      // walk a double array's {base, check} pairs instead of its dense layout
+  int small_max = -1;    // documents of at most this many bytes are compacted one per lane (-1: by batch shape)
+  int lds_bits = 1;      // 0: event bits straight to memory
+  int split_start = 0;   // start records and chunk walk as two launches
+  int dev_rounds = -1;   // repair rounds enqueued with every run (-1: two after a run that had to repair)
+  int compact_full = 0;  // both compaction kernels with every run
+  int clear_kernel = 0;  // the accumulator block is cleared by k_clear2, not by k_symbolize's blocks
+  int round_limit = -1;  // host repair rounds before the one-lane-per-document fallback (-1: the longest document's lanes)
+  int debug_repair = 0;  // print the lane records of documents that stay broken
+};
+extern DtkDebug g_dbg;
+
+// ------------------------------------------------------------------- model
+
+struct dtk_model {
+  int kind = 0;
+  int epsilon = 0, unknown = 0, identity = 0, final_state = 0, sigma_count = 0;
+  uint32_t state_count = 0;
+  std::vector<uint16_t> col;   // symbol -> column of the device table (layout_matrix); empty: the symbol itself
+  uint32_t dense_states = 0;   // double array laid out as a matrix (densify in build_datok): its states; 0: the pairs are walked
+  uint64_t array_len = 0;
+  uint32_t n_eps_states = 0, max_eps_chain = 0, unknown_used = 0;
+  uint64_t device_bytes = 0;
+  int device = 0;
+  // host copy of the sigma map, for rendering (Go string(rune) of a token surface)
+  std::vector<uint32_t> sigma_runes;
+  std::vector<uint16_t> sigma_syms;
+  uint16_t ascii[256];
+  // device
+  void *d_tab = nullptr;
+  uint16_t *d_ascii = nullptr;
+  uint32_t *d_runes = nullptr;
+  uint16_t *d_syms = nullptr;
+  void *d_codes = nullptr;  // code_entry [256] u16, code_lt256 [256] u8, code_runes [n_runes] u8
+  DtkTableDev tab{};
+  DtkSigmaDev sig{};
+};
+
+int go_decode_host(const uint8_t *p, size_t n, uint32_t *r);
+int gunzip(const uint8_t *gz, size_t n, std::vector<uint8_t> &out);
+bool special_ids_ok(const dtk_model *m);
+int layout_matrix(dtk_model *m, const std::vector<uint32_t> &arr, uint64_t n_states, bool da_dense);
+int build_foma(dtk_model *m, const std::vector<uint8_t> &raw);
+
+// -------------------------------------------------------------------- batch
+
+struct dtk_batch {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  uint64_t max_bytes = 0;
+  uint32_t max_docs = 0;
+  // inputs
+  uint8_t *d_text_own = nullptr;
+  uint64_t *d_off_own = nullptr;
+  const uint8_t *d_text = nullptr;
+  const uint64_t *d_off = nullptr;
+  uint32_t n_docs = 0;
+  uint64_t total = 0;
+  // intermediates
+  uint16_t *d_sym = nullptr;
+  uint32_t *d_rsbits = nullptr;                // rune-start bitmap of the input (1 bit per byte)
+  uint32_t *d_bits = nullptr;                  // event bitmaps of the walk (EVB_KINDS kinds), cleared every run
+  uint32_t bit_words = 0;                      // words per kind of the current input
+  uint32_t *d_doc_tail = nullptr;              // per document: final SentenceEnd / TextEnd (carved from d_acc)
+  uint8_t *d_acc = nullptr;                    // per-document accumulators + totals (one memset)
+  uint64_t acc_bytes = 0;
+  uint32_t *d_status = nullptr;
+  // speculative chunk lanes
+  std::vector<uint64_t> h_doc_off;   // host copy of the document offsets (lane planning)
+  uint32_t cfg_chunk = 0xFFFFFFFFu;  // 0 = one lane per document, 0xFFFFFFFF = automatic
+  uint32_t cfg_extend = 240;         // move the warm-up start back to the previous blank, at most this far
+  uint32_t cfg_warm = 8;             // (16 until round 3: 8 costs no repair round on any corpus and 5 % fewer lookups) plus the way back to the previous blank (cfg_extend); a miss only costs a repair round
+  uint32_t chunk = 0;                // chunk size of the current plan (0 = none)
+  bool plan_valid = false;
+  uint32_t n_lanes = 0, lane_cap = 0;
+  uint32_t *d_lane_doc = nullptr, *d_chunk_off = nullptr, *d_redo = nullptr;
+  // long documents are compacted in segments of DTK_SEG_LANES lanes (tables built with the lane plan)
+  uint32_t *d_seg_tab = nullptr;     // seg_doc | seg_lane0 | seg_nl | doc_seg0
+  DtkSegSum *d_seg_sum = nullptr;
+  DtkSegIn *d_seg_in = nullptr;
+  uint32_t n_segs = 0, seg_cap = 0;
+  bool long_docs = false;            // some document has more than one segment
+  uint32_t max_doc_lanes = 0;        // lanes of the longest document (bounds the repair rounds)
+  uint32_t *d_blk_doc = nullptr;     // document of the first byte of every 4 KiB input block
+  // compaction: documents of at most small_max bytes go one per lane (k_compact_small), the others one per wave
+  uint32_t small_max = 0, n_big = 0;
+  uint32_t *d_big_docs = nullptr;    // ids of the documents above small_max
+  uint32_t *d_first_bad = nullptr, *d_fail_lane = nullptr;
+  DtkLaneCount *d_lane_cnt = nullptr;
+  DtkLaneState *d_lane_start = nullptr, *d_lane_end = nullptr;
+  DtkLanePlan *d_lane_plan = nullptr;
+  uint32_t repair_rounds = 0;        // of the last run
+  const dtk_model *last_model = nullptr;
+  uint32_t last_flags = 0;
+  uint64_t *d_csr = nullptr;  // tok_off | sent_off | text_off
+  uint64_t *d_tok_off = nullptr, *d_sent_off = nullptr, *d_text_off = nullptr;
+  uint64_t *d_tok_cnt = nullptr, *d_sent_cnt = nullptr, *d_text_cnt = nullptr;  // per-document counts
+  uint64_t *d_scan_ws = nullptr;  // tile sums of the multi-block scan (many documents)
+  uint64_t *d_totals = nullptr;  // [0..3] scan totals, [4] walk steps, [6] invalid UTF-8 bytes, [7] irregular flag,
+                                 // [8..9] as u32[4]: documents to repair after the first pass / after each device-side round
+  uint32_t dev_rounds = 0;       // repair rounds enqueued ahead of time in the last run
+  bool expect_repairs = false;   // the last run needed repairs: enqueue rounds ahead of time in the next one
+  uint32_t round_limit = 0xFFFFFFFFu;  // repair rounds from the host before the one-lane-per-document fallback (DATOK_ROUND_LIMIT)
+  bool acc_primed = false;       // the accumulator block has been cleared whole once (k_symbolize clears it from then on)
+  uint64_t epoch = 0;            // number of the run (k_symbolize marks runs that saw invalid UTF-8 with it)
+  bool expect_eot = false;       // the last run had documents with EOT calls: launch their compaction kernel with the run
+  bool ran_full = false;         // that kernel has run since the last dtk_batch_run
+  uint64_t *h_totals = nullptr;  // pinned
+  uint64_t *h_off_pin = nullptr; // pinned staging of the document offsets (a copy from pageable memory would block until
+                                 // the text copy in front of it has finished: 0.7 ms per 16 MiB batch)
+  // outputs (grown on demand, never inside a run unless a re-launch is needed)
+  uint64_t tok_cap = 0, sent_cap = 0, text_cap = 0;
+  int32_t *d_rstart = nullptr, *d_rend = nullptr, *d_sent = nullptr;
+  uint32_t *d_bstart = nullptr, *d_bend = nullptr, *d_ttok = nullptr, *d_tsent = nullptr;
+  uint32_t *d_sbefore = nullptr, *d_ts_end = nullptr, *d_doc_ns = nullptr;  // renderer inputs (compact)
+  // device rendering of the writer output (dtk_batch_render): workspace + output, grown on demand
+  uint64_t *d_rws = nullptr;  uint64_t rws_cap = 0;   // scans, tile sums, per-text regions (u64 words)
+  uint64_t *d_out_off = nullptr;
+  uint8_t *d_out = nullptr;   uint64_t out_cap = 0;
+  uint64_t out_total = 0;
+  uint64_t n_invalid = 0;     // nonzero: the last run saw invalid UTF-8 (each such byte prints as U+FFFD, 3 bytes)
+  uint32_t render_flags = 0xFFFFFFFFu;  // flags of the rendering held in d_out (none)
+  std::vector<uint8_t> h_out;
+  std::vector<uint64_t> h_out_off;
+  // the exact pass over ST_IRREGULAR documents (normally none): ids, call counts / offsets, calls
+  uint32_t *d_exact_ids = nullptr, *d_exact_cnt = nullptr;
+  uint64_t *d_exact_off = nullptr;
+  DtkCall *d_calls = nullptr;
+  uint32_t exact_cap = 0;
+  uint64_t calls_cap = 0;
+  std::vector<uint32_t> h_exact_ids;
+  std::vector<uint64_t> h_exact_off;
+  std::vector<DtkCall> h_calls;
+  // optional stage timing
+  bool profiling = false;
+  hipEvent_t ev[DTK_N_STAGES + 1] = {};
+  // last run
+  bool ran = false, totals_valid = false;
+  DtkCompactArgs last_args{};
+  dtk_totals totals{};
+  // Results on the host (dtk_batch_result_host): page-locked buffers owned by the batch, filled by one chain of
+  // asynchronous copies on a stream of their own (dl_stream) -- the batch's own stream is free for the next kernels,
+  // the copy engine for the next slice's upload (PCIe is full duplex).  `fields` (DTK_R_*) selects what is copied.
+  // (one buffer per row of host_arrays, dtk_results.cpp)
+  enum { PB_R16, PB_RSTART, PB_REND, PB_BSTART, PB_BEND, PB_BITS, PB_TAIL, PB_SENT, PB_TTOK, PB_TSENT, PB_CSR, PB_STATUS,
+         PB_N };
+  struct PinBuf { void *p = nullptr; size_t cap = 0; } pin[PB_N];
+  PinBuf h_plan;            // staging of the lane plan's tables (plan_lanes)
+  uint32_t fields = DTK_R_ALL;
+  uint32_t *d_r16 = nullptr;      // DTK_R_TOK_RUNE16: the packed rune offsets (filled on the download stream)
+  uint64_t r16_cap = 0;
+  uint64_t max_doc_bytes = 0;     // of the current input (what decides whether the narrow form exists)
+  bool max_doc_valid = false;
+  hipStream_t dl_stream = nullptr;  // created with the first download, unless the caller lends one (a pipeline's slices share one:
+  bool dl_own = false;              //  the runtime maps streams onto four hardware queues, and streams that share a queue serialise)
+  hipEvent_t ev_ran = nullptr;      // behind the last launch of dtk_batch_run (dtk_batch_done)
+  bool ev_ran_valid = false;
+  // Lent streams (dtk_batch_set_streams): the batches of a pipeline share one stream for their kernels and one for their
+  // uploads -- the runtime has four hardware queues, and a pipeline of any depth then needs three (kernels, uploads,
+  // downloads).  The upload's end is an event the kernels wait for.
+  bool stream_own = true;
+  hipStream_t up_stream = nullptr;  // null: uploads run on `stream`
+  hipEvent_t ev_up = nullptr;
+  bool up_pending = false;          // an upload on up_stream has not been waited for yet
+  uint32_t eager_fields = 0;  // the last run's k_to_host was asked for these (0: none); finish() decides whether it counts
+  bool results_changed = false;  // finish() had to touch the result arrays after the run (repair, growth, EOT kernel, exact pass)
+  hipEvent_t ev_dl = nullptr;  // behind the batch's copies on the (possibly shared) download stream
+  bool dl_waited = true;
+  bool dl_begun = false;    // the copies of the last run's results have been enqueued
+  uint32_t dl_fields = 0;   // ... these fields
+};
+
+int pin_fit(dtk_batch::PinBuf &pb, size_t n);
+int wait_own(dtk_batch *b);
+DtkSym sym_of(const dtk_batch *b);
+DtkWalkArgs walk_args(dtk_batch *b);
+int finish(dtk_batch *b);
+int launch_to_host(dtk_batch *b);
+
+// The DTK_R_* arrays the last run wrote: DTK_NO_RUNE_OFFSETS / DTK_NO_BYTE_OFFSETS leave theirs alone.
+inline uint32_t run_fields(const dtk_batch *b) {
+  uint32_t f = ~0u;
+  if (b->last_flags & DTK_NO_RUNE_OFFSETS) f &= ~(uint32_t)(DTK_R_TOK_RUNE | DTK_R_TOK_RUNE16);
+  if (b->last_flags & DTK_NO_BYTE_OFFSETS) f &= ~(uint32_t)DTK_R_TOK_BYTE;
+  return f;
+}
+
+// The last run's output arrays, into the fields of the same names of `o` (dtk_result_view, DtkCompactArgs or
+// DtkExactArgs); what the run does not write is null.  The kernels' arguments also get the renderer's bookkeeping,
+// which any of the offsets-only flags leaves out.
+template <class A>
+void set_outputs(const dtk_batch *b, A &o) {
+  const uint32_t f = run_fields(b);
+  o.tok_off = b->d_tok_off; o.sent_off = b->d_sent_off; o.text_off = b->d_text_off;
+  o.tok_rstart = (f & DTK_R_TOK_RUNE) ? b->d_rstart : nullptr; o.tok_rend = (f & DTK_R_TOK_RUNE) ? b->d_rend : nullptr;
+  o.tok_bstart = (f & DTK_R_TOK_BYTE) ? b->d_bstart : nullptr; o.tok_bend = (f & DTK_R_TOK_BYTE) ? b->d_bend : nullptr;
+  o.sent = b->d_sent; o.text_tok_end = b->d_ttok; o.text_sent_end = b->d_tsent;
+  if constexpr (!std::is_same<A, dtk_result_view>::value) {
+    const bool ro = (b->last_flags & (DTK_OFFSETS_ONLY | DTK_NO_RUNE_OFFSETS | DTK_NO_BYTE_OFFSETS)) != 0;
+    o.tok_sbefore = ro ? nullptr : b->d_sbefore; o.text_s_end = ro ? nullptr : b->d_ts_end;
+    o.doc_ns = ro ? nullptr : b->d_doc_ns;
+  }
+}
+
+#pragma GCC visibility pop

@@ -28,7 +28,7 @@
 // the shipped models have some 170 symbols and 200 distinct entries), else the 16-bit entries themselves.  A code
 // is an index into `lut` (256 entries); DTK_SYM_CONT = no rune starts here.  Half the stream's traffic -- it was 44 %
 // of what a batch moves -- and the lean walk's windows (codes) in 40 instead of 72 bytes of LDS per lane.  The code of a
-// byte below 128 is the byte itself (upload() in dtk_host.cpp; k_symbolize copies those).
+// byte below 128 is the byte itself (upload() in dtk_model.cpp; k_symbolize copies those).
 #define DTK_SYM_CONT 0xFFu
 #ifndef DTK_WIN8
 #define DTK_WIN8 32u  // positions in a lean-walk row of codes (a multiple of 16; the row has 8 bytes more: 40 B)
@@ -124,7 +124,6 @@ struct DtkTableDev {
   uint32_t start;        // image of the reference's state 1
   uint32_t fused;        // matrix: uint32 cells with fused epsilon+rune entries (see MatrixFusedTrans)
   uint32_t ident_guard;  // identity symbol if arcs on `unknown` exist, else 0xFFFFFFFF
-  uint32_t plain_walk;   // 1: always use the general walk loop (env DATOK_PLAIN_WALK, for A/B runs and tests)
   uint32_t da_dense;     // 1: a double-array tokenizer whose transitions were laid out as a (fused) matrix at load
   uint32_t da_len;       // double array: pairs
   uint32_t da_size;      // array[1].check & RESTBIT (datok.go:333-335)
@@ -175,10 +174,8 @@ struct DtkSpecArgs {
   uint32_t *fail_lane;              // per document: first lane that missed its successor's record
   const uint32_t *redo_from;        // repair rounds: first lane to redo per document, or null
   const uint8_t *text;              // input bytes (k_spec_start: whitespace-guided warm-up), or null
-  uint32_t warm_ws;                 // start the warm-up behind the warm_ws-th whitespace run before the chunk (0: fixed)
-  uint32_t warm_min;                // ... looking backwards from chunk start - warm_min
-  uint32_t first_repair;            // repair rounds: 1 in the round that follows the first pass
   uint32_t warm_extend;             // move the warm-up start back to the previous blank, at most this many bytes (0: off)
+  uint32_t first_repair;            // repair rounds: 1 in the round that follows the first pass
   uint32_t lds_words;               // LDS bitmap words per kind for one wave (0: event bits go straight to memory)
   // A repair round enqueued ahead of time (device-side repair): its kernels return at once unless *go != 0
   // (the number of documents the previous verification found broken); null: run.
@@ -309,7 +306,7 @@ struct DtkToHostArgs {
   void *dst[DTK_TOHOST_MAX];           // mapped page-locked host memory
   uint64_t bytes[DTK_TOHOST_MAX];      // size in bytes (count_from < 0), else bytes per element
   int32_t count_from[DTK_TOHOST_MAX];  // < 0: fixed size; 0..2: totals[count_from] elements
-  uint64_t cap[DTK_TOHOST_MAX];        // elements the destination holds (count_from >= 0)
+  uint64_t cap[DTK_TOHOST_MAX];        // elements source and destination hold (count_from >= 0)
   uint32_t n;
   const uint64_t *totals;              // device totals block (scan3)
   const uint32_t *skip_if;             // documents still to repair: nothing is copied unless this is 0 (null: copy)

@@ -1,0 +1,259 @@
+// dtk_results.cpp -- a finished run's results: the device view, the copies to the host (inside the run, k_to_host,
+// or on the download stream), the host view, and rendering.
+#include <algorithm>
+#include <array>
+#include <cstdlib>
+#include <cstring>
+
+#include "dtk_host.h"
+
+namespace {
+// An array that can go to the host: `count` >= 0: totals[count] elements of `size` bytes, in a device array of `cap`
+// elements; < 0: `size` bytes.
+struct HostArray {
+  uint32_t field;  // DTK_R_*
+  int slot;        // dtk_batch::PB_*: its page-locked buffer
+  const void *src;
+  uint64_t size;
+  int count;
+  uint64_t cap;
+  void (*view)(dtk_result_view *o, const void *p);  // where dtk_batch_result_host shows it
+};
+#define VIEW(f) [](dtk_result_view *o, const void *p) { o->f = static_cast<decltype(o->f)>(p); }
+
+// The batch's arrays, in the order their copies are enqueued: the large ones first (k_to_host deals its pieces out to
+// its waves by array; on the download stream the small copies ride behind the large ones).
+std::array<HostArray, dtk_batch::PB_N> host_arrays(const dtk_batch *b) {
+  const uint64_t nd = b->n_docs;
+  const HostArray t[] = {
+      {DTK_R_TOK_RUNE16, dtk_batch::PB_R16, b->d_r16, 4, 0, b->r16_cap, VIEW(tok_r16)},
+      {DTK_R_TOK_RUNE, dtk_batch::PB_RSTART, b->d_rstart, 4, 0, b->tok_cap, VIEW(tok_rstart)},
+      {DTK_R_TOK_RUNE, dtk_batch::PB_REND, b->d_rend, 4, 0, b->tok_cap, VIEW(tok_rend)},
+      {DTK_R_TOK_BYTE, dtk_batch::PB_BSTART, b->d_bstart, 4, 0, b->tok_cap, VIEW(tok_bstart)},
+      {DTK_R_TOK_BYTE, dtk_batch::PB_BEND, b->d_bend, 4, 0, b->tok_cap, VIEW(tok_bend)},
+      {DTK_R_EVENTS, dtk_batch::PB_BITS, b->d_bits, (uint64_t)EVB_KINDS * b->bit_words * 4, -1, 0, VIEW(ev_bits)},
+      {DTK_R_EVENTS, dtk_batch::PB_TAIL, b->d_doc_tail, nd * 4, -1, 0, VIEW(doc_tail)},
+      {DTK_R_SENT, dtk_batch::PB_SENT, b->d_sent, 4, 1, b->sent_cap, VIEW(sent)},
+      {DTK_R_TEXTS, dtk_batch::PB_TTOK, b->d_ttok, 4, 2, b->text_cap, VIEW(text_tok_end)},
+      {DTK_R_TEXTS, dtk_batch::PB_TSENT, b->d_tsent, 4, 2, b->text_cap, VIEW(text_sent_end)},
+      // (tok_off | sent_off | text_off lie back to back: dtk_batch_run)
+      {DTK_R_CSR, dtk_batch::PB_CSR, b->d_csr, 3 * (nd + 1) * 8, -1, 0, VIEW(tok_off)},
+      {DTK_R_STATUS, dtk_batch::PB_STATUS, b->d_status, nd * 4, -1, 0, VIEW(status)}};
+  static_assert(sizeof t / sizeof t[0] == dtk_batch::PB_N, "one row per page-locked buffer");
+  std::array<HostArray, dtk_batch::PB_N> r;
+  std::copy(t, t + dtk_batch::PB_N, r.begin());
+  return r;
+}
+}  // namespace
+
+extern "C" int dtk_batch_result_device(dtk_batch *b, dtk_result_view *o) {
+  if (!b || !o) return DTK_E_ARG;
+  int rc = finish(b);
+  if (rc != DTK_OK) return rc;
+  o->tok_r16 = nullptr;  // (host results only)
+  set_outputs(b, *o);
+  o->status = b->d_status; o->ev_bits = b->d_bits; o->ev_words = b->bit_words; o->doc_tail = b->d_doc_tail;
+  o->n_exact = (uint32_t)b->h_exact_ids.size();
+  o->exact_doc = b->d_exact_ids; o->exact_off = b->d_exact_off; o->calls = (const dtk_call *)b->d_calls;
+  return DTK_OK;
+}
+
+extern "C" int dtk_batch_set_result_fields(dtk_batch *b, uint32_t fields) {
+  if (!b || (fields & ~(uint32_t)(DTK_R_ALL | DTK_R_TOK_RUNE16 | DTK_R_EAGER))) return DTK_E_ARG;
+  b->fields = fields;
+  return DTK_OK;
+}
+
+// DTK_R_EAGER: the selected arrays leave for the host inside the run, by a kernel behind the compaction that reads
+// the sizes where they are -- on the device (k_to_host).  Page-locked buffers sized like the device arrays; no more
+// elements are copied than the device array holds (a count beyond it means the compaction wrote nothing there, and
+// finish() grows the arrays and has them copied on the download stream).
+int launch_to_host(dtk_batch *b) {
+  const uint32_t f = b->fields & run_fields(b) & DTK_R_ALL;
+  DtkToHostArgs a{};
+  for (const HostArray &r : host_arrays(b)) {
+    if (!(f & r.field)) continue;
+    dtk_batch::PinBuf &pb = b->pin[r.slot];
+    int rc = pin_fit(pb, (size_t)(r.count >= 0 ? r.cap * r.size : r.size));
+    if (rc != DTK_OK) return rc;
+    void *dp = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&dp, pb.p, 0));
+    a.src[a.n] = r.src; a.dst[a.n] = dp; a.bytes[a.n] = r.size; a.count_from[a.n] = r.count;
+    a.cap[a.n] = r.count >= 0 ? std::min<uint64_t>(pb.cap / r.size, r.cap) : 0;
+    a.n++;
+  }
+  if (a.n == 0) return DTK_OK;
+  a.totals = b->d_totals;
+  a.skip_if = b->last_args.skip_if;
+  a.done = b->d_totals + 11;
+  a.epoch = b->epoch;
+  if (dtk_launch_to_host(&a, b->stream)) return hip_fail(hipGetLastError(), "results to the host");
+  b->eager_fields = f;
+  return DTK_OK;
+}
+
+// Completes the run (as dtk_batch_totals: speculation check, repairs, capacity check -- the batch's stream is idle
+// afterwards) and enqueues the copies of the selected result arrays on the download stream.  Returns at once.
+extern "C" int dtk_batch_set_download_stream(dtk_batch *b, void *stream) {
+  if (!b) return DTK_E_ARG;
+  if (b->dl_begun && !b->dl_waited) { HIP_TRY(hipEventSynchronize(b->ev_dl)); b->dl_waited = true; }
+  if (b->dl_stream && b->dl_own) HIP_TRY(hipStreamDestroy(b->dl_stream));
+  b->dl_stream = (hipStream_t)stream;
+  b->dl_own = false;
+  return DTK_OK;
+}
+
+extern "C" void *dtk_batch_download_stream(dtk_batch *b) {
+  if (!b) return nullptr;
+  if (!b->dl_stream) {
+    if (hipStreamCreateWithFlags(&b->dl_stream, hipStreamNonBlocking) != hipSuccess) { b->dl_stream = nullptr; return nullptr; }
+    b->dl_own = true;
+  }
+  return (void *)b->dl_stream;
+}
+
+extern "C" int dtk_batch_download_begin(dtk_batch *b) {
+  if (!b) return DTK_E_ARG;
+  int rc = finish(b);
+  if (rc != DTK_OK) return rc;
+  uint32_t sel = b->fields & (DTK_R_ALL | DTK_R_TOK_RUNE16);
+  if (sel & DTK_R_TOK_RUNE16) {
+    // the narrow form holds every offset of a document of at most 32 767 bytes; a batch with a longer one gets the
+    // 32-bit arrays in its place
+    if (!b->max_doc_valid) {
+      uint64_t m = 0;
+      for (uint32_t d = 0; d < b->n_docs; d++) m = std::max(m, b->h_doc_off[d + 1] - b->h_doc_off[d]);
+      b->max_doc_bytes = m;
+      b->max_doc_valid = true;
+    }
+    if (b->max_doc_bytes > 32767u) sel = (sel & ~(uint32_t)DTK_R_TOK_RUNE16) | DTK_R_TOK_RUNE;
+  }
+  sel &= run_fields(b);
+  if (b->dl_begun && (b->dl_fields & sel) == sel) return DTK_OK;
+  const uint32_t want = sel & ~(b->dl_begun ? b->dl_fields : 0u);
+  if (!dtk_batch_download_stream(b)) return hip_fail(hipGetLastError(), "download stream");
+  const uint64_t tot[3] = {b->totals.n_tokens, b->totals.n_sent, b->totals.n_texts};
+  for (const HostArray &r : host_arrays(b)) {
+    if (!(want & r.field)) continue;
+    const uint64_t bytes = r.count >= 0 ? tot[r.count] * r.size : r.size;
+    const void *src = r.src;
+    if (r.field == DTK_R_TOK_RUNE16) {
+      if (!bytes) continue;
+      // packed on the download stream itself, in front of its copy: the batch's stream is idle (finish()) and stays free
+      if (b->r16_cap < b->tok_cap) {
+        if (b->d_r16) HIP_TRY(hipFree(b->d_r16));
+        b->d_r16 = nullptr; b->r16_cap = 0;
+        HIP_TRY(hipMalloc((void **)&b->d_r16, std::max<uint64_t>(b->tok_cap, 4) * 4));
+        b->r16_cap = b->tok_cap;
+      }
+      if (dtk_launch_pack_r16(b->d_rstart, b->d_rend, b->d_r16, tot[0], b->dl_stream)) return hip_fail(hipGetLastError(), "pack r16");
+      src = b->d_r16;
+    }
+    rc = pin_fit(b->pin[r.slot], (size_t)bytes);
+    if (rc != DTK_OK) return rc;
+    if (bytes) HIP_TRY(hipMemcpyAsync(b->pin[r.slot].p, src, (size_t)bytes, hipMemcpyDeviceToHost, b->dl_stream));
+  }
+  if (!b->ev_dl) HIP_TRY(hipEventCreateWithFlags(&b->ev_dl, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(b->ev_dl, b->dl_stream));
+  b->dl_waited = false;
+  b->dl_fields = (b->dl_begun ? b->dl_fields : 0u) | want;
+  b->dl_begun = true;
+  return DTK_OK;
+}
+
+extern "C" int dtk_batch_result_host(dtk_batch *b, dtk_result_view *o) {
+  if (!b || !o) return DTK_E_ARG;
+  int rc = dtk_batch_download_begin(b);
+  if (rc != DTK_OK) return rc;
+  if (!b->dl_waited) { HIP_TRY(hipEventSynchronize(b->ev_dl)); b->dl_waited = true; }
+  memset(o, 0, sizeof(*o));
+  for (const HostArray &r : host_arrays(b))
+    if (b->dl_fields & r.field) r.view(o, b->pin[r.slot].p);
+  o->sent_off = o->tok_off ? o->tok_off + (b->n_docs + 1) : nullptr;
+  o->text_off = o->tok_off ? o->tok_off + 2 * ((uint64_t)b->n_docs + 1) : nullptr;
+  o->ev_words = b->bit_words;
+  o->n_exact = (uint32_t)b->h_exact_ids.size();
+  o->exact_doc = b->h_exact_ids.data(); o->exact_off = b->h_exact_off.data(); o->calls = (const dtk_call *)b->h_calls.data();
+  return DTK_OK;
+}
+
+// ---------------------------------------------------------------- rendering
+//
+// NewTokenWriter(w, bits) for every document of the batch, on the device (dtk_render.hip).
+static int render(dtk_batch *b, uint32_t bits) {
+  int rc = finish(b);
+  if (rc != DTK_OK) return rc;
+  if (bits & ~31u) return DTK_E_ARG;
+  if (b->last_flags & (DTK_OFFSETS_ONLY | DTK_NO_RUNE_OFFSETS | DTK_NO_BYTE_OFFSETS)) return DTK_E_STATE;  // the run skipped what the renderer reads
+  // the positions were computed under the run's NEWLINE_AFTER_EOT rule (token_writer.go:66-68)
+  if ((bits ^ b->last_flags) & DTK_NEWLINE_AFTER_EOT) return DTK_E_ARG;
+  bits &= 15u;
+  if (b->render_flags == bits) return DTK_OK;
+  hipStream_t s = b->stream;
+  const uint64_t nt = b->totals.n_tokens, ns = b->totals.n_sent, nx = b->totals.n_texts, nd = b->n_docs;
+  const uint64_t tt = dtk_render_tiles(nt), st = dtk_render_tiles(ns);
+  const uint64_t words = 2 * (nt + 1) + (ns + 1) + 2 * tt + st + (nd + 1) + 4 * (nx + 1) + 8;
+  if (words > b->rws_cap) {
+    if (b->d_rws) HIP_TRY(hipFree(b->d_rws));
+    b->d_rws = nullptr; b->rws_cap = 0;
+    HIP_TRY(hipMalloc((void **)&b->d_rws, (words + words / 8) * 8));
+    b->rws_cap = words + words / 8;
+  }
+  DtkRenderArgs R{};
+  R.text = b->d_text; R.doc_off = b->d_off; R.n_docs = b->n_docs; R.flags = bits;
+  R.tok_off = b->d_tok_off; R.sent_off = b->d_sent_off; R.text_off = b->d_text_off;
+  R.n_tok = nt; R.n_sent = ns; R.n_text = nx;
+  R.rstart = b->d_rstart; R.rend = b->d_rend; R.sent = b->d_sent;
+  R.bstart = b->d_bstart; R.bend = b->d_bend; R.sbefore = b->d_sbefore;
+  R.ttok = b->d_ttok; R.tsent = b->d_tsent; R.ts_end = b->d_ts_end; R.doc_ns = b->d_doc_ns;
+  R.sym = sym_of(b); if (!b->n_invalid) R.sym.base = nullptr;
+  uint64_t *q = b->d_rws;
+  R.A = q; q += nt + 1; R.P = q; q += nt + 1; R.Q = q; q += ns + 1;
+  R.blkA = q; q += tt; R.blkP = q; q += tt; R.blkQ = q; q += st;
+  R.ns_off = q; q += nd + 1;
+  R.tx_base = q; q += nx + 1; R.tx_stream = q; q += nx + 1; R.tx_pos = q; q += nx + 1; R.tx_sent = q; q += nx + 1;
+  R.out_off = b->d_out_off;
+  if (dtk_launch_render(&R, 0, s)) return hip_fail(hipGetLastError(), "render sizes");
+  HIP_TRY(hipMemcpyAsync(b->h_totals + 10, R.tx_base + nx, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint64_t total = b->h_totals[10];
+  if (total > b->out_cap) {
+    if (b->d_out) HIP_TRY(hipFree(b->d_out));
+    b->d_out = nullptr; b->out_cap = 0;
+    HIP_TRY(hipMalloc((void **)&b->d_out, total + total / 8 + 256));
+    b->out_cap = total + total / 8 + 256;
+  }
+  R.out = b->d_out; R.out_total = total;
+  if (total) {
+    HIP_TRY(hipMemsetAsync(b->d_out, '\n', total, s));  // every separator that is not a space
+    if (dtk_launch_render(&R, 1, s)) return hip_fail(hipGetLastError(), "render bytes");
+  }
+  b->out_total = total;
+  b->render_flags = bits;
+  return DTK_OK;
+}
+
+extern "C" int dtk_batch_render_device(dtk_batch *b, uint32_t bits, dtk_render_view *o) {
+  if (!b || !o) return DTK_E_ARG;
+  int rc = render(b, bits);
+  if (rc != DTK_OK) return rc;
+  o->bytes = b->d_out; o->doc_off = b->d_out_off; o->total = b->out_total;
+  return DTK_OK;
+}
+
+extern "C" int dtk_batch_render_host(dtk_batch *b, uint32_t bits, dtk_render_view *o) {
+  if (!b || !o) return DTK_E_ARG;
+  int rc = render(b, bits);
+  if (rc != DTK_OK) return rc;
+  b->h_out.resize(std::max<uint64_t>(b->out_total, 1));
+  b->h_out_off.resize((size_t)b->n_docs + 1);
+  if (b->out_total)
+    HIP_TRY(hipMemcpyAsync(b->h_out.data(), b->d_out, b->out_total, hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipMemcpyAsync(b->h_out_off.data(), b->d_out_off, ((size_t)b->n_docs + 1) * 8, hipMemcpyDeviceToHost,
+                         b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  o->bytes = b->h_out.data(); o->doc_off = b->h_out_off.data(); o->total = b->out_total;
+  return DTK_OK;
+}
+
+extern "C" void dtk_free(void *p) { free(p); }

@@ -141,7 +141,6 @@ struct EventSink {
     c_sev = 0; e_pos = 0xFFFFFFFFu; e_tok = 0;
   }
   __device__ __forceinline__ void put(uint32_t kind, uint32_t pos) {
-    if (DTK_KO & 8) return;
     const uint32_t G = gb + pos, m = 1u << (G & 31u), w = (G >> 5) - w0;
     // (one wave-uniform test keeps the common case free of exec-mask juggling: all lanes inside the LDS range)
     if (__builtin_amdgcn_ballot_w64(w >= lw) == 0ull) {
@@ -202,7 +201,6 @@ struct EventSink {
   // inside the wave's LDS bitmaps (their 64 chunks plus a bit per document boundary; DTK_LDS_BIT_WORDS) -- no window
   // test, no range test.  What a lane reports at or behind its stop position goes through the calls above.
   __device__ __forceinline__ void put_first(uint32_t kind, uint32_t pos) {
-    if (DTK_KO & 8) return;
     // (k_spec_both only runs with LDS bitmaps: without them dtk_batch_run launches start records and walk apart;
     //  gbr = the document's bit base relative to the wave's first LDS word)
     const uint32_t G = gbr + pos;
@@ -232,7 +230,7 @@ struct EventSink {
     if (!text_end) c_text++;
     c_sev += sentence_end ? 0u : 1u;
     if (has_tok) c_sent += sentence_end ? 0u : 1u; else st |= ST_EMPTY_TEXT;
-    if (tailw && !(DTK_KO & 8)) *tailw = (p << 2) | bits;
+    if (tailw) *tailw = (p << 2) | bits;
   }
   template <bool IS_MATRIX>
   __device__ __forceinline__ void tail(uint32_t /*bs*/, uint32_t p, bool sentence_end, bool text_end, bool has_tok) {
@@ -727,7 +725,7 @@ __device__ __forceinline__ void walk_fused(const MatrixFusedTrans &tr, const Dtk
     //  SentenceEnd on its way there; the positions before it need no test, see EventSink::put_first)
     const bool beyond = MODE != MODE_DOC && p >= stop_pos;
     const uint32_t tp_old = tp, F_old = F;
-    if (MODE != MODE_START && !(DTK_KO & 1)) {
+    if (MODE != MODE_START) {
       if (FIRST) {
         if (flush && !beyond) sink.template token_first<IS_MATRIX>(tp, p, ((F ^ 4u) & 7u) != 0);
         if (sentE && !beyond) sink.sentence_first(p, (F & 8u) != 0);
@@ -736,7 +734,7 @@ __device__ __forceinline__ void walk_fused(const MatrixFusedTrans &tr, const Dtk
         if (sentE) sink.template sentence<IS_MATRIX>(bs, p, (F & 8u) != 0);
       }
     }
-    const uint32_t win = (DTK_KO & 2) ? 0u : hi - bs;   // bytes the window holds (before this iteration's rewind)
+    const uint32_t win = hi - bs;   // bytes the window holds (before this iteration's rewind)
     const uint32_t bs_old = bs, p_old = p;
     F = flush ? 12u : (F | (sentE ? 1u : 0u));
     bs = flush ? p_old : bs;
@@ -758,7 +756,7 @@ __device__ __forceinline__ void walk_fused(const MatrixFusedTrans &tr, const Dtk
     // (one chain of bit operations: `||` makes the compiler branch between the tests)
     if (hardfail | eot_now | (beyond & (FIRST ? epsE : flush)) | (flush & (win > DTK_WINDOW)) | (win > DTK_WINDOW_BYTES) |
         over | ((p >= len) & !backtrack)) {
-      if (FIRST && MODE != MODE_START && beyond && !(DTK_KO & 1)) {  // what the common path left to this block
+      if (FIRST && MODE != MODE_START && beyond) {  // what the common path left to this block
         if (flush) sink.template token<IS_MATRIX>(bs_old, tp_old, p_old, ((F_old ^ 4u) & 7u) != 0);
         if (sentE) sink.template sentence<IS_MATRIX>(bs_old, p_old, (F_old & 8u) != 0);
       }
@@ -915,7 +913,7 @@ static int with_trans(const DtkTableDev *tab, bool codes, F &&f) {
       MatrixFusedTrans tr{(const uint32_t *)tab->tab, tab->stride, tab->n_eps, tab->start, tab->ident_guard};
       // (da_dense: a double-array tokenizer laid out as a fused matrix -- the table's walk, datok.go's EOT rules)
       auto call = [&](auto t) { if (tab->da_dense) f(t, std::false_type{}); else f(t, std::true_type{}); };
-      if (tab->ident_guard == 0xFFFFFFFFu && !tab->plain_walk && codes) {  // the lean loop applies
+      if (tab->ident_guard == 0xFFFFFFFFu && codes) {  // the lean loop applies
         MatrixLeanTrans lt;
         static_cast<MatrixFusedTrans &>(lt) = tr;
         call(lt);

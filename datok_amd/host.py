@@ -13,7 +13,6 @@ TOKENS, SENTENCES, TOKEN_POS, SENTENCE_POS, NEWLINE_AFTER_EOT = 1, 2, 4, 8, 16
 SIMPLE = TOKENS | SENTENCES
 # dtk_batch_run only (datok_gpu.h): no renderer bookkeeping / only one kind of token offsets
 OFFSETS_ONLY, NO_BYTE_OFFSETS, NO_RUNE_OFFSETS = 256, 512, 1024
-OFFSETS_ONLY = 256   # Batch.run only: skip the device renderer's bookkeeping
 
 # calls at one cursor position, in the order they fire (flag byte of event_bytes(); datok_gpu.h DTK_EVB_* / DTK_TAIL_*)
 EV_S_EOT, EV_E_EOT, EV_TOK_END, EV_S_EPS, EV_S_EOF, EV_E_EOF = 1, 2, 4, 8, 32, 64
@@ -420,6 +419,7 @@ class Batch:
     R_CSR, R_TOK_RUNE, R_TOK_BYTE, R_SENT, R_TEXTS, R_STATUS, R_EVENTS, R_ALL = 1, 2, 4, 8, 16, 32, 64, 127
     R_TOK_RUNE16 = 128   # the rune offsets as int16 pairs (BatchResult.tok_r16); a batch with a document longer than
                          # 32 767 bytes gets tok_rstart / tok_rend in their place
+    R_EAGER = 256        # the selected arrays leave for the host inside the run (k_to_host) where they fit
 
     def set_result_fields(self, fields=R_ALL):
         """Which arrays result() brings to the host (the others come back empty)."""

@@ -89,7 +89,7 @@ const char *dtk_last_hip_error(void);
 /* Test hook.  The library never reads the environment; the code paths it otherwise picks by model, batch shape or
  * history (general loop instead of the lean one, 16-bit stream entries, the double array's pairs instead of its
  * dense layout, two-launch first pass, ...) can be forced through this call so that the test suite runs over each
- * of them.  key: the name in dtk_host.cpp's table, with or without the "DATOK_" prefix the tests' environment
+ * of them.  key: the name in dtk_model.cpp's table, with or without the "DATOK_" prefix the tests' environment
  * variables carry (datok_amd/_lib.py forwards those); value: an integer as text (NULL = 1).  No switch changes a
  * result.  Set before the models / batches it should affect are created. */
 int dtk_debug_configure(const char *key, const char *value);

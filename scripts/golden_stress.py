@@ -52,6 +52,5 @@ for model in ("tokenizer_de.matok", "tokenizer_en.matok"):
             tot = b.totals()
             res = b.result()
             assert_batch_equals_oracle(om, res, text, off, docs=range(0, n_docs, max(1, n_docs // 512)))
-            print("%s chunk %s warm %d (DATOK_WARM_WS=%s MIN=%s): lanes %d, repair rounds %d, flagged %d" % (
-                model, chunk, warm, os.environ.get("DATOK_WARM_WS", "0"), os.environ.get("DATOK_WARM_MIN", "0"),
-                tot["n_lanes"], tot["repair_rounds"], tot["n_flagged"]), flush=True)
+            print("%s chunk %s warm %d: lanes %d, repair rounds %d, flagged %d" % (
+                model, chunk, warm, tot["n_lanes"], tot["repair_rounds"], tot["n_flagged"]), flush=True)

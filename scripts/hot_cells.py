@@ -50,7 +50,7 @@ def load(path):
 
 def walk(m, text, counts):
     """matrix.go:384-635 on one document (no EOT, no unknown arcs); counts[(t, a)] += 1 per lookup of the device's
-    fused table (dtk_host.cpp layout_matrix: where (t, a) has no arc, t has an epsilon arc to e and (e, a) has one,
+    fused table (dtk_model.cpp layout_matrix: where (t, a) has no arc, t has an epsilon arc to e and (e, a) has one,
     one cell stands for fail + epsilon step + rune)."""
     arr, N, eps, ident = m["arr"], m["N"], m["eps"], m["ident"]
     sigma = m["sigma"]

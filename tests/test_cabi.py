@@ -66,9 +66,10 @@ def test_error_strings_and_constants():
             datok_amd.NEWLINE_AFTER_EOT, datok_amd.SIMPLE) == (1, 2, 4, 8, 16, 3)   # token_writer.go:17-25
 
 
-def test_library_never_reads_the_environment():
+def test_library_never_reads_the_environment_and_knows_only_live_hooks():
     """kernel selection of a shipped library must not depend on the caller's environment.  No getenv in the
-    native sources; the test hooks go through dtk_debug_configure (which this harness feeds from DATOK_* variables)."""
+    native sources; the test hooks go through dtk_debug_configure (which this harness feeds from DATOK_* variables),
+    which knows the live hooks only: the names of removed ones are rejected."""
     for base in (os.path.join("datok_amd", "csrc"), "include"):
         for f in os.listdir(os.path.join(ROOT, base)):
             if f.endswith((".cpp", ".hip", ".h", ".hpp")):
@@ -78,8 +79,9 @@ def test_library_never_reads_the_environment():
     from datok_amd import _lib
     L = datok_amd.lib()
     assert L.dtk_debug_configure(b"DATOK_NO_SUCH_SWITCH", b"1") == _lib.E_ARG
-    assert L.dtk_debug_configure(b"WARM_WS", b"0") == _lib.OK          # (its default: nothing changes)
-    assert L.dtk_debug_configure(b"DATOK_WARM_MIN", b"0") == _lib.OK
+    assert L.dtk_debug_configure(b"DEV_ROUNDS", b"-1") == _lib.OK        # (their defaults: nothing changes)
+    assert L.dtk_debug_configure(b"DATOK_SMALL_MAX", b"-1") == _lib.OK
+    assert L.dtk_debug_configure(b"WARM_WS", b"0") == _lib.E_ARG          # (a finished experiment's switch: gone)
 
 
 def test_python_structs_mirror_the_header(tmp_path):

@@ -650,7 +650,7 @@ def test_kernel_variants_forced_by_environment(env, tmp_path):
 @pytest.mark.gpu
 def test_double_array_dense_layout_and_pairs_path(gpu):
     """A double-array tokenizer is walked through a dense (fused matrix) layout of its own transitions built at load
-    (dtk_host.cpp build_datok) -- every double-array test of this suite runs that way.  DATOK_NO_DENSE=1 keeps the
+    (dtk_model.cpp build_datok) -- every double-array test of this suite runs that way.  DATOK_NO_DENSE=1 keeps the
     {base, check} pairs of the file on the device (DaTrans, two dependent loads per step): the same tests in a
     process of their own, so that path stays exact too."""
     import subprocess
@@ -888,6 +888,37 @@ def test_result_fields_select_what_comes_to_the_host(gpu, oracle_models):
             exp = oracle_doc(om, text2[int(off2[d]):int(off2[d + 1])].tobytes())
             a, e = int(r2.tok_off[d]), int(r2.tok_off[d + 1])
             assert np.array_equal(r2.tok_bstart[a:e], exp["tok_bstart"]) and np.array_equal(r2.tok_bend[a:e], exp["tok_bend"])
+
+
+@pytest.mark.gpu
+def test_eager_results_equal_the_oracle(gpu, oracle_models):
+    """DTK_R_EAGER (the copy to the host inside the run, k_to_host): on a plain corpus, on a run that needs repair
+    rounds, and on a batch with more tokens than its device arrays were created for but fewer than their page-locked
+    buffers hold -- the eager copy must not read behind the device arrays, and the results come by the download."""
+    import datok_amd
+    from datok_amd import corpus
+    B = datok_amd.Batch
+    om = oracle_models("tokenizer_de.matok")
+    tok = gpu("tokenizer_de.matok")
+    words = np.frombuffer(b"a bc " * 40000, dtype=np.uint8)
+    cases = [(corpus.german_docs(300, 1500, seed=23), None),
+             (corpus.german_docs(384, 4096, seed=9), (256, 0)),
+             ((words, np.arange(0, len(words) + 1, len(words) // 8, dtype=np.uint64)), None)]
+    for (text, off), chunking in cases:
+        n_docs = len(off) - 1
+        with B(len(text), n_docs) as b:
+            if chunking:
+                b.set_chunking(chunking[0], chunking[1], extend=0)
+            b.set_result_fields(B.R_ALL | B.R_EAGER)
+            b.set_input(text, off)
+            b.run(tok, 0)
+            tot = b.totals()
+            if chunking:
+                assert tot["repair_rounds"] > 0
+            if text is words:
+                tok_cap = len(text) // 3 + n_docs + 16             # dtk_batch_create
+                assert tok_cap < tot["n_tokens"] <= tok_cap * 5 // 4
+            assert assert_batch_equals_oracle(om, b.result(), text, off) == n_docs
 
 
 @pytest.mark.gpu

@@ -19,6 +19,7 @@ ST_BAD_OFFSET = 64
 EXPORTS = [
     "dtk_device_count", "dtk_set_device", "dtk_strerror", "dtk_last_hip_error",
     "dtk_model_load", "dtk_model_load_mem", "dtk_model_free", "dtk_model_type", "dtk_model_get_info",
+    "dtk_model_info_mem",
     "dtk_batch_create", "dtk_batch_free", "dtk_batch_set_input", "dtk_batch_set_input_device",
     "dtk_batch_run", "dtk_batch_sync", "dtk_batch_stream", "dtk_batch_totals",
     "dtk_batch_set_profiling", "dtk_batch_stage_ms", "dtk_batch_set_chunking", "dtk_batch_set_warm_extend",
@@ -116,6 +117,7 @@ def lib():
     L.dtk_model_type.restype = C.c_char_p
     L.dtk_model_type.argtypes = [vp]
     L.dtk_model_get_info.argtypes = [vp, C.POINTER(ModelInfo)]
+    L.dtk_model_info_mem.argtypes = [C.c_char_p, sz, C.POINTER(ModelInfo)]
     L.dtk_batch_create.argtypes = [u64, u32, C.POINTER(vp)]
     L.dtk_batch_free.argtypes = [vp]
     L.dtk_batch_free.restype = None

@@ -31,7 +31,8 @@ struct DtkDebug {
   int sym16 = 0;         // 16-bit stream entries (and the general loop) although the model's entries fit a code table
   int force_wide = 0;    // 32-bit plain cells for any model (MatrixTrans<uint32_t>)
   int file_columns = 0;  // keep the file's column order
-  int no_fused = 0;      // plain uint16 cells: no fused epsilon + rune cells
+  int no_fused = 0;      // plain cells (uint16, uint32 from 32 767 states on): no fused epsilon + rune cells
+  int wide_fused = 0;    // 64-bit fused cells for any model (else only where the state ids do not fit 15 bits)
   int no_dense = 0;      // walk a double array's {base, check} pairs instead of its dense layout
   int small_max = -1;    // documents of at most this many bytes are compacted one per lane (-1: by batch shape)
   int lds_bits = 1;      // 0: event bits straight to memory
@@ -56,6 +57,7 @@ struct dtk_model {
   uint32_t n_eps_states = 0, max_eps_chain = 0, unknown_used = 0;
   uint64_t device_bytes = 0;
   int device = 0;
+  bool host_only = false;      // dtk_model_info_mem: the host images are built and measured, nothing is copied to a device
   // host copy of the sigma map, for rendering (Go string(rune) of a token surface)
   std::vector<uint32_t> sigma_runes;
   std::vector<uint16_t> sigma_syms;

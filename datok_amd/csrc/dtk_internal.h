@@ -117,12 +117,12 @@ struct DtkTableDev {
   // base (unused upstream, masked by getBase, datok.go:271-273) caches "this
   // index has an epsilon arc" so the probe of datok.go:876 needs no extra load.
   const void *tab;
-  uint32_t entry_bytes;  // 2 or 4 (matrix), 8 (double array)
+  uint32_t entry_bytes;  // matrix: 2 or 4 plain, 4 or 8 fused (dtk_model.cpp pick_encoding); 8 (double array pairs)
   uint32_t stride;       // matrix: cells per row
   uint32_t n_states;     // matrix: highest state id
   uint32_t n_eps;        // matrix: states 1..n_eps have an epsilon arc
   uint32_t start;        // image of the reference's state 1
-  uint32_t fused;        // matrix: uint32 cells with fused epsilon+rune entries (see MatrixFusedTrans)
+  uint32_t fused;        // matrix: cells with fused epsilon+rune entries, of entry_bytes 4 or 8 (FusedCell32 / FusedCell64, dtk_walk_core.h)
   uint32_t ident_guard;  // identity symbol if arcs on `unknown` exist, else 0xFFFFFFFF
   uint32_t da_dense;     // 1: a double-array tokenizer whose transitions were laid out as a (fused) matrix at load
   uint32_t da_len;       // double array: pairs

@@ -55,7 +55,7 @@ extern "C" int dtk_debug_configure(const char *key, const char *value) {
   const int v = value ? atoi(value) : 1;
   const struct { const char *name; int *field; bool flag; } tab[] = {
       {"SYM16", &g_dbg.sym16, true}, {"FORCE_WIDE", &g_dbg.force_wide, true}, {"FILE_COLUMNS", &g_dbg.file_columns, true},
-      {"NO_FUSED", &g_dbg.no_fused, true}, {"NO_DENSE", &g_dbg.no_dense, true}, {"SMALL_MAX", &g_dbg.small_max, false},
+      {"NO_FUSED", &g_dbg.no_fused, true}, {"WIDE_FUSED", &g_dbg.wide_fused, true}, {"NO_DENSE", &g_dbg.no_dense, true}, {"SMALL_MAX", &g_dbg.small_max, false},
       {"LDS_BITS", &g_dbg.lds_bits, false}, {"SPLIT_START", &g_dbg.split_start, false}, {"DEV_ROUNDS", &g_dbg.dev_rounds, false},
       {"COMPACT_FULL", &g_dbg.compact_full, true}, {"CLEAR_KERNEL", &g_dbg.clear_kernel, true},
       {"ROUND_LIMIT", &g_dbg.round_limit, false}, {"DEBUG_REPAIR", &g_dbg.debug_repair, true}};
@@ -150,38 +150,41 @@ static size_t parse_sigma(dtk_model *m, const std::vector<uint8_t> &raw, size_t 
   return off;
 }
 
-static int upload(dtk_model *m, const void *tab, size_t tab_bytes) {
-  HIP_TRY(hipGetDevice(&m->device));
+// What upload() brings to the device besides the table: built on the host first (build_images), so that
+// dtk_model_info_mem can answer for a model without a device.
+struct HostImages {
+  size_t slack = 0;                 // zeroed bytes behind the table
+  uint16_t ascii_dev[256];
+  size_t first = 0, nr = 0;         // the sigma runes >= 256: sigma_runes[first .. first + nr)
+  std::vector<uint16_t> syms_dev;   // their columns
+  std::vector<uint16_t> entries;    // code -> stream entry [256]
+  std::vector<uint8_t> bytes;       // rune < 256 -> code [256], sigma rune >= 256 -> code [nr]
+};
+
+// symbols as the device sees them: the column of the table they index, see layout_matrix
+static uint32_t colof(const dtk_model *m, int sym) {
+  return (sym >= 0 && (size_t)sym < m->col.size()) ? m->col[(size_t)sym] : (uint32_t)sym;
+}
+
+// Everything about the device form of a model that is decided on the host: the symbol tables, the stream's code
+// table, the special symbols as columns, and what the model will hold in HBM.
+static void build_images(dtk_model *m, size_t tab_bytes, HostImages &im) {
   // (2048 cells of slack behind the last row: the lean walk asks for its next cell before it knows that the reader is
   //  at EOF, with whatever stream entry lies behind the document -- any 11-bit symbol index; the cell is not used)
-  const size_t slack = (DTK_SYM_MASK + 1u) * 4u;
-  HIP_TRY(hipMalloc(&m->d_tab, std::max<size_t>(tab_bytes, 16) + slack));
-  HIP_TRY(hipMemset((char *)m->d_tab + tab_bytes, 0, slack));
-  HIP_TRY(hipMemcpy(m->d_tab, tab, tab_bytes, hipMemcpyHostToDevice));
-  // (symbols as the device sees them: the column of the table they index, see layout_matrix)
-  auto colof = [&](int sym) -> uint32_t {
-    return (sym >= 0 && (size_t)sym < m->col.size()) ? m->col[(size_t)sym] : (uint32_t)sym;
-  };
-  uint16_t ascii_dev[256];
-  for (int i = 0; i < 256; i++) ascii_dev[i] = (uint16_t)colof(m->ascii[i]);
-  HIP_TRY(hipMalloc((void **)&m->d_ascii, 256 * sizeof(uint16_t)));
-  HIP_TRY(hipMemcpy(m->d_ascii, ascii_dev, 256 * sizeof(uint16_t), hipMemcpyHostToDevice));
+  const bool cells64 = m->tab.kind == DTK_KIND_MATRIX && m->tab.fused && m->tab.entry_bytes == 8;
+  im.slack = (DTK_SYM_MASK + 1u) * (cells64 ? 8u : 4u);
+  for (int i = 0; i < 256; i++) im.ascii_dev[i] = (uint16_t)colof(m, m->ascii[i]);
   // the device's sorted rune list only holds runes >= 256 (the others go through the 256-entry table)
   size_t first = 0;
   while (first < m->sigma_runes.size() && m->sigma_runes[first] < 256u) first++;
   const size_t nr = m->sigma_runes.size() - first;
-  HIP_TRY(hipMalloc((void **)&m->d_runes, std::max<size_t>(nr, 1) * sizeof(uint32_t)));
-  HIP_TRY(hipMalloc((void **)&m->d_syms, std::max<size_t>(nr, 1) * sizeof(uint16_t)));
-  if (nr) {
-    HIP_TRY(hipMemcpy(m->d_runes, m->sigma_runes.data() + first, nr * sizeof(uint32_t), hipMemcpyHostToDevice));
-    std::vector<uint16_t> syms_dev(nr);
-    for (size_t i = 0; i < nr; i++) syms_dev[i] = (uint16_t)colof(m->sigma_syms[first + i]);
-    HIP_TRY(hipMemcpy(m->d_syms, syms_dev.data(), nr * sizeof(uint16_t), hipMemcpyHostToDevice));
-  }
-  m->device_bytes = tab_bytes + slack + 512 + nr * 6;
+  im.first = first; im.nr = nr;
+  im.syms_dev.resize(nr);
+  for (size_t i = 0; i < nr; i++) im.syms_dev[i] = (uint16_t)colof(m, m->sigma_syms[first + i]);
+  m->device_bytes = tab_bytes + im.slack + 512 + nr * 6;
   {
     // The stream's code table (dtk_internal.h): every entry the symboliser can write for this model, numbered.
-    std::vector<uint16_t> entries;
+    std::vector<uint16_t> &entries = im.entries;
     bool fits = true;
     auto code_of = [&](uint32_t e) -> uint8_t {
       for (size_t i = 0; i < entries.size(); i++)
@@ -190,10 +193,11 @@ static int upload(dtk_model *m, const void *tab, size_t tab_bytes) {
       entries.push_back((uint16_t)e);
       return (uint8_t)(entries.size() - 1);
     };
-    const uint32_t ident = m->identity < 0 ? 0u : colof(m->identity);
-    std::vector<uint8_t> bytes(256 + nr);
+    const uint32_t ident = m->identity < 0 ? 0u : colof(m, m->identity);
+    std::vector<uint8_t> &bytes = im.bytes;
+    bytes.assign(256 + nr, 0);
     for (uint32_t i = 0; i < 256; i++) {  // matrix.go:421-426; a rune of 128..255 takes two bytes
-      const uint32_t e = (ascii_dev[i] & DTK_SYM_MASK) | (i == DTK_EOT ? 1u << DTK_SYM_CLS_SHIFT : 0u) |
+      const uint32_t e = (im.ascii_dev[i] & DTK_SYM_MASK) | (i == DTK_EOT ? 1u << DTK_SYM_CLS_SHIFT : 0u) |
                          ((i < 128 ? 1u : 2u) << DTK_SYM_W_SHIFT);
       // (the code of a byte < 128 is the byte: the symboliser copies those, k_symbolize's light path)
       if (i < 128) { entries.push_back((uint16_t)e); bytes[i] = (uint8_t)i; } else bytes[i] = code_of(e);
@@ -201,7 +205,7 @@ static int upload(dtk_model *m, const void *tab, size_t tab_bytes) {
     uint32_t fffd = (ident & DTK_SYM_MASK) | (3u << DTK_SYM_CLS_SHIFT);
     for (size_t i = 0; i < nr; i++) {
       const uint32_t r = m->sigma_runes[first + i], w = r < 0x800u ? 2u : (r < 0x10000u ? 3u : 4u);
-      const uint32_t e = (colof(m->sigma_syms[first + i]) & DTK_SYM_MASK) | (2u << DTK_SYM_CLS_SHIFT);
+      const uint32_t e = (colof(m, m->sigma_syms[first + i]) & DTK_SYM_MASK) | (2u << DTK_SYM_CLS_SHIFT);
       bytes[256 + i] = code_of(e | (w << DTK_SYM_W_SHIFT));
       if (r == 0xFFFDu) fffd = e;
     }
@@ -211,27 +215,50 @@ static int upload(dtk_model *m, const void *tab, size_t tab_bytes) {
     m->sig.code_fffd1 = code_of(fffd | (1u << DTK_SYM_W_SHIFT));  // an invalid byte decodes to U+FFFD, one byte wide
     m->sig.n_codes = (fits && !g_dbg.sym16) ? (uint32_t)entries.size() : 0u;
     entries.resize(256, 0);  // (DTK_SYM_CONT and the unused codes: width 0)
-    HIP_TRY(hipMalloc(&m->d_codes, 512 + bytes.size()));
-    HIP_TRY(hipMemcpy(m->d_codes, entries.data(), 512, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy((char *)m->d_codes + 512, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
-    m->sig.code_entry = (const uint16_t *)m->d_codes;
-    m->sig.code_lt256 = (const uint8_t *)m->d_codes + 512;
-    m->sig.code_runes = (const uint8_t *)m->d_codes + 768;
     m->device_bytes += 512 + bytes.size();
   }
-  m->sig.ascii = m->d_ascii;
-  m->sig.runes = m->d_runes;
-  m->sig.syms = m->d_syms;
   m->sig.n_runes = (uint32_t)nr;
   // a net without identity symbol (-1, fomafile.go:88): unmapped runes get symbol 0, which has
   // no arcs (matrix.go:459), and no symbol ever equals the identity (matrix.go:478)
-  m->sig.identity = m->identity < 0 ? 0u : colof(m->identity);
+  m->sig.identity = m->identity < 0 ? 0u : colof(m, m->identity);
+  m->tab.epsilon = colof(m, m->epsilon);
+  m->tab.unknown = m->unknown < 0 ? (uint32_t)m->unknown : colof(m, m->unknown);
+  m->tab.identity = m->identity < 0 ? (uint32_t)m->identity : colof(m, m->identity);
+  if (m->tab.ident_guard != 0xFFFFFFFFu) m->tab.ident_guard = colof(m, (int)m->tab.ident_guard);
+}
+
+static int copy_images(dtk_model *m, const void *tab, size_t tab_bytes, const HostImages &im) {
+  HIP_TRY(hipGetDevice(&m->device));
+  HIP_TRY(hipMalloc(&m->d_tab, std::max<size_t>(tab_bytes, 16) + im.slack));
+  HIP_TRY(hipMemset((char *)m->d_tab + tab_bytes, 0, im.slack));
+  HIP_TRY(hipMemcpy(m->d_tab, tab, tab_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMalloc((void **)&m->d_ascii, 256 * sizeof(uint16_t)));
+  HIP_TRY(hipMemcpy(m->d_ascii, im.ascii_dev, 256 * sizeof(uint16_t), hipMemcpyHostToDevice));
+  const size_t nr = im.nr;
+  HIP_TRY(hipMalloc((void **)&m->d_runes, std::max<size_t>(nr, 1) * sizeof(uint32_t)));
+  HIP_TRY(hipMalloc((void **)&m->d_syms, std::max<size_t>(nr, 1) * sizeof(uint16_t)));
+  if (nr) {
+    HIP_TRY(hipMemcpy(m->d_runes, m->sigma_runes.data() + im.first, nr * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_syms, im.syms_dev.data(), nr * sizeof(uint16_t), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMalloc(&m->d_codes, 512 + im.bytes.size()));
+  HIP_TRY(hipMemcpy(m->d_codes, im.entries.data(), 512, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy((char *)m->d_codes + 512, im.bytes.data(), im.bytes.size(), hipMemcpyHostToDevice));
+  m->sig.code_entry = (const uint16_t *)m->d_codes;
+  m->sig.code_lt256 = (const uint8_t *)m->d_codes + 512;
+  m->sig.code_runes = (const uint8_t *)m->d_codes + 768;
+  m->sig.ascii = m->d_ascii;
+  m->sig.runes = m->d_runes;
+  m->sig.syms = m->d_syms;
   m->tab.tab = m->d_tab;
-  m->tab.epsilon = colof(m->epsilon);
-  m->tab.unknown = m->unknown < 0 ? (uint32_t)m->unknown : colof(m->unknown);
-  m->tab.identity = m->identity < 0 ? (uint32_t)m->identity : colof(m->identity);
-  if (m->tab.ident_guard != 0xFFFFFFFFu) m->tab.ident_guard = colof((int)m->tab.ident_guard);
   return DTK_OK;
+}
+
+// the device form of a model whose table image is `tab`: built on the host, then copied (unless nobody asked for a device)
+static int upload(dtk_model *m, const void *tab, size_t tab_bytes) {
+  HostImages im;
+  build_images(m, tab_bytes, im);
+  return m->host_only ? DTK_OK : copy_images(m, tab, tab_bytes, im);
 }
 
 bool special_ids_ok(const dtk_model *m) {
@@ -242,6 +269,26 @@ bool special_ids_ok(const dtk_model *m) {
          (m->identity != m->unknown || m->identity < 0) && m->epsilon != m->identity;
 }
 
+
+// The cell encoding of a matrix table with states 1..N and S symbols (layout_matrix; build_datok asks before it
+// densifies a double array).
+//   FUSED32  15-bit state ids: target | nontoken<<15 | via<<16 | fused<<31 in one uint32
+//   FUSED64  larger automata: uint2, .x = target[29:0] | nontoken<<30 | fused<<31, .y = via.  The lean loop addresses a
+//            cell by a 32-bit BYTE offset that it gets from one 24-bit multiply-add (DTK_TAB, dtk_walk_core.h), so this
+//            form applies when   N + 1 < 2^24   and   ((N + 1) * stride + 2048) * 8 < 2^32   (2048: the slack cells)
+//   PLAIN16 / PLAIN32  target | nontoken in the top bit, no fused cells: what DATOK_NO_FUSED / DATOK_FORCE_WIDE select
+//            for the tests, and what a table beyond the 32-bit byte offset keeps
+enum CellEnc { ENC_PLAIN16, ENC_PLAIN32, ENC_FUSED32, ENC_FUSED64 };
+static uint32_t stride_of(uint64_t S) { return (uint32_t)((S + 7) & ~7ull); }
+static CellEnc pick_encoding(uint64_t N, uint64_t S) {
+  const bool fits15 = (N + 1) <= 0x7FFFu;
+  if (g_dbg.force_wide) return ENC_PLAIN32;
+  if (g_dbg.no_fused) return fits15 ? ENC_PLAIN16 : ENC_PLAIN32;
+  if (fits15 && !g_dbg.wide_fused) return ENC_FUSED32;
+  const bool fits64 = (N + 1) < (1ull << 24) && ((N + 1) * stride_of(S) + (DTK_SYM_MASK + 1u)) * 8ull < (1ull << 32);
+  if (fits64) return ENC_FUSED64;
+  return fits15 ? ENC_FUSED32 : ENC_PLAIN32;
+}
 
 // ParseMatrix (matrix.go:235-337)
 static int build_matrix(dtk_model *m, const std::vector<uint8_t> &raw) {
@@ -302,10 +349,9 @@ int layout_matrix(dtk_model *m, const std::vector<uint32_t> &arr, uint64_t n_sta
     m->max_eps_chain = best;
   }
 
-  // 32-bit cells for automata with 32767 states or more; DATOK_FORCE_WIDE=1 selects them for any
-  // model (no shipped model is that large: this is how the tests reach MatrixTrans<uint32_t>)
-  const bool wide = (N + 1) > 0x7FFFu || g_dbg.force_wide;
-  const uint32_t stride = (uint32_t)((S + 7) & ~7ull);
+  // the cell encoding: fused cells of 32 bits where the state ids fit 15, of 64 bits beyond (pick_encoding)
+  const CellEnc enc = pick_encoding(N, S);
+  const uint32_t stride = stride_of(S);
   const size_t cells_total = (size_t)(N + 1) * stride;
   // Columns: the symbols of running text first -- blank, the lower-case letters by frequency, full stop, comma,
   // newline, umlauts, digits, capitals --, so that the cells a row is mostly asked for share one or two cache lines
@@ -331,14 +377,33 @@ int layout_matrix(dtk_model *m, const std::vector<uint32_t> &arr, uint64_t n_sta
     for (uint64_t a = 1; a < S; a++)
       if (col[a] == 0xFFFFu) col[a] = (uint16_t)next_col++;
   }
-  // 15-bit state ids: uint32 cells with fused epsilon+rune entries (MatrixFusedTrans);
-  // DATOK_NO_FUSED=1 keeps the plain uint16 table (for A/B measurements)
-  const bool fused = !wide && !g_dbg.no_fused;
-  const size_t cell_bytes = (wide || fused) ? 4 : 2;
+  const bool fused = enc == ENC_FUSED32 || enc == ENC_FUSED64;
+  const size_t cell_bytes = enc == ENC_FUSED64 ? 8 : (enc == ENC_PLAIN16 ? 2 : 4);
   std::vector<uint8_t> host(cells_total * cell_bytes, 0);
-  auto put = [&](size_t at, uint32_t v) {
-    if (cell_bytes == 4) memcpy(host.data() + at * 4, &v, 4);
-    else { uint16_t h = (uint16_t)v; memcpy(host.data() + at * 2, &h, 2); }
+  // a cell: target, nontoken flag, and for a fused cell the epsilon target it goes through (else via = 0)
+  auto put = [&](size_t at, uint32_t tgt, bool nontoken, uint32_t via) {
+    switch (enc) {
+      case ENC_FUSED64: {
+        const uint32_t v[2] = {tgt | (nontoken ? 0x40000000u : 0u) | (via ? 0x80000000u : 0u), via};
+        memcpy(host.data() + at * 8, v, 8);
+        break;
+      }
+      case ENC_FUSED32: {
+        const uint32_t v = tgt | (nontoken ? 0x8000u : 0u) | (via ? 0x80000000u | (via << 16) : 0u);
+        memcpy(host.data() + at * 4, &v, 4);
+        break;
+      }
+      case ENC_PLAIN32: {
+        const uint32_t v = tgt | (nontoken ? DTK_FIRSTBIT : 0u);
+        memcpy(host.data() + at * 4, &v, 4);
+        break;
+      }
+      case ENC_PLAIN16: {
+        const uint16_t h = (uint16_t)(tgt | (nontoken ? 0x8000u : 0u));
+        memcpy(host.data() + at * 2, &h, 2);
+        break;
+      }
+    }
   };
   for (uint64_t a = 1; a < S; a++) {
     for (uint64_t t = 1; t <= N; t++) {
@@ -347,13 +412,11 @@ int layout_matrix(dtk_model *m, const std::vector<uint32_t> &arr, uint64_t n_sta
       if (tgt == 0) continue;
       if (tgt > N) return DTK_E_MODEL;
       if ((int)a == m->unknown) m->unknown_used = 1;
-      const size_t at = (size_t)newid[t] * stride + col[a];
-      if (wide) put(at, newid[tgt] | (x & DTK_FIRSTBIT));
-      else put(at, newid[tgt] | ((x & DTK_FIRSTBIT) ? 0x8000u : 0u));
+      put((size_t)newid[t] * stride + col[a], newid[tgt], (x & DTK_FIRSTBIT) != 0, 0u);
     }
   }
   if (fused) {
-    // (t, a) empty, t --epsilon--> e, (e, a) present:  1<<31 | e<<16 | cell(e, a)
+    // (t, a) empty, t --epsilon--> e, (e, a) present: the fused cell  cell(e, a) through e
     for (uint64_t t = 1; t <= N; t++) {
       const uint32_t e = cell((uint64_t)m->epsilon, t) & ~DTK_FIRSTBIT;
       if (e == 0 || e > N) continue;
@@ -363,8 +426,7 @@ int layout_matrix(dtk_model *m, const std::vector<uint32_t> &arr, uint64_t n_sta
         const uint32_t x2 = cell(a, e);
         const uint32_t tgt2 = x2 & ~DTK_FIRSTBIT;
         if (tgt2 == 0 || tgt2 > N) continue;
-        put((size_t)newid[t] * stride + col[a],
-            0x80000000u | (newid[e] << 16) | newid[tgt2] | ((x2 & DTK_FIRSTBIT) ? 0x8000u : 0u));
+        put((size_t)newid[t] * stride + col[a], newid[tgt2], (x2 & DTK_FIRSTBIT) != 0, newid[e]);
       }
     }
   }
@@ -439,11 +501,11 @@ static int build_datok(dtk_model *m, const std::vector<uint8_t> &raw) {
     }
   }
   // The double array is a compressed encoding of the same kind of automaton the matrix holds dense: a shipped
-  // model has some 20 000 states hidden in its 2.9 million pairs.  If they fit the fused cells (15-bit state ids),
-  // the device walks them as a matrix -- one load per step instead of two dependent ones, the lean loop, fused
-  // epsilon cells -- under the double array's own rules for EOT (datok.go:1019-1030; walk_fused<.., IS_MATRIX =
-  // false>, compaction and replay go by m->kind).  DATOK_NO_DENSE=1 keeps the pairs (DaTrans; what the tests of that
-  // path set).
+  // model has some 20 000 states hidden in its 2.9 million pairs.  If they fit the fused cells (pick_encoding: 15-bit
+  // state ids in 32-bit cells, 64-bit cells beyond), the device walks them as a matrix -- one load per step instead of
+  // two dependent ones, the lean loop, fused epsilon cells -- under the double array's own rules for EOT
+  // (datok.go:1019-1030; walk_fused<.., IS_MATRIX = false>, compaction and replay go by m->kind).  DATOK_NO_DENSE=1
+  // keeps the pairs (DaTrans; what the tests of that path set).
   // (only with fused cells: the lean loop and the fused general loop carry the double array's EOT rules; the plain
   //  matrix encodings that DATOK_NO_FUSED / DATOK_FORCE_WIDE select for the tests are not run with them)
   if (!g_dbg.no_dense && !g_dbg.no_fused && !g_dbg.force_wide) {
@@ -486,7 +548,10 @@ static int build_datok(dtk_model *m, const std::vector<uint8_t> &raw) {
         if (ok && t != 0 && id[t] == 0) {
           id[t] = (uint32_t)order.size();
           order.push_back(t);
-          ok = order.size() <= 0x7FFFu;    // the fused cells' 15-bit state ids
+          if (order.size() > 0x7FFFu) {    // (the 64-bit cells' limits only matter beyond the 15-bit ids)
+            const CellEnc enc = pick_encoding(order.size() - 1, S);
+            ok = enc == ENC_FUSED32 || enc == ENC_FUSED64;  // the fused cells must hold the reachable states
+          }
         }
         trans.push_back(ok && t != 0 ? (id[t] | (x & DTK_FIRSTBIT)) : 0u);
       }
@@ -518,22 +583,38 @@ static int build_datok(dtk_model *m, const std::vector<uint8_t> &raw) {
 }
 
 
-extern "C" int dtk_model_load_mem(const void *gz_bytes, size_t n, dtk_model **out) {
-  if (!gz_bytes || !out) return DTK_E_ARG;
-  *out = nullptr;
-  if (dtk_device_count() <= 0) return DTK_E_NO_DEVICE;
+// gunzip, sniff the magic (fomafile.go:476-482), parse, lay out: the device copy too unless m->host_only
+static int build_model(dtk_model *m, const void *gz_bytes, size_t n) {
   std::vector<uint8_t> raw;
   int rc = gunzip((const uint8_t *)gz_bytes, n, raw);
   if (rc != DTK_OK) return rc;
   if (raw.size() < 5) return DTK_E_FORMAT;
+  if (memcmp(raw.data(), "MATOK", 5) == 0) return build_matrix(m, raw);      // fomafile.go:476
+  if (memcmp(raw.data(), "DATOK", 5) == 0) return build_datok(m, raw);       // fomafile.go:478
+  if (raw.size() >= 10 && memcmp(raw.data(), "##foma-net", 10) == 0) return build_foma(m, raw);
+  return DTK_E_FORMAT;                                                       // fomafile.go:482
+}
+
+extern "C" int dtk_model_load_mem(const void *gz_bytes, size_t n, dtk_model **out) {
+  if (!gz_bytes || !out) return DTK_E_ARG;
+  *out = nullptr;
+  if (dtk_device_count() <= 0) return DTK_E_NO_DEVICE;
   dtk_model *m = new dtk_model();
-  if (memcmp(raw.data(), "MATOK", 5) == 0) rc = build_matrix(m, raw);      // fomafile.go:476
-  else if (memcmp(raw.data(), "DATOK", 5) == 0) rc = build_datok(m, raw);  // fomafile.go:478
-  else if (raw.size() >= 10 && memcmp(raw.data(), "##foma-net", 10) == 0) rc = build_foma(m, raw);
-  else rc = DTK_E_FORMAT;                                                  // fomafile.go:482
+  const int rc = build_model(m, gz_bytes, n);
   if (rc != DTK_OK) { dtk_model_free(m); return rc; }
   *out = m;
   return DTK_OK;
+}
+
+// Which path will this model take: the image is parsed and laid out exactly as dtk_model_load_mem does it, and
+// nothing is copied anywhere.  Host only: needs no device.
+extern "C" int dtk_model_info_mem(const void *gz_bytes, size_t n, dtk_model_info *out) {
+  if (!gz_bytes || !out) return DTK_E_ARG;
+  dtk_model m;
+  m.host_only = true;
+  const int rc = build_model(&m, gz_bytes, n);
+  if (rc != DTK_OK) return rc;
+  return dtk_model_get_info(&m, out);
 }
 
 extern "C" int dtk_model_load(const char *path, dtk_model **out) {

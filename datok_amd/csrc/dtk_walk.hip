@@ -492,8 +492,8 @@ extern "C" int dtk_launch_exact(const DtkTableDev *tab, const DtkExactArgs *args
   return with_trans(tab, args->sym.lut != nullptr, [&](auto tr, auto is_matrix) {
     using TR = decltype(tr);
     if constexpr (TR::LEAN) {
-      const MatrixFusedTrans base = tr;
-      hipLaunchKernelGGL((k_exact_doc<MatrixFusedTrans, decltype(is_matrix)::value>), dim3(blocks), dim3(WAVE), 0, s, base, *args,
+      const typename TR::general base = tr;  // (the exact pass walks the general loop)
+      hipLaunchKernelGGL((k_exact_doc<typename TR::general, decltype(is_matrix)::value>), dim3(blocks), dim3(WAVE), 0, s, base, *args,
                          tab->epsilon, tab->unknown, tab->identity);
     } else {
       hipLaunchKernelGGL((k_exact_doc<TR, decltype(is_matrix)::value>), dim3(blocks), dim3(WAVE), 0, s, tr, *args,

@@ -33,13 +33,40 @@ struct MatrixTrans {
   }
 };
 
-// Matrix with fused cells (uint32): where state t has an epsilon arc to e and no arc on
-// symbol a, but e has one, the cell (t, a) holds  1<<31 | e<<16 | cell(e, a).  The walk then
-// does in one lookup what the reference does in three (matrix.go:472-497 fail + backtrack to
-// the state remembered at this very rune, :563-576 epsilon step, :579-591 the rune from e).
-// Only built when state ids fit 15 bits.
-struct MatrixFusedTrans {
-  const uint32_t *tab;
+// Matrix with fused cells: where state t has an epsilon arc to e and no arc on symbol a, but e has one, the cell
+// (t, a) holds cell(e, a) together with e ("via") and a mark.  The walk then does in one lookup what the reference
+// does in three (matrix.go:472-497 fail + backtrack to the state remembered at this very rune, :563-576 epsilon
+// step, :579-591 the rune from e).
+// Two cell formats (dtk_model.cpp, pick_encoding), the loops below are written over their accessors.  Both keep the
+// three cases in the sign of one 32-bit word -- head < 0 fused, > 0 plain, == 0 no arc:
+//   FusedCell32  state ids of 15 bits:  target | nontoken<<15 | via<<16 | fused<<31
+//   FusedCell64  32 767 states and more, one global_load_dwordx2:
+//                .x = target[29:0] | nontoken<<30 | fused<<31,  .y = via (0 in a plain cell)
+//                (via in a word of its own: no shift, no mask, and head / target / nontoken read the word the sign
+//                 test reads -- the wide loop has the instructions of the narrow one minus the via extraction)
+struct FusedCell32 {
+  typedef uint32_t raw;
+  static constexpr uint32_t SHIFT = 2;  // log2 of the cell size
+  static __device__ __forceinline__ raw none() { return 0u; }
+  static __device__ __forceinline__ uint32_t head(raw x) { return x; }
+  static __device__ __forceinline__ uint32_t target(raw x) { return x & 0x7FFFu; }
+  static __device__ __forceinline__ uint32_t via(raw x) { return (x >> 16) & 0x7FFFu; }
+  static __device__ __forceinline__ bool nontoken(raw x) { return (x & 0x8000u) != 0u; }
+};
+struct FusedCell64 {
+  typedef uint2 raw;
+  static constexpr uint32_t SHIFT = 3;
+  static __device__ __forceinline__ raw none() { return make_uint2(0u, 0u); }
+  static __device__ __forceinline__ uint32_t head(raw x) { return x.x; }
+  static __device__ __forceinline__ uint32_t target(raw x) { return x.x & 0x3FFFFFFFu; }
+  static __device__ __forceinline__ uint32_t via(raw x) { return x.y; }
+  static __device__ __forceinline__ bool nontoken(raw x) { return (x.x & 0x40000000u) != 0u; }
+};
+
+template <typename CELL>
+struct FusedTransOf {
+  typedef CELL cell;
+  const typename CELL::raw *tab;
   uint32_t stride, n_eps, start;
   uint32_t ident_guard;  // the identity symbol if the model has arcs on `unknown`, else no symbol
   static constexpr bool FUSED = true;
@@ -50,19 +77,28 @@ struct MatrixFusedTrans {
   // via: 0, or the epsilon target e the fused cell goes through
   __device__ __forceinline__ bool step(uint32_t t0, uint32_t, uint32_t a, uint32_t &t, uint32_t &aux,
                                        bool &nontoken, uint32_t &st, uint32_t &via) const {
-    const uint32_t x = tab[(size_t)t0 * stride + a];
-    t = x & 0x7FFFu;
-    nontoken = (x & 0x8000u) != 0;
-    via = x >> 31 ? (x >> 16) & 0x7FFFu : 0u;
+    const typename CELL::raw x = tab[(size_t)t0 * stride + a];
+    t = CELL::target(x);
+    nontoken = CELL::nontoken(x);
+    via = CELL::head(x) >> 31 ? CELL::via(x) : 0u;
     aux = 0;
     (void)st;
     return t != 0;
   }
 };
+// (named types, not aliases: the kernels' names carry them)
+struct MatrixFusedTrans : FusedTransOf<FusedCell32> {};    // built when state ids fit 15 bits
+struct MatrixFused64Trans : FusedTransOf<FusedCell64> {};  // ... and beyond
 
-// The same table walked by the lean loop (walk_fused): chosen by the launcher when no state has an
-// arc on `unknown` (a separate type so that the kernels only carry one loop: fewer registers).
+// The same tables walked by the lean loop (walk_fused): chosen by the launcher when no state has an
+// arc on `unknown` (separate types so that the kernels only carry one loop: fewer registers).
+// (k_spec_both is built for DTK_WALK_OCC waves per SIMD with either: the wide loop needs no more registers)
 struct MatrixLeanTrans : MatrixFusedTrans {
+  typedef MatrixFusedTrans general;
+  static constexpr bool LEAN = true;
+};
+struct MatrixLean64Trans : MatrixFused64Trans {
+  typedef MatrixFused64Trans general;
   static constexpr bool LEAN = true;
 };
 
@@ -566,14 +602,16 @@ extern "C" int dtk_probe_read(unsigned long long *out, int reset) {
 }
 #endif
 
-template <int MODE, bool FIRST = false, bool IS_MATRIX = true>
-__device__ __forceinline__ void walk_fused(const MatrixFusedTrans &tr, const DtkSym &sym,
+template <int MODE, bool FIRST = false, bool IS_MATRIX = true, typename TRANS = MatrixFusedTrans>
+__device__ __forceinline__ void walk_fused(const TRANS &tr, const DtkSym &sym,
                                            uint64_t off, uint32_t len, DtkLaneState init, uint32_t stop_pos,
                                            EventSink &sink, uint32_t epsilon, uint32_t cap, DtkLaneState &fin,
                                            uint32_t &st_out, uint32_t &steps_out, uint16_t *win_row,
                                            const uint16_t *lut) {
+  typedef typename TRANS::cell CELL;       // the cell format: FusedCell32 / FusedCell64
+  typedef typename CELL::raw cell_t;
   const DtkSymAt s{sym, off};
-  const uint32_t *__restrict__ tab = tr.tab;
+  const cell_t *__restrict__ tab = tr.tab;
   const uint32_t stride = tr.stride, n_eps = tr.n_eps;
   uint32_t t = init.t;
   uint32_t p = init.p, tp = init.p, bs = init.p, hi = init.p;
@@ -607,23 +645,23 @@ __device__ __forceinline__ void walk_fused(const MatrixFusedTrans &tr, const Dtk
     if (p >= len) {
       bool first_ = true;
       while (t <= n_eps && !done) {
-        const uint32_t x_ = tab[__umul24(t, stride) + epsilon];
+        const cell_t x_ = tab[__umul24(t, stride) + epsilon];
         const bool ov_ = __builtin_usub_overflow(budget, 1u, &budget);
-        if ((int32_t)x_ <= 0) { st |= ST_BAD_MODEL; done = true; break; }
+        if ((int32_t)CELL::head(x_) <= 0) { st |= ST_BAD_MODEL; done = true; break; }
         if (p > tp) { /* matrix.go:565-572 */
           if (MODE != MODE_START) sink.template token<IS_MATRIX>(bs, tp, p, ((F ^ 4u) & 7u) != 0);
           F = 12u;
           if (hi - bs > DTK_WINDOW && count_runes(s, bs, hi) > DTK_WINDOW) st |= ST_WINDOW_OVERFLOW;
           tp = p; bs = p; eps_t = 0;
           if (MODE != MODE_DOC && p >= stop_pos) {
-            fin.p = p; fin.t = x_ & 0x7FFFu; fin.aux = 0; fin.flags = init.flags & LANE_F_OK;
+            fin.p = p; fin.t = CELL::target(x_); fin.aux = 0; fin.flags = init.flags & LANE_F_OK;
             done = true;
           }
         } else { /* matrix.go:573-576 */
           if (MODE != MODE_START) sink.template sentence<IS_MATRIX>(bs, p, (F & 8u) != 0);
           F |= 1u;
         }
-        t = x_ & 0x7FFFu;
+        t = CELL::target(x_);
         if (eot_stale && first_ && !done) { /* matrix.go:593-605 behind the first successful step, see the hard-fail block */
           /* (a TextEnd behind a Token that ends at the same position: rows in call order, the exact pass) */
           if (MODE != MODE_START) sink.out_of_order();
@@ -652,11 +690,13 @@ __device__ __forceinline__ void walk_fused(const MatrixFusedTrans &tr, const Dtk
   // between a cell's arrival and the next request, and a wave issues in order.  What the rare block decides (hard
   // fail, EOT, EOF drain) is not known yet when the request leaves: it asks again.
   //   x  : the cell (t, e)          en : the stream entry behind the rune at p (position p + width(e))
-  uint32_t x = 0, en = 0;
-#define DTK_TAB(t_, e_) (*reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(tab) +                  \
-                                                            ((__umul24((t_), stride) + ((e_) & DTK_SYM_MASK)) << 2)))
-  // the fused table is at most 2^15 states x 2^11 symbols x 4 B: a 32-bit byte offset from the
-  // uniform base (one 24-bit multiply-add) instead of 64-bit address arithmetic
+  cell_t x = CELL::none();
+  uint32_t en = 0;
+#define DTK_TAB(t_, e_) (*reinterpret_cast<const cell_t *>(reinterpret_cast<const char *>(tab) +                    \
+                                                          ((__umul24((t_), stride) + ((e_) & DTK_SYM_MASK)) << CELL::SHIFT)))
+  // the fused table is at most 2^15 states x 2^11 symbols x 4 B, resp. what pick_encoding (dtk_model.cpp) admits to
+  // the 64-bit cells: a 32-bit byte offset from the uniform base (one 24-bit multiply-add) instead of 64-bit
+  // address arithmetic
   if (!done) {
     x = DTK_TAB(t, e);
     const uint32_t pn0 = p + ((e >> DTK_SYM_W_SHIFT) & 7u);
@@ -676,10 +716,11 @@ __device__ __forceinline__ void walk_fused(const MatrixFusedTrans &tr, const Dtk
     const bool he = t <= n_eps;
     eps_t = he ? t : eps_t; eps_p = he ? p : eps_p;
     const bool r = w == 0u;
-    const uint32_t tgt = x & 0x7FFFu, via = (x >> 16) & 0x7FFFu;
-    const bool comp = (int32_t)x < 0;                   // a fused cell: the epsilon arc of t, then the rune from there
-    const bool plain = (int32_t)x > 0;
-    const bool fail = x == 0u;
+    const uint32_t xh = CELL::head(x);                  // the word that says fused / plain / no arc
+    const uint32_t tgt = CELL::target(x), via = CELL::via(x);
+    const bool comp = (int32_t)xh < 0;                  // a fused cell: the epsilon arc of t, then the rune from there
+    const bool plain = (int32_t)xh > 0;
+    const bool fail = xh == 0u;
     const bool advance = comp || (plain && !r);         // the rune is consumed, matrix.go:579-591
     const bool backtrack = fail && !r && eps_t != 0;    // matrix.go:487-497
     // ---- where the walk goes, and the request for its cell
@@ -687,15 +728,15 @@ __device__ __forceinline__ void walk_fused(const MatrixFusedTrans &tr, const Dtk
     const uint32_t p_n = backtrack ? eps_p : (advance ? pn : p);
     // right after a backtrack the bare epsilon symbol: width 0, that iteration consumes nothing (matrix.go:487-497)
     const uint32_t e_n = backtrack ? epsilon : en;
-    const uint32_t x_n = DTK_TAB(t_n, e_n);
+    const cell_t x_n = DTK_TAB(t_n, e_n);
     // nontoken && (comp || (advance && p == tp)), matrix.go:584-588.  (As lane masks combined in scalar registers,
     //  and here, in the block of the comparisons: written with && / || or & / | further down the compiler builds
     //  the predicate from 0/1 integers in vector registers, seven instructions instead of two.)
-    const unsigned long long m_comp = __builtin_amdgcn_ballot_w64((int32_t)x < 0),
-                             m_adv = m_comp | (__builtin_amdgcn_ballot_w64((int32_t)x > 0) & ~__builtin_amdgcn_ballot_w64(w == 0u));
+    const unsigned long long m_comp = __builtin_amdgcn_ballot_w64((int32_t)xh < 0),
+                             m_adv = m_comp | (__builtin_amdgcn_ballot_w64((int32_t)xh > 0) & ~__builtin_amdgcn_ballot_w64(w == 0u));
     // (a fused cell's rune is the first of its token unless the walk has backtracked to a slot BEHIND the token
     //  start -- bufft > buffc, the reference's own odd case: then its epsilon half neither flushes nor rewinds)
-    const unsigned long long m_skip = __builtin_amdgcn_ballot_w64((x & 0x8000u) != 0u) &
+    const unsigned long long m_skip = __builtin_amdgcn_ballot_w64(CELL::nontoken(x)) &
                                       ((m_comp & __builtin_amdgcn_ballot_w64(p > tp)) | (m_adv & __builtin_amdgcn_ballot_w64(p == tp)));
     uint32_t code_n;  // (its entry is looked up at the end of the iteration: the code has arrived by then)
     {
@@ -873,7 +914,7 @@ __device__ __forceinline__ void walk_any(const TRANS &tr, const DtkSym &sym, uin
                                          DtkLaneState &fin, uint32_t &st_out, uint32_t &steps_out,
                                          uint16_t *win_row, const uint16_t *lut) {
   if constexpr (TRANS::LEAN)
-    walk_fused<MODE, FIRST, IS_MATRIX>(tr, sym, off, len, init, stop_pos, sink, epsilon, cap, fin, st_out, steps_out, win_row, lut);
+    walk_fused<MODE, FIRST, IS_MATRIX, TRANS>(tr, sym, off, len, init, stop_pos, sink, epsilon, cap, fin, st_out, steps_out, win_row, lut);
   else
     walk_lane<TRANS, IS_MATRIX, MODE>(tr, sym, off, len, init, stop_pos, sink, epsilon, unknown, identity, cap,
                                       fin, st_out, steps_out, win_row);
@@ -910,16 +951,21 @@ template <typename F>
 static int with_trans(const DtkTableDev *tab, bool codes, F &&f) {
   if (tab->kind == DTK_KIND_MATRIX) {
     if (tab->fused) {
-      MatrixFusedTrans tr{(const uint32_t *)tab->tab, tab->stride, tab->n_eps, tab->start, tab->ident_guard};
       // (da_dense: a double-array tokenizer laid out as a fused matrix -- the table's walk, datok.go's EOT rules)
       auto call = [&](auto t) { if (tab->da_dense) f(t, std::false_type{}); else f(t, std::true_type{}); };
-      if (tab->ident_guard == 0xFFFFFFFFu && codes) {  // the lean loop applies
-        MatrixLeanTrans lt;
-        static_cast<MatrixFusedTrans &>(lt) = tr;
-        call(lt);
-      } else {
-        call(tr);
-      }
+      // the general loop's policy `gen`, or the lean one `lean` where that loop applies
+      auto pick = [&](auto gen, auto lean) {
+        gen.tab = (decltype(gen.tab))tab->tab;
+        gen.stride = tab->stride; gen.n_eps = tab->n_eps; gen.start = tab->start; gen.ident_guard = tab->ident_guard;
+        if (tab->ident_guard == 0xFFFFFFFFu && codes) {
+          static_cast<decltype(gen) &>(lean) = gen;
+          call(lean);
+        } else {
+          call(gen);
+        }
+      };
+      if (tab->entry_bytes == 8) pick(MatrixFused64Trans{}, MatrixLean64Trans{});  // 64-bit cells (32 767 states and more)
+      else pick(MatrixFusedTrans{}, MatrixLeanTrans{});
     } else if (tab->entry_bytes == 2) {
       MatrixTrans<uint16_t> tr{(const uint16_t *)tab->tab, tab->stride, tab->n_eps, tab->start};
       f(tr, std::true_type{});

@@ -16,6 +16,8 @@
 //   (*T).Transduce(r, w)      matrix.go:340-342      Tokenizer::Transduce(std::istream&, std::ostream&)
 //   (*T).TransduceTokenWriter matrix.go:348-698      Tokenizer::TransduceTokenWriter(std::istream&, TokenWriter&)
 //   (*T).Type()               matrix.go:102          Tokenizer::Type()
+//   --                                               datok::ModelInfo(image, n, &info): the device layout a
+//                                                    model file gets (dtk_model_info_mem; host only)
 //
 // The FSA walk itself runs on the GPU (dtk_batch_run); this header only drains
 // the reader, calls the C-ABI and REPLAYS the returned events into the
@@ -341,6 +343,14 @@ inline std::unique_ptr<Tokenizer> LoadTokenizerFile(const std::string &file) {
     return nullptr;
   }
   return std::make_unique<GpuTokenizer>(m);
+}
+
+// Which table and loop a model image (.matok / .datok / Foma net, gzip'd) gets on the device, decided as the loader
+// decides it and without a device (dtk_model_info_mem): false + log line for an image the loader would reject.
+inline bool ModelInfo(const void *gz_bytes, size_t n, dtk_model_info *out) {
+  const int rc = dtk_model_info_mem(gz_bytes, n, out);
+  if (rc != DTK_OK) std::fprintf(stderr, "datok: model image: %s\n", dtk_strerror(rc));
+  return rc == DTK_OK;
 }
 
 }  // namespace datok

@@ -121,15 +121,22 @@ typedef struct {
   uint64_t array_len;    /* matrix: u32 cells; double array: {base,check} pairs */
   uint32_t n_eps_states; /* states with an epsilon arc */
   uint32_t max_eps_chain;/* longest path of epsilon arcs */
-  uint32_t entry_bytes;  /* device table cell size (2 or 4 matrix, 8 double array) */
+  uint32_t entry_bytes;  /* device table cell size.  Matrix, and a double array laid out as one (dense_states != 0):
+                          * 4 = fused cells with 15-bit state ids (the lean loop's table), 8 = fused cells of 64 bits
+                          * (32 767 states and more), 2 or 4 = plain cells (the test hooks' layouts; 4 also for a table
+                          * beyond the 64-bit cells' 32-bit byte offset).  Double array walked as pairs: 8 */
   uint64_t device_bytes; /* HBM held by the model */
   uint32_t unknown_used; /* 1 if any state has an arc on the unknown symbol */
   uint32_t dense_states; /* double array only: its states, if its transitions were laid out as a matrix on the
-                          * device at load (entry_bytes is then 4); 0: the {base, check} pairs are walked */
+                          * device at load (entry_bytes is then 4 or 8, see there); 0: the {base, check} pairs are walked */
   uint32_t stream_codes; /* distinct symbol-stream entries of the model if they fit a byte (the stream is then one
                           * code per input byte and the lean loop may apply); 0: 16-bit entries, general loop */
 } dtk_model_info;
 int dtk_model_get_info(const dtk_model *m, dtk_model_info *out);
+/* The same answer for an image that is not loaded: parses gz_bytes and decides the device layout exactly as
+ * dtk_model_load_mem does (device_bytes: what the model would hold), and touches no device -- like dtk_foma_to_matok
+ * it runs on a machine without a GPU.  What a grammar maintainer's CI asks after an update: which table, which loop. */
+int dtk_model_info_mem(const void *gz_bytes, size_t n, dtk_model_info *out);
 
 /* ---- batch: one data-parallel TransduceTokenWriter over n_docs documents.
  *      Each document is one reference call with a fresh writer

@@ -30,7 +30,7 @@ EXPORTS = [
     "dtk_pinned_alloc", "dtk_pinned_free",
     "dtk_batch_set_result_fields", "dtk_batch_download_begin", "dtk_pipeline_set_result_fields",
     "dtk_batch_set_download_stream", "dtk_batch_download_stream", "dtk_batch_done", "dtk_batch_set_streams",
-    "dtk_debug_configure",
+    "dtk_debug_configure", "dtk_blk_start", "dtk_blk_end",
     "dtk_multi_create", "dtk_multi_free", "dtk_multi_type", "dtk_multi_set_result_fields", "dtk_multi_set_chunking", "dtk_multi_run",
 ]
 
@@ -59,7 +59,9 @@ class ResultView(C.Structure):
                 ("sent", C.c_void_p), ("text_tok_end", C.c_void_p), ("text_sent_end", C.c_void_p),
                 ("status", C.c_void_p), ("ev_bits", C.c_void_p), ("ev_words", C.c_uint64), ("doc_tail", C.c_void_p),
                 ("n_exact", C.c_uint32), ("exact_doc", C.c_void_p), ("exact_off", C.c_void_p),
-                ("calls", C.c_void_p), ("tok_r16", C.c_void_p)]
+                ("calls", C.c_void_p), ("tok_r16", C.c_void_p),
+                ("tok_rblk", C.c_void_p), ("tok_rblk_head", C.c_void_p),
+                ("tok_bblk", C.c_void_p), ("tok_bblk_head", C.c_void_p)]
 
 
 SLICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)
@@ -168,6 +170,8 @@ def lib():
     L.dtk_multi_set_result_fields.argtypes = [vp, u32]
     L.dtk_multi_set_chunking.argtypes = [vp, u32, u32]
     L.dtk_multi_run.argtypes = [vp, vp, vp, u32, u32, SLICE_FN, vp]
+    for f in (L.dtk_blk_start, L.dtk_blk_end):
+        f.argtypes, f.restype = [vp, vp, u64], C.c_int32
     L.dtk_pinned_alloc.restype = vp
     L.dtk_pinned_alloc.argtypes = [sz]
     L.dtk_pinned_free.argtypes = [vp]

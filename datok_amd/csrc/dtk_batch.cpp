@@ -115,11 +115,13 @@ extern "C" void dtk_batch_free(dtk_batch *b) {
                   b->d_csr, b->d_rstart, b->d_rend, b->d_sent,
                   b->d_bstart, b->d_bend, b->d_ttok, b->d_tsent,
                   b->d_sbefore, b->d_ts_end, b->d_doc_ns, b->d_scan_ws, b->d_rws, b->d_out_off, b->d_out,
-                  b->d_exact_ids, b->d_exact_cnt, b->d_exact_off, b->d_calls, b->d_r16};
+                  b->d_exact_ids, b->d_exact_cnt, b->d_exact_off, b->d_calls, b->d_r16,
+                  b->blk[0].d_words, b->blk[0].d_heads, b->blk[1].d_words, b->blk[1].d_heads, b->d_blk_flag};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (b->h_totals) (void)hipHostFree(b->h_totals);
   if (b->h_off_pin) (void)hipHostFree(b->h_off_pin);
+  if (b->h_blk_flag) (void)hipHostFree(b->h_blk_flag);
   for (hipEvent_t e : b->ev)
     if (e) (void)hipEventDestroy(e);
   if (b->stream && b->stream_own) (void)hipStreamDestroy(b->stream);
@@ -454,6 +456,7 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
   if (prc != DTK_OK) return prc;
   if (b->dl_begun && !b->dl_waited) { HIP_TRY(hipEventSynchronize(b->ev_dl)); b->dl_waited = true; }  // (the last run's results on their way out)
   b->dl_begun = false;
+  b->blk_pending = b->blk_failed = 0;
   if (b->up_pending) {  // the kernels wait for the input's upload on the other stream
     HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_up, 0));
     b->up_pending = false;

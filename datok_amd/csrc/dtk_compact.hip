@@ -1007,6 +1007,42 @@ extern "C" int dtk_launch_pack_r16(const int32_t *rs, const int32_t *re, uint32_
   return (int)hipGetLastError();
 }
 
+// ---- DTK_R_TOK_RUNE_BLK / DTK_R_TOK_BYTE_BLK: a pair of offset arrays as blocks of 64 tokens with 16-bit offsets
+// against one or two bases per block (dtk_off_block, include/datok_gpu.h) -- any document length at 4.25 B per token.
+// One wave per block, one token per lane; blockIdx.y is the pair.  Lanes behind the last token take part in nothing.
+__global__ __launch_bounds__(256) void k_pack_blk(DtkPackBlkArgs A) {
+  const DtkPackBlkPair P = A.pair[blockIdx.y];
+  const uint32_t lane = lane_id();
+  const uint64_t blk = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (blk * WAVE >= A.n) return;  // (wave-uniform)
+  const uint64_t i = blk * WAVE + lane;
+  const bool live = i < A.n;
+  int32_t s = 0, e = 0;
+  if (live) { s = P.start[i]; e = P.end[i]; }
+  // the first token of a new text or document starts before its predecessor's end: the block's one break
+  const int32_t prev_e = __shfl_up(e, 1);
+  const unsigned long long dec = __ballot(live && lane != 0u && s < prev_e);
+  const uint32_t brk = dec ? (uint32_t)__ffsll((long long)dec) - 1u : (uint32_t)WAVE;
+  const bool seg1 = lane >= brk;
+  const int32_t lo = live ? min(s, e) : INT32_MAX, hi = live ? max(s, e) : INT32_MIN;
+  const int32_t lo0 = wave_min(seg1 ? INT32_MAX : lo), hi0 = wave_max(seg1 ? INT32_MIN : hi);  // (lane 0 is live)
+  int32_t lo1 = 0, hi1 = 0;
+  if (brk < WAVE) { lo1 = wave_min(seg1 ? lo : INT32_MAX); hi1 = wave_max(seg1 ? hi : INT32_MIN); }  // (lane brk is live)
+  const int32_t base = seg1 ? lo1 : lo0;
+  if (live) P.words[i] = ((uint32_t)(s - base) & 0xFFFFu) | ((uint32_t)(e - base) << 16);
+  if (lane == 0u) {
+    reinterpret_cast<uint4 *>(P.heads)[blk] = make_uint4((uint32_t)lo0, (uint32_t)lo1, brk, 0u);
+    if ((int64_t)hi0 - lo0 > (int64_t)A.span || (int64_t)hi1 - lo1 > (int64_t)A.span) atomicOr(P.flag, 1u);
+  }
+}
+
+extern "C" int dtk_launch_pack_blk(const DtkPackBlkArgs *args, void *stream) {
+  if (args->n == 0 || args->n_pairs == 0) return 0;
+  const uint64_t blocks = (args->n + WAVE - 1) / WAVE;
+  hipLaunchKernelGGL(k_pack_blk, dim3((unsigned)((blocks + 3u) / 4u), args->n_pairs), dim3(256), 0, (hipStream_t)stream, *args);
+  return (int)hipGetLastError();
+}
+
 // ---------------------------------------------------------------- launchers
 
 // ---- clears: the accumulator block and the two event arrays of a run in one launch (16-byte stores)

@@ -35,6 +35,28 @@ __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t &total) 
   return x - v;
 }
 
+// minimum / maximum over the 64 lanes, the same DPP ladder: a lane without a source keeps its own value (`old` is the
+// value itself), lane 63 ends up with the result.
+#define DTK_WAVE_FOLD(x, op)                                                                   \
+  do {                                                                                         \
+    x = op(x, __builtin_amdgcn_update_dpp(x, x, 0x111, 0xF, 0xF, false)); /* row_shr:1 */      \
+    x = op(x, __builtin_amdgcn_update_dpp(x, x, 0x112, 0xF, 0xF, false)); /* row_shr:2 */      \
+    x = op(x, __builtin_amdgcn_update_dpp(x, x, 0x114, 0xF, 0xF, false)); /* row_shr:4 */      \
+    x = op(x, __builtin_amdgcn_update_dpp(x, x, 0x118, 0xF, 0xF, false)); /* row_shr:8 */      \
+    x = op(x, __builtin_amdgcn_update_dpp(x, x, 0x142, 0xA, 0xF, false)); /* row_bcast:15 */   \
+    x = op(x, __builtin_amdgcn_update_dpp(x, x, 0x143, 0xC, 0xF, false)); /* row_bcast:31 */   \
+  } while (0)
+__device__ __forceinline__ int32_t wave_min(int32_t v) {
+  int x = v;
+  DTK_WAVE_FOLD(x, min);
+  return __builtin_amdgcn_readlane(x, WAVE - 1);
+}
+__device__ __forceinline__ int32_t wave_max(int32_t v) {
+  int x = v;
+  DTK_WAVE_FOLD(x, max);
+  return __builtin_amdgcn_readlane(x, WAVE - 1);
+}
+
 __device__ __forceinline__ uint32_t doc_of(const uint64_t *__restrict__ doc_off, uint32_t lo, uint32_t hi,
                                            uint64_t g) {
   // largest d in [lo, hi) with doc_off[d] <= g   (invariant: doc_off[lo] <= g < doc_off[hi])

@@ -42,6 +42,8 @@ struct DtkDebug {
   int clear_kernel = 0;  // the accumulator block is cleared by k_clear2, not by k_symbolize's blocks
   int round_limit = -1;  // host repair rounds before the one-lane-per-document fallback (-1: the longest document's lanes)
   int debug_repair = 0;  // print the lane records of documents that stay broken
+  int blk_span = -1;     // what a segment of a 64-token block may span in the blocked offsets (-1 or 0: 65 535); read where
+                         // k_pack_blk is launched, so that ordinary text reaches the fallback to the 32-bit arrays
 };
 extern DtkDebug g_dbg;
 
@@ -178,13 +180,21 @@ struct dtk_batch {
   // asynchronous copies on a stream of their own (dl_stream) -- the batch's own stream is free for the next kernels,
   // the copy engine for the next slice's upload (PCIe is full duplex).  `fields` (DTK_R_*) selects what is copied.
   // (one buffer per row of host_arrays, dtk_results.cpp)
-  enum { PB_R16, PB_RSTART, PB_REND, PB_BSTART, PB_BEND, PB_BITS, PB_TAIL, PB_SENT, PB_TTOK, PB_TSENT, PB_CSR, PB_STATUS,
+  enum { PB_R16, PB_RBLK, PB_RBLK_HEAD, PB_BBLK, PB_BBLK_HEAD, PB_RSTART, PB_REND, PB_BSTART, PB_BEND, PB_BITS, PB_TAIL, PB_SENT, PB_TTOK, PB_TSENT, PB_CSR, PB_STATUS,
          PB_N };
   struct PinBuf { void *p = nullptr; size_t cap = 0; } pin[PB_N];
   PinBuf h_plan;            // staging of the lane plan's tables (plan_lanes)
   uint32_t fields = DTK_R_ALL;
   uint32_t *d_r16 = nullptr;      // DTK_R_TOK_RUNE16: the packed rune offsets (filled on the download stream)
   uint64_t r16_cap = 0;
+  // DTK_R_TOK_RUNE_BLK ([0]) / DTK_R_TOK_BYTE_BLK ([1]): the blocked offsets, sized from tok_cap and packed on the
+  // download stream like d_r16.  A block that does not fit 16 bits raises the pair's flag word; dtk_batch_result_host
+  // reads its page-locked copy behind the download and brings the pair's 32-bit arrays in its place.
+  struct BlkPair { uint32_t *d_words = nullptr; void *d_heads = nullptr; uint64_t cap = 0; } blk[2];
+  uint32_t *d_blk_flag = nullptr;  // [2]
+  uint32_t *h_blk_flag = nullptr;  // [2], page-locked
+  uint32_t blk_pending = 0;        // blocked fields on their way whose flag nobody has looked at yet
+  uint32_t blk_failed = 0;         // blocked fields the last run's offsets do not fit: the 32-bit arrays stand in
   uint64_t max_doc_bytes = 0;     // of the current input (what decides whether the narrow form exists)
   bool max_doc_valid = false;
   hipStream_t dl_stream = nullptr;  // created with the first download, unless the caller lends one (a pipeline's slices share one:
@@ -216,8 +226,8 @@ int launch_to_host(dtk_batch *b);
 // The DTK_R_* arrays the last run wrote: DTK_NO_RUNE_OFFSETS / DTK_NO_BYTE_OFFSETS leave theirs alone.
 inline uint32_t run_fields(const dtk_batch *b) {
   uint32_t f = ~0u;
-  if (b->last_flags & DTK_NO_RUNE_OFFSETS) f &= ~(uint32_t)(DTK_R_TOK_RUNE | DTK_R_TOK_RUNE16);
-  if (b->last_flags & DTK_NO_BYTE_OFFSETS) f &= ~(uint32_t)DTK_R_TOK_BYTE;
+  if (b->last_flags & DTK_NO_RUNE_OFFSETS) f &= ~(uint32_t)(DTK_R_TOK_RUNE | DTK_R_TOK_RUNE16 | DTK_R_TOK_RUNE_BLK);
+  if (b->last_flags & DTK_NO_BYTE_OFFSETS) f &= ~(uint32_t)(DTK_R_TOK_BYTE | DTK_R_TOK_BYTE_BLK);
   return f;
 }
 

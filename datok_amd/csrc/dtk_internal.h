@@ -314,11 +314,27 @@ struct DtkToHostArgs {
   uint64_t epoch;
 };
 
+// DTK_R_TOK_RUNE_BLK / DTK_R_TOK_BYTE_BLK (k_pack_blk): one pair of offset arrays into its blocked form
+// (include/datok_gpu.h, dtk_off_block).  The byte offsets are below 2^31: both pairs are read as int32.
+struct DtkPackBlkPair {
+  const int32_t *start, *end;  // n each
+  uint32_t *words;             // n
+  void *heads;                 // ceil(n / 64) dtk_off_block, 16-byte aligned
+  uint32_t *flag;              // device word, cleared in front of the launch: 1 is ORed in if a block does not fit
+};
+struct DtkPackBlkArgs {
+  struct DtkPackBlkPair pair[2];
+  uint32_t n_pairs;
+  uint32_t span;  // largest maximum - minimum a segment of a block may have (65 535)
+  uint64_t n;     // tokens
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
 int dtk_launch_to_host(const struct DtkToHostArgs *args, void *stream);
 int dtk_launch_pack_r16(const int32_t *rs, const int32_t *re, uint32_t *out, uint64_t n, void *stream);
+int dtk_launch_pack_blk(const struct DtkPackBlkArgs *args, void *stream);
 // launchers (dtk_symbolize / dtk_walk / dtk_repair / dtk_compact .hip); stream is a hipStream_t
 int dtk_launch_symbolize(const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs,
                          uint64_t total, const struct DtkSigmaDev *sig, void *sym, int padded,

@@ -58,7 +58,8 @@ extern "C" int dtk_debug_configure(const char *key, const char *value) {
       {"NO_FUSED", &g_dbg.no_fused, true}, {"WIDE_FUSED", &g_dbg.wide_fused, true}, {"NO_DENSE", &g_dbg.no_dense, true}, {"SMALL_MAX", &g_dbg.small_max, false},
       {"LDS_BITS", &g_dbg.lds_bits, false}, {"SPLIT_START", &g_dbg.split_start, false}, {"DEV_ROUNDS", &g_dbg.dev_rounds, false},
       {"COMPACT_FULL", &g_dbg.compact_full, true}, {"CLEAR_KERNEL", &g_dbg.clear_kernel, true},
-      {"ROUND_LIMIT", &g_dbg.round_limit, false}, {"DEBUG_REPAIR", &g_dbg.debug_repair, true}};
+      {"ROUND_LIMIT", &g_dbg.round_limit, false}, {"DEBUG_REPAIR", &g_dbg.debug_repair, true},
+      {"BLK_SPAN", &g_dbg.blk_span, false}};
   if (strncmp(key, "DATOK_", 6) == 0) key += 6;
   for (const auto &e : tab)
     if (strcmp(key, e.name) == 0) {

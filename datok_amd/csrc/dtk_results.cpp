@@ -5,11 +5,13 @@
 #include <cstdlib>
 #include <cstring>
 
+#define DTK_BLK_DECODER  // (this unit emits dtk_blk_start / dtk_blk_end of datok_gpu.h as exported functions)
 #include "dtk_host.h"
 
 namespace {
 // An array that can go to the host: `count` >= 0: totals[count] elements of `size` bytes, in a device array of `cap`
-// elements; < 0: `size` bytes.
+// elements -- 0 tokens, 1 sentence ints, 2 texts, 3 (kPerBlock) blocks of 64 tokens, i.e. one element per 64 tokens,
+// rounded up; < 0: `size` bytes.
 struct HostArray {
   uint32_t field;  // DTK_R_*
   int slot;        // dtk_batch::PB_*: its page-locked buffer
@@ -20,6 +22,11 @@ struct HostArray {
   void (*view)(dtk_result_view *o, const void *p);  // where dtk_batch_result_host shows it
 };
 #define VIEW(f) [](dtk_result_view *o, const void *p) { o->f = static_cast<decltype(o->f)>(p); }
+constexpr int kPerBlock = 3;
+constexpr uint32_t kBlkFields = DTK_R_TOK_RUNE_BLK | DTK_R_TOK_BYTE_BLK;
+constexpr uint32_t kBlkField[2] = {DTK_R_TOK_RUNE_BLK, DTK_R_TOK_BYTE_BLK};
+constexpr uint32_t kBlkWide[2] = {DTK_R_TOK_RUNE, DTK_R_TOK_BYTE};  // what stands in for a pair that does not fit
+uint64_t blocks_of(uint64_t tokens) { return (tokens + 63) / 64; }
 
 // The batch's arrays, in the order their copies are enqueued: the large ones first (k_to_host deals its pieces out to
 // its waves by array; on the download stream the small copies ride behind the large ones).
@@ -27,6 +34,12 @@ std::array<HostArray, dtk_batch::PB_N> host_arrays(const dtk_batch *b) {
   const uint64_t nd = b->n_docs;
   const HostArray t[] = {
       {DTK_R_TOK_RUNE16, dtk_batch::PB_R16, b->d_r16, 4, 0, b->r16_cap, VIEW(tok_r16)},
+      {DTK_R_TOK_RUNE_BLK, dtk_batch::PB_RBLK, b->blk[0].d_words, 4, 0, b->blk[0].cap, VIEW(tok_rblk)},
+      {DTK_R_TOK_RUNE_BLK, dtk_batch::PB_RBLK_HEAD, b->blk[0].d_heads, sizeof(dtk_off_block), kPerBlock,
+       blocks_of(b->blk[0].cap), VIEW(tok_rblk_head)},
+      {DTK_R_TOK_BYTE_BLK, dtk_batch::PB_BBLK, b->blk[1].d_words, 4, 0, b->blk[1].cap, VIEW(tok_bblk)},
+      {DTK_R_TOK_BYTE_BLK, dtk_batch::PB_BBLK_HEAD, b->blk[1].d_heads, sizeof(dtk_off_block), kPerBlock,
+       blocks_of(b->blk[1].cap), VIEW(tok_bblk_head)},
       {DTK_R_TOK_RUNE, dtk_batch::PB_RSTART, b->d_rstart, 4, 0, b->tok_cap, VIEW(tok_rstart)},
       {DTK_R_TOK_RUNE, dtk_batch::PB_REND, b->d_rend, 4, 0, b->tok_cap, VIEW(tok_rend)},
       {DTK_R_TOK_BYTE, dtk_batch::PB_BSTART, b->d_bstart, 4, 0, b->tok_cap, VIEW(tok_bstart)},
@@ -44,6 +57,39 @@ std::array<HostArray, dtk_batch::PB_N> host_arrays(const dtk_batch *b) {
   std::copy(t, t + dtk_batch::PB_N, r.begin());
   return r;
 }
+
+// The blocked form of the pairs in `want` (kBlkFields), packed on the download stream itself, in front of its copies:
+// the batch's stream is idle (finish()) and stays free.  The device arrays follow tok_cap like d_r16.
+int pack_blocked(dtk_batch *b, uint32_t want, uint64_t n_tokens) {
+  if (!b->d_blk_flag) {
+    HIP_TRY(hipMalloc((void **)&b->d_blk_flag, 2 * sizeof(uint32_t)));
+    HIP_TRY(hipHostMalloc((void **)&b->h_blk_flag, 2 * sizeof(uint32_t), hipHostMallocDefault));
+    b->h_blk_flag[0] = b->h_blk_flag[1] = 0;
+  }
+  const int32_t *src[2][2] = {{b->d_rstart, b->d_rend}, {(const int32_t *)b->d_bstart, (const int32_t *)b->d_bend}};
+  DtkPackBlkArgs a{};
+  for (int k = 0; k < 2; k++) {
+    if (!(want & kBlkField[k])) continue;
+    dtk_batch::BlkPair &p = b->blk[k];
+    if (p.cap < b->tok_cap || !p.d_words) {
+      if (p.d_words) HIP_TRY(hipFree(p.d_words));
+      if (p.d_heads) HIP_TRY(hipFree(p.d_heads));
+      p.d_words = nullptr; p.d_heads = nullptr; p.cap = 0;
+      const uint64_t cap = std::max<uint64_t>(b->tok_cap, 64);
+      HIP_TRY(hipMalloc((void **)&p.d_words, cap * 4));
+      HIP_TRY(hipMalloc(&p.d_heads, blocks_of(cap) * sizeof(dtk_off_block)));
+      p.cap = cap;
+    }
+    if (n_tokens > p.cap) return DTK_E_CAPACITY;  // (finish() has grown tok_cap to the run's tokens: never expected)
+    // the flag word is cleared in front of the kernel and goes home behind the blocked arrays (dtk_batch_download_begin)
+    HIP_TRY(hipMemsetAsync(b->d_blk_flag + k, 0, sizeof(uint32_t), b->dl_stream));
+    a.pair[a.n_pairs++] = DtkPackBlkPair{src[k][0], src[k][1], p.d_words, p.d_heads, b->d_blk_flag + k};
+  }
+  a.n = n_tokens;
+  a.span = g_dbg.blk_span > 0 ? (uint32_t)g_dbg.blk_span : 65535u;
+  if (dtk_launch_pack_blk(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "pack blocked offsets");
+  return DTK_OK;
+}
 }  // namespace
 
 extern "C" int dtk_batch_result_device(dtk_batch *b, dtk_result_view *o) {
@@ -51,6 +97,7 @@ extern "C" int dtk_batch_result_device(dtk_batch *b, dtk_result_view *o) {
   int rc = finish(b);
   if (rc != DTK_OK) return rc;
   o->tok_r16 = nullptr;  // (host results only)
+  o->tok_rblk = o->tok_bblk = nullptr; o->tok_rblk_head = o->tok_bblk_head = nullptr;
   set_outputs(b, *o);
   o->status = b->d_status; o->ev_bits = b->d_bits; o->ev_words = b->bit_words; o->doc_tail = b->d_doc_tail;
   o->n_exact = (uint32_t)b->h_exact_ids.size();
@@ -59,7 +106,7 @@ extern "C" int dtk_batch_result_device(dtk_batch *b, dtk_result_view *o) {
 }
 
 extern "C" int dtk_batch_set_result_fields(dtk_batch *b, uint32_t fields) {
-  if (!b || (fields & ~(uint32_t)(DTK_R_ALL | DTK_R_TOK_RUNE16 | DTK_R_EAGER))) return DTK_E_ARG;
+  if (!b || (fields & ~(uint32_t)(DTK_R_ALL | DTK_R_TOK_RUNE16 | DTK_R_EAGER | kBlkFields))) return DTK_E_ARG;
   b->fields = fields;
   return DTK_OK;
 }
@@ -116,7 +163,7 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
   if (!b) return DTK_E_ARG;
   int rc = finish(b);
   if (rc != DTK_OK) return rc;
-  uint32_t sel = b->fields & (DTK_R_ALL | DTK_R_TOK_RUNE16);
+  uint32_t sel = b->fields & (DTK_R_ALL | DTK_R_TOK_RUNE16 | kBlkFields);
   if (sel & DTK_R_TOK_RUNE16) {
     // the narrow form holds every offset of a document of at most 32 767 bytes; a batch with a longer one gets the
     // 32-bit arrays in its place
@@ -126,13 +173,20 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
       b->max_doc_bytes = m;
       b->max_doc_valid = true;
     }
-    if (b->max_doc_bytes > 32767u) sel = (sel & ~(uint32_t)DTK_R_TOK_RUNE16) | DTK_R_TOK_RUNE;
+    // (with DTK_R_TOK_RUNE_BLK beside it the narrowest form that applies is asked for: tok_r16, else the blocks)
+    if (b->max_doc_bytes <= 32767u) sel &= ~(uint32_t)DTK_R_TOK_RUNE_BLK;
+    else sel = (sel & ~(uint32_t)DTK_R_TOK_RUNE16) | ((sel & DTK_R_TOK_RUNE_BLK) ? 0u : (uint32_t)DTK_R_TOK_RUNE);
   }
+  // a pair whose blocks did not fit 16 bits in this run (dtk_batch_result_host saw its flag): the 32-bit arrays
+  for (int k = 0; k < 2; k++)
+    if (sel & b->blk_failed & kBlkField[k]) sel = (sel & ~kBlkField[k]) | kBlkWide[k];
   sel &= run_fields(b);
   if (b->dl_begun && (b->dl_fields & sel) == sel) return DTK_OK;
   const uint32_t want = sel & ~(b->dl_begun ? b->dl_fields : 0u);
   if (!dtk_batch_download_stream(b)) return hip_fail(hipGetLastError(), "download stream");
-  const uint64_t tot[3] = {b->totals.n_tokens, b->totals.n_sent, b->totals.n_texts};
+  const uint64_t tot[4] = {b->totals.n_tokens, b->totals.n_sent, b->totals.n_texts, blocks_of(b->totals.n_tokens)};
+  const uint32_t blk_want = tot[0] ? want & kBlkFields : 0u;  // (no token: nothing to pack, empty arrays)
+  if (blk_want && (rc = pack_blocked(b, blk_want, tot[0])) != DTK_OK) return rc;
   for (const HostArray &r : host_arrays(b)) {
     if (!(want & r.field)) continue;
     const uint64_t bytes = r.count >= 0 ? tot[r.count] * r.size : r.size;
@@ -153,6 +207,10 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
     if (rc != DTK_OK) return rc;
     if (bytes) HIP_TRY(hipMemcpyAsync(b->pin[r.slot].p, src, (size_t)bytes, hipMemcpyDeviceToHost, b->dl_stream));
   }
+  for (int k = 0; k < 2; k++)
+    if (blk_want & kBlkField[k])
+      HIP_TRY(hipMemcpyAsync(b->h_blk_flag + k, b->d_blk_flag + k, sizeof(uint32_t), hipMemcpyDeviceToHost, b->dl_stream));
+  b->blk_pending |= blk_want;
   if (!b->ev_dl) HIP_TRY(hipEventCreateWithFlags(&b->ev_dl, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(b->ev_dl, b->dl_stream));
   b->dl_waited = false;
@@ -166,6 +224,20 @@ extern "C" int dtk_batch_result_host(dtk_batch *b, dtk_result_view *o) {
   int rc = dtk_batch_download_begin(b);
   if (rc != DTK_OK) return rc;
   if (!b->dl_waited) { HIP_TRY(hipEventSynchronize(b->ev_dl)); b->dl_waited = true; }
+  if (b->blk_pending) {
+    // A blocked pair with a block that does not fit 16 bits: its 32-bit arrays come over now and the blocked pointers
+    // stay NULL.  blk_failed holds for the rest of the run: a second call neither copies again nor flips forms.
+    uint32_t failed = 0;
+    for (int k = 0; k < 2; k++)
+      if ((b->blk_pending & kBlkField[k]) && b->h_blk_flag[k]) failed |= kBlkField[k];
+    b->blk_pending = 0;
+    if (failed) {
+      b->blk_failed |= failed;
+      b->dl_fields &= ~failed;
+      if ((rc = dtk_batch_download_begin(b)) != DTK_OK) return rc;
+      if (!b->dl_waited) { HIP_TRY(hipEventSynchronize(b->ev_dl)); b->dl_waited = true; }
+    }
+  }
   memset(o, 0, sizeof(*o));
   for (const HostArray &r : host_arrays(b))
     if (b->dl_fields & r.field) r.view(o, b->pin[r.slot].p);

@@ -292,11 +292,24 @@ def event_bit(doc_off_d, d):
     return int(doc_off_d) + int(d)
 
 
+def unpack_blocked(words, heads, first=0, last=None):
+    """(start, end) as int32 arrays from the blocked form of a pair of offset arrays (dtk_off_block, datok_gpu.h;
+    what dtk_blk_start / dtk_blk_end give token by token).  words: uint32[n]; heads: int32[ceil(n / 64), 4] with
+    the columns base0, base1, brk, reserved.  first / last: only the tokens [first, last) of the batch."""
+    words = np.asarray(words, dtype=np.uint32)
+    heads = np.asarray(heads).view(np.int32).reshape(-1, 4)
+    i = np.arange(int(first), len(words) if last is None else int(last), dtype=np.int64)
+    h = heads[i >> 6]
+    base = np.where((i & 63) < h[:, 2], h[:, 0], h[:, 1]).astype(np.int32)
+    w = words[i]
+    return base + (w & np.uint32(0xFFFF)).astype(np.int32), base + (w >> np.uint32(16)).astype(np.int32)
+
+
 class BatchResult:
     """Host copy of dtk_result_view (CSR over documents)."""
     __slots__ = ("tok_off", "sent_off", "text_off", "tok_rstart", "tok_rend", "tok_bstart",
                  "tok_bend", "sent", "text_tok_end", "text_sent_end", "status", "ev_bits", "doc_tail", "doc_off", "exact",
-                 "tok_r16")
+                 "tok_r16", "tok_rblk", "tok_rblk_head", "tok_bblk", "tok_bblk_head")
 
     def events(self, d):
         """Flag byte per cursor position of document d (event_bytes()), for replays."""
@@ -311,8 +324,13 @@ class BatchResult:
         rs, re = self.tok_rstart[a:b], self.tok_rend[a:b]
         if len(self.tok_r16) and not len(self.tok_rstart):  # (R_TOK_RUNE16: int16 pairs {start, end})
             rs, re = self.tok_r16[a:b, 0].astype(np.int32), self.tok_r16[a:b, 1].astype(np.int32)
+        elif len(self.tok_rblk) and not len(self.tok_rstart):  # (R_TOK_RUNE_BLK: 16-bit blocks)
+            rs, re = unpack_blocked(self.tok_rblk, self.tok_rblk_head, a, b)
+        bs, be = self.tok_bstart[a:b], self.tok_bend[a:b]
+        if len(self.tok_bblk) and not len(self.tok_bstart):    # (R_TOK_BYTE_BLK)
+            bs, be = (x.astype(np.uint32) for x in unpack_blocked(self.tok_bblk, self.tok_bblk_head, a, b))
         return dict(tok_rstart=rs, tok_rend=re,
-                    tok_bstart=self.tok_bstart[a:b], tok_bend=self.tok_bend[a:b],
+                    tok_bstart=bs, tok_bend=be,
                     sent=self.sent[s0:s1], text_tok_end=self.text_tok_end[t0:t1],
                     text_sent_end=self.text_sent_end[t0:t1], status=int(self.status[d]))
 
@@ -420,6 +438,9 @@ class Batch:
     R_TOK_RUNE16 = 128   # the rune offsets as int16 pairs (BatchResult.tok_r16); a batch with a document longer than
                          # 32 767 bytes gets tok_rstart / tok_rend in their place
     R_EAGER = 256        # the selected arrays leave for the host inside the run (k_to_host) where they fit
+    R_TOK_RUNE_BLK = 512   # the rune / byte offsets as blocks of 64 tokens with 16-bit offsets (BatchResult.tok_rblk +
+    R_TOK_BYTE_BLK = 1024  # tok_rblk_head / tok_bblk + tok_bblk_head, unpack_blocked): any document length; a batch with
+                           # a block that does not fit gets the 32-bit arrays in their place
 
     def set_result_fields(self, fields=R_ALL):
         """Which arrays result() brings to the host (the others come back empty)."""
@@ -458,6 +479,11 @@ class Batch:
         r.ev_bits = arr(v.ev_bits, 5 * int(v.ev_words), np.uint32).reshape(5, -1) if v.ev_bits else np.zeros((5, 0), np.uint32)
         r.doc_tail = arr(v.doc_tail, nd, np.uint32)
         r.tok_r16 = arr(v.tok_r16, 2 * t["n_tokens"], np.int16).reshape(-1, 2)
+        n_blk = (t["n_tokens"] + 63) // 64
+        r.tok_rblk = arr(v.tok_rblk, t["n_tokens"], np.uint32)
+        r.tok_rblk_head = arr(v.tok_rblk_head, 4 * n_blk, np.int32).reshape(-1, 4)
+        r.tok_bblk = arr(v.tok_bblk, t["n_tokens"], np.uint32)
+        r.tok_bblk_head = arr(v.tok_bblk_head, 4 * n_blk, np.int32).reshape(-1, 4)
         r.doc_off = self._doc_off
         r.exact = _exact_calls(v, arr)   # documents walked by the exact pass: id -> calls in order
         return r

@@ -80,6 +80,34 @@ enum {
 typedef struct dtk_model dtk_model;
 typedef struct dtk_batch dtk_batch;
 
+/* ---- token offsets as 16-bit blocks (DTK_R_TOK_RUNE_BLK, DTK_R_TOK_BYTE_BLK): 4.25 B per token instead of 8, for
+ *      documents of any length.  Tokens are taken in the batch-wide order of the result arrays (the order tok_off
+ *      indexes); block j holds the tokens [64j, 64j + 64).  Inside one text the offsets never decrease from one token
+ *      to the next, and 64 consecutive tokens span little (the reference's window holds at most 1024 runes between two
+ *      rewinds); the large jumps are the resets at a text or document boundary.  A block therefore has one break:
+ *        brk   = the smallest lane l >= 1 of the block with start[64j + l] < end[64j + l - 1], or 64 if there is none
+ *        base0 = the minimum over every start and end of the lanes < brk
+ *        base1 = the minimum over the lanes >= brk, or 0 if brk == 64
+ *        word[i] = (start[i] - base) | (end[i] - base) << 16   with base = lane < brk ? base0 : base1
+ *      (both halves unsigned 16-bit; the -1 of token_writer.go:66-68 lands in a base).  The last block of a batch is
+ *      partial: lanes behind the last token take part in nothing.  A batch in which some segment of some block spans
+ *      more than 65 535 does not get this form: the pointers come back NULL and the 32-bit arrays are delivered in
+ *      their place. ---- */
+typedef struct { int32_t base0, base1; uint32_t brk, reserved; } dtk_off_block;
+/* The decoders: inline for C, cgo and C++ callers; libdatok_gpu.so also exports the two under the same names for
+ * callers that bind symbols (ctypes, ...) -- the library's own unit defines DTK_BLK_DECODER away to emit them. */
+#ifndef DTK_BLK_DECODER
+#define DTK_BLK_DECODER static inline
+#endif
+DTK_BLK_DECODER int32_t dtk_blk_start(const uint32_t *words, const dtk_off_block *heads, uint64_t i) {
+  const dtk_off_block *h = heads + (i >> 6);
+  return ((uint32_t)(i & 63u) < h->brk ? h->base0 : h->base1) + (int32_t)(words[i] & 0xFFFFu);
+}
+DTK_BLK_DECODER int32_t dtk_blk_end(const uint32_t *words, const dtk_off_block *heads, uint64_t i) {
+  const dtk_off_block *h = heads + (i >> 6);
+  return ((uint32_t)(i & 63u) < h->brk ? h->base0 : h->base1) + (int32_t)(words[i] >> 16);
+}
+
 /* ---- devices ---- */
 int dtk_device_count(void);
 int dtk_set_device(int device);          /* device used by subsequent loads / batches of this thread */
@@ -259,6 +287,12 @@ typedef struct {
   const dtk_call *calls;
   /* DTK_R_TOK_RUNE16 (host results only): (uint16_t)tok_rstart[i] | (uint32_t)(uint16_t)tok_rend[i] << 16, or NULL */
   const uint32_t *tok_r16;
+  /* DTK_R_TOK_RUNE_BLK / DTK_R_TOK_BYTE_BLK (host results only): the rune resp. byte offsets in blocks of 64 tokens,
+   * one word per token and one dtk_off_block per block (above); NULL when not delivered */
+  const uint32_t *tok_rblk;
+  const dtk_off_block *tok_rblk_head;
+  const uint32_t *tok_bblk;
+  const dtk_off_block *tok_bblk_head;
 } dtk_result_view;
 int dtk_batch_result_device(dtk_batch *b, dtk_result_view *out);
 /* status words of the first n documents, copied to the caller's array */
@@ -292,7 +326,15 @@ enum {
    * compaction reads the row counts on the device and streams the rows into the batch's page-locked buffers, so no
    * host round trip stands between the walk and the copy.  dtk_batch_result_host then finds them there (a run that
    * needed a repair round, larger arrays or the exact pass copies again by itself). */
-  DTK_R_EAGER = 256
+  DTK_R_EAGER = 256,
+  /* tok_rblk + tok_rblk_head resp. tok_bblk + tok_bblk_head: the rune resp. byte offsets as 16-bit blocks
+   * (dtk_off_block above; decode with dtk_blk_start / dtk_blk_end), packed on the download stream in front of their
+   * copies.  Host results only, not part of DTK_R_ALL nor of the eager copy.  If a block of the batch does not fit 16
+   * bits the pair's pointers come back NULL and its 32-bit arrays are delivered in their place (the caller looks at
+   * which pointer it got, as with tok_r16).  DTK_R_TOK_RUNE16 | DTK_R_TOK_RUNE_BLK asks for the narrowest form that
+   * applies: tok_r16 for a batch of documents of up to 32 767 bytes, the blocked form for any other. */
+  DTK_R_TOK_RUNE_BLK = 512,
+  DTK_R_TOK_BYTE_BLK = 1024
 };
 int dtk_batch_set_result_fields(dtk_batch *b, uint32_t fields);
 int dtk_batch_download_begin(dtk_batch *b);

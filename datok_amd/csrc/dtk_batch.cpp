@@ -3,44 +3,30 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 
 #include "dtk_host.h"
 
-// page-locked memory for n bytes in `pb` (grown with a quarter of slack: allocation costs milliseconds)
-int pin_fit(dtk_batch::PinBuf &pb, size_t n) {
-  if (n <= pb.cap && pb.p) return DTK_OK;
-  if (pb.p) HIP_TRY(hipHostFree(pb.p));
-  pb.p = nullptr; pb.cap = 0;
-  const size_t cap = std::max<size_t>(n + n / 4, 256);
-  HIP_TRY(hipHostMalloc(&pb.p, cap, hipHostMallocDefault));
-  pb.cap = cap;
-  return DTK_OK;
-}
-
+// The output arrays for `tok` tokens, `sent` sentence ints and `text` texts.  A group's capacity is 0 while its arrays
+// are regrown: no kernel is ever handed a capacity that one of them does not have.
 static int alloc_outputs(dtk_batch *b, uint64_t tok, uint64_t sent, uint64_t text) {
-  auto grow = [&](auto *&p, uint64_t n) -> int {
-    if (p) HIP_TRY(hipFree(p));
-    p = nullptr;
-    HIP_TRY(hipMalloc((void **)&p, std::max<uint64_t>(n, 4) * 4));
-    return DTK_OK;
-  };
+  auto grow = [](auto &a, uint64_t n) { return a.fit(n, std::max<uint64_t>(n, 4)); };
   int rc;
   if (tok > b->tok_cap) {
-    if ((rc = grow(b->d_rstart, tok))) return rc;
-    if ((rc = grow(b->d_rend, tok))) return rc;
-    if ((rc = grow(b->d_bstart, tok))) return rc;
-    if ((rc = grow(b->d_bend, tok))) return rc;
-    if ((rc = grow(b->d_sbefore, tok))) return rc;
+    b->tok_cap = 0;
+    if ((rc = grow(b->d_rstart, tok)) || (rc = grow(b->d_rend, tok)) || (rc = grow(b->d_bstart, tok)) ||
+        (rc = grow(b->d_bend, tok)) || (rc = grow(b->d_sbefore, tok)))
+      return rc;
     b->tok_cap = tok;
   }
   if (sent > b->sent_cap) {
+    b->sent_cap = 0;
     if ((rc = grow(b->d_sent, sent))) return rc;
     b->sent_cap = sent;
   }
   if (text > b->text_cap) {
-    if ((rc = grow(b->d_ttok, text))) return rc;
-    if ((rc = grow(b->d_tsent, text))) return rc;
-    if ((rc = grow(b->d_ts_end, text))) return rc;
+    b->text_cap = 0;
+    if ((rc = grow(b->d_ttok, text)) || (rc = grow(b->d_tsent, text)) || (rc = grow(b->d_ts_end, text))) return rc;
     b->text_cap = text;
   }
   return DTK_OK;
@@ -50,90 +36,53 @@ extern "C" int dtk_batch_create(uint64_t max_bytes, uint32_t max_docs, dtk_batch
   if (!out || max_docs == 0) return DTK_E_ARG;
   *out = nullptr;
   if (dtk_device_count() <= 0) return DTK_E_NO_DEVICE;
-  dtk_batch *b = new dtk_batch();
+  std::unique_ptr<dtk_batch> b(new dtk_batch());
   b->max_bytes = max_bytes;
   b->max_docs = max_docs;
-  auto fail = [&](int rc) { dtk_batch_free(b); return rc; };
-#define B_TRY(call)                                                  \
-  do {                                                               \
-    hipError_t e_ = (call);                                          \
-    if (e_ != hipSuccess) return fail(hip_fail(e_, #call));          \
-  } while (0)
-  B_TRY(hipGetDevice(&b->device));
-  B_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+  HIP_TRY(hipGetDevice(&b->device));
+  int rc = b->stream.create();
+  if (rc != DTK_OK) return rc;
   if (g_dbg.round_limit >= 0) b->round_limit = (uint32_t)g_dbg.round_limit;
-  const uint64_t pad = 256;
-  B_TRY(hipMalloc((void **)&b->d_text_own, max_bytes + pad));
-  B_TRY(hipMalloc((void **)&b->d_off_own, ((uint64_t)max_docs + 1) * 8));
-  B_TRY(hipMalloc((void **)&b->d_sym, (max_bytes + pad) * 2));
-  B_TRY(hipMalloc((void **)&b->d_rsbits, (max_bytes + pad) / 8 + 64));
-  // per array: total + 4 * n_docs + 4 slots, rounded up to 256 by dtk_batch_run
-  // one bit per cursor position and kind: total + n_docs positions, rounded up to 16 bytes per kind, two words of slack
-  B_TRY(hipMalloc((void **)&b->d_bits, (EVB_KINDS * ((max_bytes + max_docs) / 32 + 8) + 8) * 4));
-  b->acc_bytes = DTK_TOTALS_BYTES + 3 * ((uint64_t)max_docs + 1) * 8 + 4 * (uint64_t)max_docs * 4 + 64;
-  B_TRY(hipMalloc((void **)&b->d_acc, b->acc_bytes));
-  B_TRY(hipMalloc((void **)&b->d_redo, (uint64_t)max_docs * 4));
-  B_TRY(hipMalloc((void **)&b->d_blk_doc, (max_bytes / DTK_SYM_BLOCK_BYTES + 3) * 4));
-
-  B_TRY(hipMalloc((void **)&b->d_chunk_off, ((uint64_t)max_docs + 1) * 4));
-  B_TRY(hipMalloc((void **)&b->d_big_docs, ((uint64_t)max_docs + 1) * 4));
-  // the three row-offset arrays, carved from one block per run (n_docs + 1 words each, back to back: one copy brings
-  // them to the host)
-  B_TRY(hipMalloc((void **)&b->d_csr, 3 * ((uint64_t)max_docs + 1) * 8));
-  b->d_tok_off = b->d_csr; b->d_sent_off = b->d_csr + ((uint64_t)max_docs + 1); b->d_text_off = b->d_csr + 2 * ((uint64_t)max_docs + 1);
-  B_TRY(hipMalloc((void **)&b->d_doc_ns, ((uint64_t)max_docs + 1) * 4));
-  B_TRY(hipMalloc((void **)&b->d_scan_ws, ((uint64_t)max_docs / 2048 + 2) * 4 * 8));
-  B_TRY(hipMalloc((void **)&b->d_out_off, ((uint64_t)max_docs + 1) * 8));
-
-  // [0..15] device totals ([10] doubles as the render size), [16..] the striped lookup counters
-  B_TRY(hipHostMalloc((void **)&b->h_totals, DTK_TOTALS_BYTES, hipHostMallocDefault));
-  B_TRY(hipHostMalloc((void **)&b->h_off_pin, ((uint64_t)max_docs + 1) * 8, hipHostMallocDefault));
-#undef B_TRY
+  const uint64_t pad = 256, nd1 = (uint64_t)max_docs + 1;
+  auto make = [](auto &a, uint64_t n) { return a.fit(n, n); };  // (elements, not bytes)
+  if ((rc = make(b->d_text_own, max_bytes + pad)) || (rc = make(b->d_off_own, nd1)) ||
+      (rc = make(b->d_sym, max_bytes + pad)) || (rc = make(b->d_rsbits, (max_bytes + pad) / 8 + 64)) ||
+      // one bit per cursor position and kind: total + n_docs positions, rounded up to 16 bytes per kind, two words of slack
+      (rc = make(b->d_bits, EVB_KINDS * ((max_bytes + max_docs) / 32 + 8) + 8)) ||
+      // the totals block and what dtk_batch_run carves behind it: three counts, status, two check words, tail
+      (rc = make(b->d_acc, DTK_TOTALS_BYTES + 3 * nd1 * 8 + 4 * (uint64_t)max_docs * 4 + 64)) ||
+      (rc = make(b->d_redo, max_docs)) || (rc = make(b->d_blk_doc, max_bytes / DTK_SYM_BLOCK_BYTES + 3)) ||
+      (rc = make(b->d_chunk_off, nd1)) || (rc = make(b->d_big_docs, nd1)) ||
+      // the three row-offset arrays, carved from one block per run (n_docs + 1 words each, back to back: one copy brings
+      // them to the host)
+      (rc = make(b->d_csr, 3 * nd1)) || (rc = make(b->d_doc_ns, nd1)) ||
+      (rc = make(b->d_scan_ws, ((uint64_t)max_docs / 2048 + 2) * 4)) || (rc = make(b->d_out_off, nd1)) ||
+      (rc = b->h_totals_pin.fit(DTK_TOTALS_BYTES, DTK_TOTALS_BYTES)) || (rc = b->h_off_pin.fit(nd1 * 8, nd1 * 8)))
+    return rc;
+  b->d_tok_off = b->d_csr; b->d_sent_off = b->d_csr + nd1; b->d_text_off = b->d_csr + 2 * nd1;
+  b->h_totals = b->h_totals_pin.as<DtkTotalsDev>();
   // typical German: 0.18 tokens and 0.06 sentence ints per byte; grown on demand
-  int rc = alloc_outputs(b, max_bytes / 3 + max_docs + 16, max_bytes / 8 + 2ull * max_docs + 16,
-                         max_bytes / 64 + 2ull * max_docs + 16);
-  if (rc != DTK_OK) return fail(rc);
-  *out = b;
+  rc = alloc_outputs(b.get(), max_bytes / 3 + max_docs + 16, max_bytes / 8 + 2ull * max_docs + 16,
+                     max_bytes / 64 + 2ull * max_docs + 16);
+  if (rc != DTK_OK) return rc;
+  *out = b.release();
   return DTK_OK;
 }
 
-extern "C" void dtk_batch_free(dtk_batch *b) {
-  if (!b) return;
-  if (b->stream) (void)hipStreamSynchronize(b->stream);
-  if (b->up_stream) (void)hipStreamSynchronize(b->up_stream);
-  if (b->ev_up) (void)hipEventDestroy(b->ev_up);
-  if (b->dl_begun && !b->dl_waited) (void)hipEventSynchronize(b->ev_dl);
-  if (b->dl_stream && b->dl_own) (void)hipStreamDestroy(b->dl_stream);
-  if (b->ev_ran) (void)hipEventDestroy(b->ev_ran);
-  if (b->ev_dl) (void)hipEventDestroy(b->ev_dl);
-  for (auto &pb : b->pin)
-    if (pb.p) (void)hipHostFree(pb.p);
-  if (b->h_plan.p) (void)hipHostFree(b->h_plan.p);
-  void *ptrs[] = {b->d_text_own, b->d_off_own, b->d_sym, b->d_rsbits, b->d_bits, b->d_acc, b->d_redo, b->d_chunk_off, b->d_blk_doc, b->d_big_docs,
-                  b->d_lane_doc, b->d_lane_cnt, b->d_lane_start, b->d_lane_end, b->d_lane_plan,
-                  b->d_seg_tab, b->d_seg_sum, b->d_seg_in,
-                  b->d_csr, b->d_rstart, b->d_rend, b->d_sent,
-                  b->d_bstart, b->d_bend, b->d_ttok, b->d_tsent,
-                  b->d_sbefore, b->d_ts_end, b->d_doc_ns, b->d_scan_ws, b->d_rws, b->d_out_off, b->d_out,
-                  b->d_exact_ids, b->d_exact_cnt, b->d_exact_off, b->d_calls, b->d_r16,
-                  b->blk[0].d_words, b->blk[0].d_heads, b->blk[1].d_words, b->blk[1].d_heads, b->d_blk_flag};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  if (b->h_totals) (void)hipHostFree(b->h_totals);
-  if (b->h_off_pin) (void)hipHostFree(b->h_off_pin);
-  if (b->h_blk_flag) (void)hipHostFree(b->h_blk_flag);
-  for (hipEvent_t e : b->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (b->stream && b->stream_own) (void)hipStreamDestroy(b->stream);
-  delete b;
+dtk_batch::~dtk_batch() {
+  if (stream) (void)hipStreamSynchronize(stream);
+  if (up_stream) (void)hipStreamSynchronize(up_stream);
+  if (dl_begun && !dl_waited) (void)hipEventSynchronize(ev_dl);
 }
+
+extern "C" void dtk_batch_free(dtk_batch *b) { delete b; }
 
 extern "C" void *dtk_batch_stream(dtk_batch *b) { return b ? (void *)b->stream : nullptr; }
 
 // Everything this batch has enqueued so far has finished.  With a stream of its own: the stream; on a lent stream
 // (shared with other batches) only the batch's own last run, by its event.
 static int wait_ran(dtk_batch *b) {  // the kernels of the batch's last run (not an upload on the lent upload stream)
-  if (b->stream_own) HIP_TRY(hipStreamSynchronize(b->stream));
+  if (b->stream.mine) HIP_TRY(hipStreamSynchronize(b->stream));
   else if (b->ev_ran_valid) HIP_TRY(hipEventSynchronize(b->ev_ran));
   return DTK_OK;
 }
@@ -146,14 +95,9 @@ extern "C" int dtk_batch_set_streams(dtk_batch *b, void *compute, void *upload) 
   if (!b) return DTK_E_ARG;
   int rc = wait_own(b);
   if (rc != DTK_OK) return rc;
-  if (compute) {
-    if (b->stream_own && b->stream) HIP_TRY(hipStreamDestroy(b->stream));
-    b->stream = (hipStream_t)compute;
-    b->stream_own = false;
-  }
+  if (compute && (rc = b->stream.lend((hipStream_t)compute)) != DTK_OK) return rc;
   b->up_stream = (hipStream_t)upload;
-  if (upload && !b->ev_up) HIP_TRY(hipEventCreateWithFlags(&b->ev_up, hipEventDisableTiming));
-  return DTK_OK;
+  return upload ? b->ev_up.ensure(hipEventDisableTiming) : DTK_OK;
 }
 
 extern "C" int dtk_batch_set_input(dtk_batch *b, const uint8_t *text, const uint64_t *doc_off, uint32_t n_docs) {
@@ -170,8 +114,8 @@ extern "C" int dtk_batch_set_input(dtk_batch *b, const uint8_t *text, const uint
   { int rc = wait_own(b); if (rc != DTK_OK) return rc; }  // the previous run may still read the buffers
   hipStream_t us = b->up_stream ? b->up_stream : b->stream;
   if (total) HIP_TRY(hipMemcpyAsync(b->d_text_own, text, total, hipMemcpyHostToDevice, us));
-  memcpy(b->h_off_pin, doc_off, ((size_t)n_docs + 1) * 8);
-  HIP_TRY(hipMemcpyAsync(b->d_off_own, b->h_off_pin, ((uint64_t)n_docs + 1) * 8, hipMemcpyHostToDevice, us));
+  memcpy(b->h_off_pin.p, doc_off, ((size_t)n_docs + 1) * 8);
+  HIP_TRY(hipMemcpyAsync(b->d_off_own, b->h_off_pin.p, ((uint64_t)n_docs + 1) * 8, hipMemcpyHostToDevice, us));
   if (b->up_stream) { HIP_TRY(hipEventRecord(b->ev_up, us)); b->up_pending = true; }
   // the lane plan only depends on the offsets: a stream of equally shaped batches keeps it
   const bool same = b->plan_valid && b->d_off == b->d_off_own && b->n_docs == n_docs &&
@@ -288,7 +232,7 @@ static int plan_lanes(dtk_batch *b) {
   }
   b->chunk = C;
   auto flush = [&]() -> int {
-    int rc_ = pin_fit(b->h_plan, stage.size());
+    int rc_ = b->h_plan.fit(stage.size());
     if (rc_ != DTK_OK) return rc_;
     memcpy(b->h_plan.p, stage.data(), stage.size());
     hipStream_t us = b->up_stream ? b->up_stream : b->stream;
@@ -317,20 +261,14 @@ static int plan_lanes(dtk_batch *b) {
   std::vector<uint32_t> lane_doc((size_t)lanes);
   for (uint32_t d = 0; d < nd; d++)
     for (uint32_t L = chunk_off[d]; L < chunk_off[d + 1]; L++) lane_doc[L] = d;
+  // (a group's capacity is 0 while its arrays are regrown, and every array holds at least what it says afterwards)
   if (lanes > b->lane_cap) {
-    void *old[] = {b->d_lane_doc, b->d_lane_cnt, b->d_lane_start, b->d_lane_end, b->d_lane_plan};
-    for (void *p : old)
-      if (p) HIP_TRY(hipFree(p));
-    b->d_lane_doc = nullptr;
-    b->d_lane_cnt = nullptr;
-    b->d_lane_start = b->d_lane_end = nullptr;
-    b->d_lane_plan = nullptr;
     const uint64_t cap = lanes + lanes / 8 + 64;
-    HIP_TRY(hipMalloc((void **)&b->d_lane_doc, cap * 4));
-    HIP_TRY(hipMalloc((void **)&b->d_lane_cnt, cap * sizeof(DtkLaneCount)));
-    HIP_TRY(hipMalloc((void **)&b->d_lane_start, cap * sizeof(DtkLaneState)));
-    HIP_TRY(hipMalloc((void **)&b->d_lane_end, cap * sizeof(DtkLaneState)));
-    HIP_TRY(hipMalloc((void **)&b->d_lane_plan, cap * sizeof(DtkLanePlan)));
+    int rc_;
+    b->lane_cap = 0;
+    if ((rc_ = b->d_lane_doc.fit(cap, cap)) || (rc_ = b->d_lane_cnt.fit(cap, cap)) || (rc_ = b->d_lane_start.fit(cap, cap)) ||
+        (rc_ = b->d_lane_end.fit(cap, cap)) || (rc_ = b->d_lane_plan.fit(cap, cap)))
+      return rc_;
     b->lane_cap = (uint32_t)cap;
   }
   // segments of DTK_SEG_LANES lanes: the unit of k_compact for documents with many lanes
@@ -351,14 +289,11 @@ static int plan_lanes(dtk_batch *b) {
   doc_seg0[nd] = (uint32_t)seg_doc.size();
   const uint32_t ns = (uint32_t)seg_doc.size();
   if (ns > b->seg_cap) {
-    void *old[] = {b->d_seg_tab, b->d_seg_sum, b->d_seg_in};
-    for (void *p : old)
-      if (p) HIP_TRY(hipFree(p));
-    b->d_seg_tab = nullptr; b->d_seg_sum = nullptr; b->d_seg_in = nullptr;
-    const uint64_t cap = (uint64_t)ns + ns / 8 + 64;
-    HIP_TRY(hipMalloc((void **)&b->d_seg_tab, (3 * cap + 2 * ((uint64_t)b->max_docs + 1)) * 4));
-    HIP_TRY(hipMalloc((void **)&b->d_seg_sum, cap * sizeof(DtkSegSum)));
-    HIP_TRY(hipMalloc((void **)&b->d_seg_in, cap * sizeof(DtkSegIn)));
+    const uint64_t cap = (uint64_t)ns + ns / 8 + 64, tab = 3 * cap + 2 * ((uint64_t)b->max_docs + 1);
+    int rc_;
+    b->seg_cap = 0;
+    if ((rc_ = b->d_seg_tab.fit(tab, tab)) || (rc_ = b->d_seg_sum.fit(cap, cap)) || (rc_ = b->d_seg_in.fit(cap, cap)))
+      return rc_;
     b->seg_cap = (uint32_t)cap;
   }
   b->n_segs = ns;
@@ -385,7 +320,7 @@ DtkWalkArgs walk_args(dtk_batch *b) {
   w.sym = sym_of(b); w.doc_off = b->d_off; w.n_docs = b->n_docs;
   w.bits = b->d_bits; w.bit_words = b->bit_words; w.doc_tail = b->d_doc_tail; w.status = b->d_status;
   w.tok_cnt = b->d_tok_cnt; w.sent_cnt = b->d_sent_cnt; w.text_cnt = b->d_text_cnt;
-  w.steps = (unsigned long long *)(b->d_totals + 16);
+  w.steps = (unsigned long long *)dtk_step_stripe(b->d_totals, 0);
   w.step_factor = 2048;  // look-ahead is bounded by the 1024-rune window (matrix.go:365)
   return w;
 }
@@ -403,6 +338,16 @@ static DtkSpecArgs spec_args(dtk_batch *b, bool redo) {
   const bool lds = g_dbg.lds_bits != 0;
   s.lds_words = (lds && b->chunk <= DTK_LDS_BIT_CHUNK_MAX) ? DTK_LDS_BIT_WORDS(b->chunk) : 0u;
   return s;
+}
+
+// the counter of documents still to repair that the last run's scan and compaction looked at: behind its device-side rounds
+static uint32_t *n_bad_now(dtk_batch *b) { return b->d_totals->n_bad + b->dev_rounds; }
+
+// any_irregular and any_eot (one word) as a compaction launched after the run left them
+static int reread_flags(dtk_batch *b) {
+  HIP_TRY(hipMemcpyAsync(&b->h_totals->any_irregular, &b->d_totals->any_irregular, 8, hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  return DTK_OK;
 }
 
 static uint32_t cmp_mask_of(const dtk_model *m) {
@@ -423,8 +368,8 @@ static int launch_compact2(dtk_batch *b, int which) {
   a.n_segs = b->n_segs; a.chunk_off = b->d_chunk_off; a.lane_start = b->d_lane_start; a.lane_cnt = b->d_lane_cnt;
   a.seg_sum = b->d_seg_sum; a.seg_in = b->d_seg_in;
   a.doc_seq = b->d_seg_tab + 3 * (size_t)b->seg_cap + b->max_docs + 1;
-  a.any_irregular = (uint32_t *)(b->d_totals + 7);
-  a.any_eot = a.any_irregular + 1;
+  a.any_irregular = &b->d_totals->any_irregular;
+  a.any_eot = &b->d_totals->any_eot;
   b->last_args = a;
   if (seg && (which & 1) && dtk_launch_seg_prepare(&a, b->d_seg_tab + 3 * (size_t)b->seg_cap, b->stream))
     return hip_fail(hipGetLastError(), "segment carries");
@@ -476,7 +421,7 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
     const size_t nd = b->n_docs;
     uint8_t *q = b->d_acc;
     b->d_tok_off = b->d_csr; b->d_sent_off = b->d_csr + (nd + 1); b->d_text_off = b->d_csr + 2 * (nd + 1);
-    b->d_totals = (uint64_t *)q; q += DTK_TOTALS_BYTES;  // (the striped lookup counters right behind the totals)
+    b->d_totals = (DtkTotalsDev *)q; q += DTK_TOTALS_BYTES;  // (the striped lookup counters right behind the totals)
     b->d_tok_cnt = (uint64_t *)q; q += (nd + 1) * 8;
     b->d_sent_cnt = (uint64_t *)q; q += (nd + 1) * 8;
     b->d_text_cnt = (uint64_t *)q; q += (nd + 1) * 8;
@@ -488,7 +433,7 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
     b->bit_words = (uint32_t)(((b->total + nd) / 32 + 8) & ~(uint64_t)3);  // 16-byte multiples per kind
     // (the event bitmaps are cleared by k_symbolize's blocks, unless it does not run)
     const bool fold = b->total > 0;
-    // ... and the accumulator block too, once it has been cleared whole (totals[6], which k_symbolize's own blocks
+    // ... and the accumulator block too, once it has been cleared whole (invalid_epoch, which k_symbolize's own blocks
     // write, is left out there: it holds the number of the last run that saw invalid UTF-8)
     fold_acc = fold && b->acc_primed && acc_used / 16 < 0xFFFFFFFFull && !g_dbg.clear_kernel;
     if (!fold_acc) {
@@ -500,8 +445,9 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
   }
   STAGE(1);
   if (dtk_launch_symbolize(b->d_text, b->d_off, b->n_docs, b->total, &m->sig, b->d_sym,
-                           b->d_text == b->d_text_own, b->d_blk_doc, (unsigned long long *)(b->d_totals + 6), b->d_rsbits,
-                           b->d_bits, b->bit_words, fold_acc ? b->d_acc : nullptr, acc_bytes, ++b->epoch, s))
+                           b->d_text == b->d_text_own, b->d_blk_doc, (unsigned long long *)&b->d_totals->invalid_epoch,
+                           (uint32_t *)b->d_rsbits.p, b->d_bits, b->bit_words, fold_acc ? b->d_acc.p : nullptr, acc_bytes,
+                           ++b->epoch, s))
     return hip_fail(hipGetLastError(), "symbolize");
   STAGE(2);
   DtkWalkArgs w = walk_args(b);
@@ -514,7 +460,7 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
   } else {
     DtkSpecArgs sp = spec_args(b, false);
     sp_first = sp;
-    uint32_t *nb = (uint32_t *)(b->d_totals + 8);  // nb[0]: broken documents after the first pass, nb[r + 1]: after round r
+    uint32_t *nb = b->d_totals->n_bad;  // nb[0]: broken documents after the first pass, nb[r + 1]: after round r
     // DATOK_SPLIT_START=1: start records and chunk walk as two launches (the repair rounds' kernels)
     const bool split = g_dbg.split_start != 0 || sp.lds_words == 0;  // (k_spec_both reports through the wave's LDS bitmaps)
     // Device-side repair: if the batch's last run had to repair (text with tags, say), two repair rounds are
@@ -546,17 +492,17 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
     }
   }
   DtkCompactArgs c{};
-  c.text = b->d_text; c.rs_bits = b->d_rsbits; c.doc_off = b->d_off; c.n_docs = b->n_docs;
+  c.text = b->d_text; c.rs_bits = (const uint32_t *)b->d_rsbits.p; c.doc_off = b->d_off; c.n_docs = b->n_docs;
   c.bits = b->d_bits; c.bit_words = b->bit_words; c.doc_tail = b->d_doc_tail; c.status = b->d_status;
   c.flags = flags & DTK_NEWLINE_AFTER_EOT; c.kind = m->kind;
-  c.totals = b->d_totals;
+  c.totals = &b->d_totals->n_tok;
   // rows are sized by the walk's own counts (no counting pass)
   if (dtk_launch_scan3(b->d_tok_cnt, b->d_sent_cnt, b->d_text_cnt, b->d_tok_off, b->d_sent_off, b->d_text_off,
-                       b->n_docs, b->d_totals, b->d_status, b->d_scan_ws, fix_in_scan ? &sp_first : nullptr, b->d_redo,
-                       (uint32_t *)(b->d_totals + 8), b->chunk ? (const uint32_t *)(b->d_totals + 8) + b->dev_rounds : nullptr, s))
+                       b->n_docs, &b->d_totals->n_tok, b->d_status, b->d_scan_ws, fix_in_scan ? &sp_first : nullptr, b->d_redo,
+                       b->d_totals->n_bad, b->chunk ? n_bad_now(b) : nullptr, s))
     return hip_fail(hipGetLastError(), "scan");
   STAGE(8);
-  c.skip_if = b->chunk ? (const uint32_t *)(b->d_totals + 8) + b->dev_rounds : nullptr;
+  c.skip_if = b->chunk ? n_bad_now(b) : nullptr;
   b->last_args = c;
   // (the kernel for documents with EOT calls only if this batch object's last run had such documents; finish()
   //  launches it when the other kernel reports one after all)
@@ -573,7 +519,7 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
     if (rc != DTK_OK) return rc;
   }
   HIP_TRY(hipMemcpyAsync(b->h_totals, b->d_totals, DTK_TOTALS_BYTES, hipMemcpyDeviceToHost, s));
-  if (!b->ev_ran) HIP_TRY(hipEventCreateWithFlags(&b->ev_ran, hipEventDisableTiming));
+  if ((rc = b->ev_ran.ensure(hipEventDisableTiming)) != DTK_OK) return rc;
   HIP_TRY(hipEventRecord(b->ev_ran, s));
   b->ev_ran_valid = true;
   b->ran = true;
@@ -594,8 +540,9 @@ extern "C" int dtk_batch_done(dtk_batch *b) {
 
 extern "C" int dtk_batch_set_profiling(dtk_batch *b, int enable) {
   if (!b) return DTK_E_ARG;
-  if (enable && !b->ev[0])
-    for (auto &e : b->ev) HIP_TRY(hipEventCreate(&e));
+  if (enable)
+    for (Event &e : b->ev)
+      if (const int rc = e.ensure(hipEventDefault)) return rc;
   b->profiling = enable != 0;
   return DTK_OK;
 }
@@ -627,14 +574,11 @@ static int run_exact(dtk_batch *b) {
   const uint32_t n = (uint32_t)b->h_exact_ids.size();
   if (n == 0) return DTK_OK;
   if (n > b->exact_cap) {
-    void *old[] = {b->d_exact_ids, b->d_exact_cnt, b->d_exact_off};
-    for (void *p : old)
-      if (p) HIP_TRY(hipFree(p));
-    b->d_exact_ids = b->d_exact_cnt = nullptr; b->d_exact_off = nullptr; b->exact_cap = 0;
     const uint64_t cap = (uint64_t)n + n / 4 + 16;
-    HIP_TRY(hipMalloc((void **)&b->d_exact_ids, cap * 4));
-    HIP_TRY(hipMalloc((void **)&b->d_exact_cnt, cap * 4));
-    HIP_TRY(hipMalloc((void **)&b->d_exact_off, (cap + 1) * 8));
+    int rc;
+    b->exact_cap = 0;
+    if ((rc = b->d_exact_ids.fit(cap, cap)) || (rc = b->d_exact_cnt.fit(cap, cap)) || (rc = b->d_exact_off.fit(cap + 1, cap + 1)))
+      return rc;
     b->exact_cap = (uint32_t)cap;
   }
   HIP_TRY(hipMemcpy(b->d_exact_ids, b->h_exact_ids.data(), (size_t)n * 4, hipMemcpyHostToDevice));
@@ -651,12 +595,7 @@ static int run_exact(dtk_batch *b) {
   b->h_exact_off.assign((size_t)n + 1, 0);
   for (uint32_t i = 0; i < n; i++) b->h_exact_off[i + 1] = b->h_exact_off[i] + cnt[i];
   const uint64_t total = b->h_exact_off[n];
-  if (total > b->calls_cap) {
-    if (b->d_calls) HIP_TRY(hipFree(b->d_calls));
-    b->d_calls = nullptr; b->calls_cap = 0;
-    HIP_TRY(hipMalloc((void **)&b->d_calls, (total + total / 4 + 16) * sizeof(DtkCall)));
-    b->calls_cap = total + total / 4 + 16;
-  }
+  if (const int rc = b->d_calls.fit(total, total + total / 4 + 16)) return rc;
   HIP_TRY(hipMemcpy(b->d_exact_off, b->h_exact_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
   X.calls = b->d_calls;
   X.pass = 1;
@@ -668,7 +607,7 @@ static int run_exact(dtk_batch *b) {
   HIP_TRY(hipStreamSynchronize(s));
   uint64_t flagged = 0;
   for (uint32_t d = 0; d < nd; d++) flagged += st[d] != 0;
-  b->h_totals[3] = flagged;
+  b->h_totals->n_flagged = flagged;
   return DTK_OK;
 }
 
@@ -683,7 +622,7 @@ int finish(dtk_batch *b) {
   // time (dtk_batch_run) have run on the device already; what is still broken behind them is repaired from here,
   // and the scan / compaction -- which did nothing in that case -- run afterwards.
   if (b->chunk != 0) {
-    const uint32_t *hnb = (const uint32_t *)(b->h_totals + 8);
+    const uint32_t *hnb = b->h_totals->n_bad;
     for (uint32_t r = 0; r < b->dev_rounds; r++)
       if (hnb[r] != 0) b->repair_rounds++;
     uint32_t left = hnb[b->dev_rounds];
@@ -692,7 +631,7 @@ int finish(dtk_batch *b) {
       const dtk_model *m = b->last_model;
       hipStream_t s = b->stream;
       DtkWalkArgs w = walk_args(b);
-      uint32_t *n_bad = (uint32_t *)(b->d_totals + 8) + b->dev_rounds;  // (the counter the scan / compaction looked at)
+      uint32_t *n_bad = n_bad_now(b);  // (the counter the scan / compaction looked at)
       // Every round verifies at least one more lane of every broken document (the first bad lane started from a true
       // state), so the longest document's lane count bounds the rounds.  Should they run out all the same, the batch
       // is walked again with one lane per document -- no speculation, nothing to repair.
@@ -734,7 +673,7 @@ int finish(dtk_batch *b) {
         }
       }
       if (dtk_launch_scan3(b->d_tok_cnt, b->d_sent_cnt, b->d_text_cnt, b->d_tok_off, b->d_sent_off, b->d_text_off,
-                         b->n_docs, b->d_totals, b->d_status, b->d_scan_ws, nullptr, nullptr, nullptr, nullptr, s))
+                         b->n_docs, &b->d_totals->n_tok, b->d_status, b->d_scan_ws, nullptr, nullptr, nullptr, nullptr, s))
         return hip_fail(hipGetLastError(), "scan");
       b->last_args.skip_if = nullptr;
       int rc = launch_compact2(b, 3);
@@ -744,38 +683,33 @@ int finish(dtk_batch *b) {
     }
     b->expect_repairs = b->repair_rounds != 0;
   }
-  const uint64_t nt = b->h_totals[0], ns = b->h_totals[1], nx = b->h_totals[2];
-  b->n_invalid = b->h_totals[6] == b->epoch ? 1u : 0u;  // (the number of the last run that saw one: k_symbolize)
+  const uint64_t nt = b->h_totals->n_tok, ns = b->h_totals->n_sent, nx = b->h_totals->n_text;
+  b->n_invalid = b->h_totals->invalid_epoch == b->epoch ? 1u : 0u;  // (the number of the last run that saw one: k_symbolize)
   if (nt > b->tok_cap || ns > b->sent_cap || nx > b->text_cap) {
     b->results_changed = true;
     int rc = alloc_outputs(b, nt + nt / 8 + 16, ns + ns / 8 + 16, nx + nx / 8 + 16);
     if (rc != DTK_OK) return rc;
-    rc = launch_compact2(b, 3);
-    if (rc != DTK_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(b->h_totals + 7, b->d_totals + 7, 8, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
+    if ((rc = launch_compact2(b, 3)) != DTK_OK || (rc = reread_flags(b)) != DTK_OK) return rc;
   }
   // documents with EOT calls that the first compaction kernel left alone
   {
-    const bool eot = (b->h_totals[7] >> 32) != 0;
+    const bool eot = b->h_totals->any_eot != 0;
     if (eot && !b->ran_full) {
       b->results_changed = true;
-      int rc = launch_compact2(b, 2);
-      if (rc != DTK_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(b->h_totals + 7, b->d_totals + 7, 8, hipMemcpyDeviceToHost, b->stream));
-      HIP_TRY(hipStreamSynchronize(b->stream));
+      int rc;
+      if ((rc = launch_compact2(b, 2)) != DTK_OK || (rc = reread_flags(b)) != DTK_OK) return rc;
     }
     b->expect_eot = eot;
   }
   // documents whose calls are not in position order (ST_IRREGULAR): their rows come from the exact pass
   b->h_exact_ids.clear(); b->h_exact_off.assign(1, 0); b->h_calls.clear();
-  if ((uint32_t)b->h_totals[7] != 0) {
+  if (b->h_totals->any_irregular != 0) {
     b->results_changed = true;
     int rc = run_exact(b);
     if (rc != DTK_OK) return rc;
   }
   // the arrays k_to_host brought over inside the run count if the kernel made its copy and nothing was touched since
-  if (b->eager_fields && !b->results_changed && b->h_totals[11] == b->epoch) {
+  if (b->eager_fields && !b->results_changed && b->h_totals->to_host_epoch == b->epoch) {
     b->dl_begun = true;
     b->dl_waited = true;
     b->dl_fields = b->eager_fields;
@@ -785,9 +719,9 @@ int finish(dtk_batch *b) {
   b->totals.n_tokens = nt;
   b->totals.n_sent = ns;
   b->totals.n_texts = nx;
-  b->totals.n_flagged = b->h_totals[3];
+  b->totals.n_flagged = b->h_totals->n_flagged;
   b->totals.walk_steps = 0;
-  for (uint32_t i = 0; i < DTK_STEP_STRIPES; i++) b->totals.walk_steps += b->h_totals[16 + 16 * i];
+  for (uint32_t i = 0; i < DTK_STEP_STRIPES; i++) b->totals.walk_steps += *dtk_step_stripe(b->h_totals, i);
   b->totals.n_lanes = b->chunk ? b->n_lanes : b->n_docs;
   b->totals.chunk_bytes = b->chunk;
   b->totals.repair_rounds = b->repair_rounds;

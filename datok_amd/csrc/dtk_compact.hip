@@ -935,8 +935,8 @@ __global__ __launch_bounds__(SCAN1_TB) void k_scan3(const uint64_t *ca, const ui
   }
   if (tid == T - 1) {
     a[n] = ba + xa; b[n] = bb + xb; c[n] = bc + xc;
-    totals[0] = ba + xa; totals[1] = bb + xb; totals[2] = bc + xc;
-    totals[3] = bf + xf;
+    totals[0] = ba + xa; totals[1] = bb + xb; totals[2] = bc + xc;  // DtkTotalsDev: n_tok, n_sent, n_text,
+    totals[3] = bf + xf;                                            // n_flagged (its first four words, asserted there)
   }
 }
 

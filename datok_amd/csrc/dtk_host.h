@@ -9,17 +9,9 @@
 
 #include "../../include/datok_gpu.h"
 #include "dtk_internal.h"
+#include "dtk_own.h"  // the error state (hip_fail, HIP_TRY) and the owning types
 
 #pragma GCC visibility push(hidden)
-
-// --------------------------------------------------------------- error state
-
-int hip_fail(hipError_t e, const char *what);
-#define HIP_TRY(call)                                   \
-  do {                                                  \
-    hipError_t e_ = (call);                             \
-    if (e_ != hipSuccess) return hip_fail(e_, #call);   \
-  } while (0)
 
 // ---------------------------------------------------------------- test hooks
 //
@@ -65,11 +57,11 @@ struct dtk_model {
   std::vector<uint16_t> sigma_syms;
   uint16_t ascii[256];
   // device
-  void *d_tab = nullptr;
-  uint16_t *d_ascii = nullptr;
-  uint32_t *d_runes = nullptr;
-  uint16_t *d_syms = nullptr;
-  void *d_codes = nullptr;  // code_entry [256] u16, code_lt256 [256] u8, code_runes [n_runes] u8
+  DevArray<uint8_t> d_tab;
+  DevArray<uint16_t> d_ascii;
+  DevArray<uint32_t> d_runes;
+  DevArray<uint16_t> d_syms;
+  DevArray<uint8_t> d_codes;  // code_entry [256] u16, code_lt256 [256] u8, code_runes [n_runes] u8
   DtkTableDev tab{};
   DtkSigmaDev sig{};
 };
@@ -83,25 +75,25 @@ int build_foma(dtk_model *m, const std::vector<uint8_t> &raw);
 // -------------------------------------------------------------------- batch
 
 struct dtk_batch {
+  ~dtk_batch();  // waits for what is in flight; the members then release themselves, in reverse order
   int device = 0;
-  hipStream_t stream = nullptr;
+  Stream stream;  // (declared before the memory: destroyed after it)
   uint64_t max_bytes = 0;
   uint32_t max_docs = 0;
   // inputs
-  uint8_t *d_text_own = nullptr;
-  uint64_t *d_off_own = nullptr;
+  DevArray<uint8_t> d_text_own;
+  DevArray<uint64_t> d_off_own;
   const uint8_t *d_text = nullptr;
   const uint64_t *d_off = nullptr;
   uint32_t n_docs = 0;
   uint64_t total = 0;
   // intermediates
-  uint16_t *d_sym = nullptr;
-  uint32_t *d_rsbits = nullptr;                // rune-start bitmap of the input (1 bit per byte)
-  uint32_t *d_bits = nullptr;                  // event bitmaps of the walk (EVB_KINDS kinds), cleared every run
+  DevArray<uint16_t> d_sym;
+  DevArray<uint8_t> d_rsbits;                  // rune-start bitmap of the input (1 bit per byte, read as 32-bit words)
+  DevArray<uint32_t> d_bits;                   // event bitmaps of the walk (EVB_KINDS kinds), cleared every run
   uint32_t bit_words = 0;                      // words per kind of the current input
   uint32_t *d_doc_tail = nullptr;              // per document: final SentenceEnd / TextEnd (carved from d_acc)
-  uint8_t *d_acc = nullptr;                    // per-document accumulators + totals (one memset)
-  uint64_t acc_bytes = 0;
+  DevArray<uint8_t> d_acc;                     // per-document accumulators + totals (one memset)
   uint32_t *d_status = nullptr;
   // speculative chunk lanes
   std::vector<uint64_t> h_doc_off;   // host copy of the document offsets (lane planning)
@@ -111,31 +103,30 @@ struct dtk_batch {
   uint32_t chunk = 0;                // chunk size of the current plan (0 = none)
   bool plan_valid = false;
   uint32_t n_lanes = 0, lane_cap = 0;
-  uint32_t *d_lane_doc = nullptr, *d_chunk_off = nullptr, *d_redo = nullptr;
+  DevArray<uint32_t> d_lane_doc, d_chunk_off, d_redo;
   // long documents are compacted in segments of DTK_SEG_LANES lanes (tables built with the lane plan)
-  uint32_t *d_seg_tab = nullptr;     // seg_doc | seg_lane0 | seg_nl | doc_seg0
-  DtkSegSum *d_seg_sum = nullptr;
-  DtkSegIn *d_seg_in = nullptr;
+  DevArray<uint32_t> d_seg_tab;      // seg_doc | seg_lane0 | seg_nl | doc_seg0
+  DevArray<DtkSegSum> d_seg_sum;
+  DevArray<DtkSegIn> d_seg_in;
   uint32_t n_segs = 0, seg_cap = 0;
   bool long_docs = false;            // some document has more than one segment
   uint32_t max_doc_lanes = 0;        // lanes of the longest document (bounds the repair rounds)
-  uint32_t *d_blk_doc = nullptr;     // document of the first byte of every 4 KiB input block
+  DevArray<uint32_t> d_blk_doc;      // document of the first byte of every 4 KiB input block
   // compaction: documents of at most small_max bytes go one per lane (k_compact_small), the others one per wave
   uint32_t small_max = 0, n_big = 0;
-  uint32_t *d_big_docs = nullptr;    // ids of the documents above small_max
-  uint32_t *d_first_bad = nullptr, *d_fail_lane = nullptr;
-  DtkLaneCount *d_lane_cnt = nullptr;
-  DtkLaneState *d_lane_start = nullptr, *d_lane_end = nullptr;
-  DtkLanePlan *d_lane_plan = nullptr;
+  DevArray<uint32_t> d_big_docs;     // ids of the documents above small_max
+  uint32_t *d_first_bad = nullptr, *d_fail_lane = nullptr;  // (carved from d_acc)
+  DevArray<DtkLaneCount> d_lane_cnt;
+  DevArray<DtkLaneState> d_lane_start, d_lane_end;
+  DevArray<DtkLanePlan> d_lane_plan;
   uint32_t repair_rounds = 0;        // of the last run
   const dtk_model *last_model = nullptr;
   uint32_t last_flags = 0;
-  uint64_t *d_csr = nullptr;  // tok_off | sent_off | text_off
+  DevArray<uint64_t> d_csr;  // tok_off | sent_off | text_off
   uint64_t *d_tok_off = nullptr, *d_sent_off = nullptr, *d_text_off = nullptr;
   uint64_t *d_tok_cnt = nullptr, *d_sent_cnt = nullptr, *d_text_cnt = nullptr;  // per-document counts
-  uint64_t *d_scan_ws = nullptr;  // tile sums of the multi-block scan (many documents)
-  uint64_t *d_totals = nullptr;  // [0..3] scan totals, [4] walk steps, [6] invalid UTF-8 bytes, [7] irregular flag,
-                                 // [8..9] as u32[4]: documents to repair after the first pass / after each device-side round
+  DevArray<uint64_t> d_scan_ws;  // tile sums of the multi-block scan (many documents)
+  DtkTotalsDev *d_totals = nullptr;  // the head of d_acc
   uint32_t dev_rounds = 0;       // repair rounds enqueued ahead of time in the last run
   bool expect_repairs = false;   // the last run needed repairs: enqueue rounds ahead of time in the next one
   uint32_t round_limit = 0xFFFFFFFFu;  // repair rounds from the host before the one-lane-per-document fallback (DATOK_ROUND_LIMIT)
@@ -143,35 +134,35 @@ struct dtk_batch {
   uint64_t epoch = 0;            // number of the run (k_symbolize marks runs that saw invalid UTF-8 with it)
   bool expect_eot = false;       // the last run had documents with EOT calls: launch their compaction kernel with the run
   bool ran_full = false;         // that kernel has run since the last dtk_batch_run
-  uint64_t *h_totals = nullptr;  // pinned
-  uint64_t *h_off_pin = nullptr; // pinned staging of the document offsets (a copy from pageable memory would block until
+  PinBuf h_totals_pin;           // d_totals and the lookup counters behind it (DTK_TOTALS_BYTES), as the run left them
+  DtkTotalsDev *h_totals = nullptr;
+  PinBuf h_off_pin;              // staging of the document offsets (a copy from pageable memory would block until
                                  // the text copy in front of it has finished: 0.7 ms per 16 MiB batch)
   // outputs (grown on demand, never inside a run unless a re-launch is needed)
   uint64_t tok_cap = 0, sent_cap = 0, text_cap = 0;
-  int32_t *d_rstart = nullptr, *d_rend = nullptr, *d_sent = nullptr;
-  uint32_t *d_bstart = nullptr, *d_bend = nullptr, *d_ttok = nullptr, *d_tsent = nullptr;
-  uint32_t *d_sbefore = nullptr, *d_ts_end = nullptr, *d_doc_ns = nullptr;  // renderer inputs (compact)
+  DevArray<int32_t> d_rstart, d_rend, d_sent;
+  DevArray<uint32_t> d_bstart, d_bend, d_ttok, d_tsent;
+  DevArray<uint32_t> d_sbefore, d_ts_end, d_doc_ns;  // renderer inputs (compact)
   // device rendering of the writer output (dtk_batch_render): workspace + output, grown on demand
-  uint64_t *d_rws = nullptr;  uint64_t rws_cap = 0;   // scans, tile sums, per-text regions (u64 words)
-  uint64_t *d_out_off = nullptr;
-  uint8_t *d_out = nullptr;   uint64_t out_cap = 0;
+  DevArray<uint64_t> d_rws;   // scans, tile sums, per-text regions (u64 words)
+  DevArray<uint64_t> d_out_off;
+  DevArray<uint8_t> d_out;
   uint64_t out_total = 0;
   uint64_t n_invalid = 0;     // nonzero: the last run saw invalid UTF-8 (each such byte prints as U+FFFD, 3 bytes)
   uint32_t render_flags = 0xFFFFFFFFu;  // flags of the rendering held in d_out (none)
   std::vector<uint8_t> h_out;
   std::vector<uint64_t> h_out_off;
   // the exact pass over ST_IRREGULAR documents (normally none): ids, call counts / offsets, calls
-  uint32_t *d_exact_ids = nullptr, *d_exact_cnt = nullptr;
-  uint64_t *d_exact_off = nullptr;
-  DtkCall *d_calls = nullptr;
+  DevArray<uint32_t> d_exact_ids, d_exact_cnt;
+  DevArray<uint64_t> d_exact_off;
+  DevArray<DtkCall> d_calls;
   uint32_t exact_cap = 0;
-  uint64_t calls_cap = 0;
   std::vector<uint32_t> h_exact_ids;
   std::vector<uint64_t> h_exact_off;
   std::vector<DtkCall> h_calls;
   // optional stage timing
   bool profiling = false;
-  hipEvent_t ev[DTK_N_STAGES + 1] = {};
+  Event ev[DTK_N_STAGES + 1];
   // last run
   bool ran = false, totals_valid = false;
   DtkCompactArgs last_args{};
@@ -182,41 +173,38 @@ struct dtk_batch {
   // (one buffer per row of host_arrays, dtk_results.cpp)
   enum { PB_R16, PB_RBLK, PB_RBLK_HEAD, PB_BBLK, PB_BBLK_HEAD, PB_RSTART, PB_REND, PB_BSTART, PB_BEND, PB_BITS, PB_TAIL, PB_SENT, PB_TTOK, PB_TSENT, PB_CSR, PB_STATUS,
          PB_N };
-  struct PinBuf { void *p = nullptr; size_t cap = 0; } pin[PB_N];
+  PinBuf pin[PB_N];
   PinBuf h_plan;            // staging of the lane plan's tables (plan_lanes)
   uint32_t fields = DTK_R_ALL;
-  uint32_t *d_r16 = nullptr;      // DTK_R_TOK_RUNE16: the packed rune offsets (filled on the download stream)
-  uint64_t r16_cap = 0;
+  DevArray<uint32_t> d_r16;       // DTK_R_TOK_RUNE16: the packed rune offsets (filled on the download stream)
   // DTK_R_TOK_RUNE_BLK ([0]) / DTK_R_TOK_BYTE_BLK ([1]): the blocked offsets, sized from tok_cap and packed on the
   // download stream like d_r16.  A block that does not fit 16 bits raises the pair's flag word; dtk_batch_result_host
   // reads its page-locked copy behind the download and brings the pair's 32-bit arrays in its place.
-  struct BlkPair { uint32_t *d_words = nullptr; void *d_heads = nullptr; uint64_t cap = 0; } blk[2];
-  uint32_t *d_blk_flag = nullptr;  // [2]
-  uint32_t *h_blk_flag = nullptr;  // [2], page-locked
+  struct BlkPair { DevArray<uint32_t> d_words; DevArray<dtk_off_block> d_heads; uint64_t cap = 0; } blk[2];  // cap: tokens
+  DevArray<uint32_t> d_blk_flag;   // [2]
+  PinBuf h_blk_flag;               // [2]
   uint32_t blk_pending = 0;        // blocked fields on their way whose flag nobody has looked at yet
   uint32_t blk_failed = 0;         // blocked fields the last run's offsets do not fit: the 32-bit arrays stand in
   uint64_t max_doc_bytes = 0;     // of the current input (what decides whether the narrow form exists)
   bool max_doc_valid = false;
-  hipStream_t dl_stream = nullptr;  // created with the first download, unless the caller lends one (a pipeline's slices share one:
-  bool dl_own = false;              //  the runtime maps streams onto four hardware queues, and streams that share a queue serialise)
-  hipEvent_t ev_ran = nullptr;      // behind the last launch of dtk_batch_run (dtk_batch_done)
+  Stream dl_stream;                 // created with the first download, unless the caller lends one (a pipeline's slices share one:
+                                    //  the runtime maps streams onto four hardware queues, and streams that share a queue serialise)
+  Event ev_ran;                     // behind the last launch of dtk_batch_run (dtk_batch_done)
   bool ev_ran_valid = false;
   // Lent streams (dtk_batch_set_streams): the batches of a pipeline share one stream for their kernels and one for their
   // uploads -- the runtime has four hardware queues, and a pipeline of any depth then needs three (kernels, uploads,
   // downloads).  The upload's end is an event the kernels wait for.
-  bool stream_own = true;
   hipStream_t up_stream = nullptr;  // null: uploads run on `stream`
-  hipEvent_t ev_up = nullptr;
+  Event ev_up;
   bool up_pending = false;          // an upload on up_stream has not been waited for yet
   uint32_t eager_fields = 0;  // the last run's k_to_host was asked for these (0: none); finish() decides whether it counts
   bool results_changed = false;  // finish() had to touch the result arrays after the run (repair, growth, EOT kernel, exact pass)
-  hipEvent_t ev_dl = nullptr;  // behind the batch's copies on the (possibly shared) download stream
+  Event ev_dl;                 // behind the batch's copies on the (possibly shared) download stream
   bool dl_waited = true;
   bool dl_begun = false;    // the copies of the last run's results have been enqueued
   uint32_t dl_fields = 0;   // ... these fields
 };
 
-int pin_fit(dtk_batch::PinBuf &pb, size_t n);
 int wait_own(dtk_batch *b);
 DtkSym sym_of(const dtk_batch *b);
 DtkWalkArgs walk_args(dtk_batch *b);

@@ -107,6 +107,29 @@ enum { DTK_KIND_MATRIX = 0, DTK_KIND_DA = 1 };
 #define DTK_STEP_STRIPES 32u
 #define DTK_TOTALS_BYTES (128u + DTK_STEP_STRIPES * 128u)  // a batch's totals block + the counters behind it
 
+// The totals block at the head of a batch's accumulators, with its page-locked mirror on the host.
+struct DtkTotalsDev {
+  uint64_t n_tok, n_sent, n_text, n_flagged;  // k_scan3: tokens, sentence ints, texts, documents with a status
+  uint64_t unused_4[2];
+  uint64_t invalid_epoch;              // k_symbolize: number of the last run that saw an invalid UTF-8 byte
+  uint32_t any_irregular, any_eot;     // the compaction: some document is ST_IRREGULAR / is left to k_compact_eot
+  uint32_t n_bad[4];                   // documents to repair after the first pass / after each device-side round
+  uint64_t render_total;               // host copy only: bytes of the rendering (dtk_results.cpp)
+  uint64_t to_host_epoch;              // k_to_host: number of the run whose results it copied
+  uint64_t unused_12[4];
+};
+static_assert(sizeof(struct DtkTotalsDev) == DTK_TOTALS_BYTES - DTK_STEP_STRIPES * 128u, "the block is 128 bytes");
+// k_scan3 writes totals[0..3]; k_compact*, k_to_host read totals[0..2]
+static_assert(offsetof(struct DtkTotalsDev, n_tok) == 0 && offsetof(struct DtkTotalsDev, n_sent) == 8 &&
+              offsetof(struct DtkTotalsDev, n_text) == 16 && offsetof(struct DtkTotalsDev, n_flagged) == 24,
+              "the scan's four totals are the first four words");
+// k_symbolize clears the block in 16-byte units and leaves one word of one unit alone
+static_assert(offsetof(struct DtkTotalsDev, invalid_epoch) % 16 == 0 &&
+              offsetof(struct DtkTotalsDev, any_irregular) == offsetof(struct DtkTotalsDev, invalid_epoch) + 8,
+              "invalid_epoch and the two flags share a 16-byte unit");
+// the striped lookup counters behind the block (DtkWalkArgs::steps): stripe i
+static inline uint64_t *dtk_step_stripe(struct DtkTotalsDev *t, uint32_t i) { return (uint64_t *)(t + 1) + 16u * i; }
+
 struct DtkTableDev {
   int kind;
   // matrix: state-major rows, cell (t, a) at tab[t*stride + a]; column 0 is all

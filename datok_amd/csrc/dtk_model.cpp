@@ -230,24 +230,25 @@ static void build_images(dtk_model *m, size_t tab_bytes, HostImages &im) {
 
 static int copy_images(dtk_model *m, const void *tab, size_t tab_bytes, const HostImages &im) {
   HIP_TRY(hipGetDevice(&m->device));
-  HIP_TRY(hipMalloc(&m->d_tab, std::max<size_t>(tab_bytes, 16) + im.slack));
-  HIP_TRY(hipMemset((char *)m->d_tab + tab_bytes, 0, im.slack));
+  auto make = [](auto &a, size_t n) { return a.fit(n, n); };
+  int rc;
+  if ((rc = make(m->d_tab, std::max<size_t>(tab_bytes, 16) + im.slack))) return rc;
+  HIP_TRY(hipMemset(m->d_tab + tab_bytes, 0, im.slack));
   HIP_TRY(hipMemcpy(m->d_tab, tab, tab_bytes, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc((void **)&m->d_ascii, 256 * sizeof(uint16_t)));
+  if ((rc = make(m->d_ascii, 256))) return rc;
   HIP_TRY(hipMemcpy(m->d_ascii, im.ascii_dev, 256 * sizeof(uint16_t), hipMemcpyHostToDevice));
   const size_t nr = im.nr;
-  HIP_TRY(hipMalloc((void **)&m->d_runes, std::max<size_t>(nr, 1) * sizeof(uint32_t)));
-  HIP_TRY(hipMalloc((void **)&m->d_syms, std::max<size_t>(nr, 1) * sizeof(uint16_t)));
+  if ((rc = make(m->d_runes, std::max<size_t>(nr, 1))) || (rc = make(m->d_syms, std::max<size_t>(nr, 1)))) return rc;
   if (nr) {
     HIP_TRY(hipMemcpy(m->d_runes, m->sigma_runes.data() + im.first, nr * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m->d_syms, im.syms_dev.data(), nr * sizeof(uint16_t), hipMemcpyHostToDevice));
   }
-  HIP_TRY(hipMalloc(&m->d_codes, 512 + im.bytes.size()));
+  if ((rc = make(m->d_codes, 512 + im.bytes.size()))) return rc;
   HIP_TRY(hipMemcpy(m->d_codes, im.entries.data(), 512, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy((char *)m->d_codes + 512, im.bytes.data(), im.bytes.size(), hipMemcpyHostToDevice));
-  m->sig.code_entry = (const uint16_t *)m->d_codes;
-  m->sig.code_lt256 = (const uint8_t *)m->d_codes + 512;
-  m->sig.code_runes = (const uint8_t *)m->d_codes + 768;
+  HIP_TRY(hipMemcpy(m->d_codes + 512, im.bytes.data(), im.bytes.size(), hipMemcpyHostToDevice));
+  m->sig.code_entry = (const uint16_t *)m->d_codes.p;
+  m->sig.code_lt256 = m->d_codes + 512;
+  m->sig.code_runes = m->d_codes + 768;
   m->sig.ascii = m->d_ascii;
   m->sig.runes = m->d_runes;
   m->sig.syms = m->d_syms;
@@ -602,7 +603,7 @@ extern "C" int dtk_model_load_mem(const void *gz_bytes, size_t n, dtk_model **ou
   if (dtk_device_count() <= 0) return DTK_E_NO_DEVICE;
   dtk_model *m = new dtk_model();
   const int rc = build_model(m, gz_bytes, n);
-  if (rc != DTK_OK) { dtk_model_free(m); return rc; }
+  if (rc != DTK_OK) { delete m; return rc; }
   *out = m;
   return DTK_OK;
 }
@@ -633,15 +634,7 @@ extern "C" int dtk_model_load(const char *path, dtk_model **out) {
   return dtk_model_load_mem(gz.data(), gz.size(), out);
 }
 
-extern "C" void dtk_model_free(dtk_model *m) {
-  if (!m) return;
-  if (m->d_tab) (void)hipFree(m->d_tab);
-  if (m->d_ascii) (void)hipFree(m->d_ascii);
-  if (m->d_runes) (void)hipFree(m->d_runes);
-  if (m->d_syms) (void)hipFree(m->d_syms);
-  if (m->d_codes) (void)hipFree(m->d_codes);
-  delete m;
-}
+extern "C" void dtk_model_free(dtk_model *m) { delete m; }
 
 extern "C" const char *dtk_model_type(const dtk_model *m) {
   return m->kind == DTK_KIND_MATRIX ? "MATOK" : "DATOK";

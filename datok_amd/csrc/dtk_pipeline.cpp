@@ -8,11 +8,12 @@
 #include <algorithm>
 #include <condition_variable>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
 
-#include "../../include/datok_gpu.h"
+#include "dtk_own.h"
 
 struct dtk_pipeline {
   uint64_t slice_bytes = 0;
@@ -25,7 +26,12 @@ struct dtk_pipeline {
   // Three streams for the whole pipeline, whatever its depth: uploads, kernels, downloads (the HIP runtime maps streams
   // onto four hardware queues; streams that share a queue serialise -- a stream per slot made depth 4 slower than 3).
   // Slices take turns on each: the link carries slice i + 2 in and slice i out while slice i + 1 is walked.
-  hipStream_t s_up = nullptr, s_run = nullptr, s_down = nullptr;
+  Stream s_up, s_run, s_down;
+  ~dtk_pipeline() {  // the batches before the streams they were lent
+    for (dtk_batch *b : slots) dtk_batch_free(b);
+    for (hipStream_t st : {s_up.s, s_run.s, s_down.s})
+      if (st) (void)hipStreamSynchronize(st);
+  }
 };
 
 extern "C" void *dtk_pinned_alloc(size_t n) {
@@ -42,39 +48,27 @@ extern "C" void dtk_pinned_free(void *p) {
 extern "C" int dtk_pipeline_create(uint64_t slice_bytes, uint32_t slice_docs, uint32_t depth, dtk_pipeline **out) {
   if (!out || slice_bytes == 0 || slice_docs == 0 || depth == 0 || depth > 16) return DTK_E_ARG;
   *out = nullptr;
-  dtk_pipeline *p = new dtk_pipeline();
+  std::unique_ptr<dtk_pipeline> p(new dtk_pipeline());
   p->slice_bytes = slice_bytes;
   p->slice_docs = slice_docs;
-  if (hipStreamCreateWithFlags(&p->s_up, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&p->s_run, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&p->s_down, hipStreamNonBlocking) != hipSuccess) {
-    dtk_pipeline_free(p);
-    return DTK_E_HIP;
-  }
+  int rc;
+  if ((rc = p->s_up.create()) || (rc = p->s_run.create()) || (rc = p->s_down.create())) return rc;
   for (uint32_t i = 0; i < depth; i++) {
     dtk_batch *b = nullptr;
-    int rc = dtk_batch_create(slice_bytes, slice_docs, &b);
-    if (rc == DTK_OK) {
-      p->slots.push_back(b);
-      rc = dtk_batch_set_streams(b, p->s_run, p->s_up);
-      if (rc == DTK_OK) rc = dtk_batch_set_download_stream(b, p->s_down);
-    }
-    if (rc != DTK_OK) { dtk_pipeline_free(p); return rc; }
+    if ((rc = dtk_batch_create(slice_bytes, slice_docs, &b)) != DTK_OK) return rc;
+    p->slots.push_back(b);
+    if ((rc = dtk_batch_set_streams(b, p->s_run, p->s_up)) != DTK_OK ||
+        (rc = dtk_batch_set_download_stream(b, p->s_down)) != DTK_OK)
+      return rc;
   }
   p->first.assign(depth, 0);
   p->count.assign(depth, 0);
   p->touched.assign(depth, 0);
-  *out = p;
+  *out = p.release();
   return DTK_OK;
 }
 
-extern "C" void dtk_pipeline_free(dtk_pipeline *p) {
-  if (!p) return;
-  for (dtk_batch *b : p->slots) dtk_batch_free(b);
-  for (hipStream_t st : {p->s_up, p->s_run, p->s_down})
-    if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-  delete p;
-}
+extern "C" void dtk_pipeline_free(dtk_pipeline *p) { delete p; }
 
 extern "C" int dtk_pipeline_set_chunking(dtk_pipeline *p, uint32_t chunk_bytes, uint32_t warm_bytes) {
   if (!p) return DTK_E_ARG;

@@ -22,6 +22,8 @@ struct HostArray {
   void (*view)(dtk_result_view *o, const void *p);  // where dtk_batch_result_host shows it
 };
 #define VIEW(f) [](dtk_result_view *o, const void *p) { o->f = static_cast<decltype(o->f)>(p); }
+// (Only the download stream's copies use kPerBlock: launch_to_host masks the fields with DTK_R_ALL, which holds no
+// blocked field, so the kind never reaches k_to_host -- where totals[3] would be DtkTotalsDev::n_flagged.)
 constexpr int kPerBlock = 3;
 constexpr uint32_t kBlkFields = DTK_R_TOK_RUNE_BLK | DTK_R_TOK_BYTE_BLK;
 constexpr uint32_t kBlkField[2] = {DTK_R_TOK_RUNE_BLK, DTK_R_TOK_BYTE_BLK};
@@ -33,7 +35,7 @@ uint64_t blocks_of(uint64_t tokens) { return (tokens + 63) / 64; }
 std::array<HostArray, dtk_batch::PB_N> host_arrays(const dtk_batch *b) {
   const uint64_t nd = b->n_docs;
   const HostArray t[] = {
-      {DTK_R_TOK_RUNE16, dtk_batch::PB_R16, b->d_r16, 4, 0, b->r16_cap, VIEW(tok_r16)},
+      {DTK_R_TOK_RUNE16, dtk_batch::PB_R16, b->d_r16, 4, 0, b->d_r16.cap, VIEW(tok_r16)},
       {DTK_R_TOK_RUNE_BLK, dtk_batch::PB_RBLK, b->blk[0].d_words, 4, 0, b->blk[0].cap, VIEW(tok_rblk)},
       {DTK_R_TOK_RUNE_BLK, dtk_batch::PB_RBLK_HEAD, b->blk[0].d_heads, sizeof(dtk_off_block), kPerBlock,
        blocks_of(b->blk[0].cap), VIEW(tok_rblk_head)},
@@ -61,23 +63,21 @@ std::array<HostArray, dtk_batch::PB_N> host_arrays(const dtk_batch *b) {
 // The blocked form of the pairs in `want` (kBlkFields), packed on the download stream itself, in front of its copies:
 // the batch's stream is idle (finish()) and stays free.  The device arrays follow tok_cap like d_r16.
 int pack_blocked(dtk_batch *b, uint32_t want, uint64_t n_tokens) {
-  if (!b->d_blk_flag) {
-    HIP_TRY(hipMalloc((void **)&b->d_blk_flag, 2 * sizeof(uint32_t)));
-    HIP_TRY(hipHostMalloc((void **)&b->h_blk_flag, 2 * sizeof(uint32_t), hipHostMallocDefault));
-    b->h_blk_flag[0] = b->h_blk_flag[1] = 0;
+  if (!b->h_blk_flag.p) {
+    int rc;
+    if ((rc = b->d_blk_flag.fit(2, 2)) || (rc = b->h_blk_flag.fit(2 * sizeof(uint32_t), 2 * sizeof(uint32_t)))) return rc;
+    memset(b->h_blk_flag.p, 0, 2 * sizeof(uint32_t));
   }
-  const int32_t *src[2][2] = {{b->d_rstart, b->d_rend}, {(const int32_t *)b->d_bstart, (const int32_t *)b->d_bend}};
+  const int32_t *src[2][2] = {{b->d_rstart, b->d_rend}, {(const int32_t *)b->d_bstart.p, (const int32_t *)b->d_bend.p}};
   DtkPackBlkArgs a{};
   for (int k = 0; k < 2; k++) {
     if (!(want & kBlkField[k])) continue;
     dtk_batch::BlkPair &p = b->blk[k];
     if (p.cap < b->tok_cap || !p.d_words) {
-      if (p.d_words) HIP_TRY(hipFree(p.d_words));
-      if (p.d_heads) HIP_TRY(hipFree(p.d_heads));
-      p.d_words = nullptr; p.d_heads = nullptr; p.cap = 0;
       const uint64_t cap = std::max<uint64_t>(b->tok_cap, 64);
-      HIP_TRY(hipMalloc((void **)&p.d_words, cap * 4));
-      HIP_TRY(hipMalloc(&p.d_heads, blocks_of(cap) * sizeof(dtk_off_block)));
+      int rc;
+      p.cap = 0;
+      if ((rc = p.d_words.fit(cap, cap)) || (rc = p.d_heads.fit(blocks_of(cap), blocks_of(cap)))) return rc;
       p.cap = cap;
     }
     if (n_tokens > p.cap) return DTK_E_CAPACITY;  // (finish() has grown tok_cap to the run's tokens: never expected)
@@ -101,7 +101,7 @@ extern "C" int dtk_batch_result_device(dtk_batch *b, dtk_result_view *o) {
   set_outputs(b, *o);
   o->status = b->d_status; o->ev_bits = b->d_bits; o->ev_words = b->bit_words; o->doc_tail = b->d_doc_tail;
   o->n_exact = (uint32_t)b->h_exact_ids.size();
-  o->exact_doc = b->d_exact_ids; o->exact_off = b->d_exact_off; o->calls = (const dtk_call *)b->d_calls;
+  o->exact_doc = b->d_exact_ids; o->exact_off = b->d_exact_off; o->calls = (const dtk_call *)b->d_calls.p;
   return DTK_OK;
 }
 
@@ -120,8 +120,8 @@ int launch_to_host(dtk_batch *b) {
   DtkToHostArgs a{};
   for (const HostArray &r : host_arrays(b)) {
     if (!(f & r.field)) continue;
-    dtk_batch::PinBuf &pb = b->pin[r.slot];
-    int rc = pin_fit(pb, (size_t)(r.count >= 0 ? r.cap * r.size : r.size));
+    PinBuf &pb = b->pin[r.slot];
+    int rc = pb.fit((size_t)(r.count >= 0 ? r.cap * r.size : r.size));
     if (rc != DTK_OK) return rc;
     void *dp = nullptr;
     HIP_TRY(hipHostGetDevicePointer(&dp, pb.p, 0));
@@ -130,9 +130,9 @@ int launch_to_host(dtk_batch *b) {
     a.n++;
   }
   if (a.n == 0) return DTK_OK;
-  a.totals = b->d_totals;
+  a.totals = &b->d_totals->n_tok;
   a.skip_if = b->last_args.skip_if;
-  a.done = b->d_totals + 11;
+  a.done = &b->d_totals->to_host_epoch;
   a.epoch = b->epoch;
   if (dtk_launch_to_host(&a, b->stream)) return hip_fail(hipGetLastError(), "results to the host");
   b->eager_fields = f;
@@ -144,18 +144,12 @@ int launch_to_host(dtk_batch *b) {
 extern "C" int dtk_batch_set_download_stream(dtk_batch *b, void *stream) {
   if (!b) return DTK_E_ARG;
   if (b->dl_begun && !b->dl_waited) { HIP_TRY(hipEventSynchronize(b->ev_dl)); b->dl_waited = true; }
-  if (b->dl_stream && b->dl_own) HIP_TRY(hipStreamDestroy(b->dl_stream));
-  b->dl_stream = (hipStream_t)stream;
-  b->dl_own = false;
-  return DTK_OK;
+  return b->dl_stream.lend((hipStream_t)stream);
 }
 
 extern "C" void *dtk_batch_download_stream(dtk_batch *b) {
   if (!b) return nullptr;
-  if (!b->dl_stream) {
-    if (hipStreamCreateWithFlags(&b->dl_stream, hipStreamNonBlocking) != hipSuccess) { b->dl_stream = nullptr; return nullptr; }
-    b->dl_own = true;
-  }
+  if (!b->dl_stream && b->dl_stream.create() != DTK_OK) return nullptr;
   return (void *)b->dl_stream;
 }
 
@@ -194,24 +188,19 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
     if (r.field == DTK_R_TOK_RUNE16) {
       if (!bytes) continue;
       // packed on the download stream itself, in front of its copy: the batch's stream is idle (finish()) and stays free
-      if (b->r16_cap < b->tok_cap) {
-        if (b->d_r16) HIP_TRY(hipFree(b->d_r16));
-        b->d_r16 = nullptr; b->r16_cap = 0;
-        HIP_TRY(hipMalloc((void **)&b->d_r16, std::max<uint64_t>(b->tok_cap, 4) * 4));
-        b->r16_cap = b->tok_cap;
-      }
+      if ((rc = b->d_r16.fit(b->tok_cap, std::max<uint64_t>(b->tok_cap, 4))) != DTK_OK) return rc;
       if (dtk_launch_pack_r16(b->d_rstart, b->d_rend, b->d_r16, tot[0], b->dl_stream)) return hip_fail(hipGetLastError(), "pack r16");
       src = b->d_r16;
     }
-    rc = pin_fit(b->pin[r.slot], (size_t)bytes);
+    rc = b->pin[r.slot].fit((size_t)bytes);
     if (rc != DTK_OK) return rc;
     if (bytes) HIP_TRY(hipMemcpyAsync(b->pin[r.slot].p, src, (size_t)bytes, hipMemcpyDeviceToHost, b->dl_stream));
   }
   for (int k = 0; k < 2; k++)
     if (blk_want & kBlkField[k])
-      HIP_TRY(hipMemcpyAsync(b->h_blk_flag + k, b->d_blk_flag + k, sizeof(uint32_t), hipMemcpyDeviceToHost, b->dl_stream));
+      HIP_TRY(hipMemcpyAsync(b->h_blk_flag.as<uint32_t>() + k, b->d_blk_flag + k, sizeof(uint32_t), hipMemcpyDeviceToHost, b->dl_stream));
   b->blk_pending |= blk_want;
-  if (!b->ev_dl) HIP_TRY(hipEventCreateWithFlags(&b->ev_dl, hipEventDisableTiming));
+  if ((rc = b->ev_dl.ensure(hipEventDisableTiming)) != DTK_OK) return rc;
   HIP_TRY(hipEventRecord(b->ev_dl, b->dl_stream));
   b->dl_waited = false;
   b->dl_fields = (b->dl_begun ? b->dl_fields : 0u) | want;
@@ -229,7 +218,7 @@ extern "C" int dtk_batch_result_host(dtk_batch *b, dtk_result_view *o) {
     // stay NULL.  blk_failed holds for the rest of the run: a second call neither copies again nor flips forms.
     uint32_t failed = 0;
     for (int k = 0; k < 2; k++)
-      if ((b->blk_pending & kBlkField[k]) && b->h_blk_flag[k]) failed |= kBlkField[k];
+      if ((b->blk_pending & kBlkField[k]) && b->h_blk_flag.as<uint32_t>()[k]) failed |= kBlkField[k];
     b->blk_pending = 0;
     if (failed) {
       b->blk_failed |= failed;
@@ -265,12 +254,7 @@ static int render(dtk_batch *b, uint32_t bits) {
   const uint64_t nt = b->totals.n_tokens, ns = b->totals.n_sent, nx = b->totals.n_texts, nd = b->n_docs;
   const uint64_t tt = dtk_render_tiles(nt), st = dtk_render_tiles(ns);
   const uint64_t words = 2 * (nt + 1) + (ns + 1) + 2 * tt + st + (nd + 1) + 4 * (nx + 1) + 8;
-  if (words > b->rws_cap) {
-    if (b->d_rws) HIP_TRY(hipFree(b->d_rws));
-    b->d_rws = nullptr; b->rws_cap = 0;
-    HIP_TRY(hipMalloc((void **)&b->d_rws, (words + words / 8) * 8));
-    b->rws_cap = words + words / 8;
-  }
+  if ((rc = b->d_rws.fit(words, words + words / 8)) != DTK_OK) return rc;
   DtkRenderArgs R{};
   R.text = b->d_text; R.doc_off = b->d_off; R.n_docs = b->n_docs; R.flags = bits;
   R.tok_off = b->d_tok_off; R.sent_off = b->d_sent_off; R.text_off = b->d_text_off;
@@ -286,15 +270,10 @@ static int render(dtk_batch *b, uint32_t bits) {
   R.tx_base = q; q += nx + 1; R.tx_stream = q; q += nx + 1; R.tx_pos = q; q += nx + 1; R.tx_sent = q; q += nx + 1;
   R.out_off = b->d_out_off;
   if (dtk_launch_render(&R, 0, s)) return hip_fail(hipGetLastError(), "render sizes");
-  HIP_TRY(hipMemcpyAsync(b->h_totals + 10, R.tx_base + nx, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&b->h_totals->render_total, R.tx_base + nx, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  const uint64_t total = b->h_totals[10];
-  if (total > b->out_cap) {
-    if (b->d_out) HIP_TRY(hipFree(b->d_out));
-    b->d_out = nullptr; b->out_cap = 0;
-    HIP_TRY(hipMalloc((void **)&b->d_out, total + total / 8 + 256));
-    b->out_cap = total + total / 8 + 256;
-  }
+  const uint64_t total = b->h_totals->render_total;
+  if ((rc = b->d_out.fit(total, total + total / 8 + 256)) != DTK_OK) return rc;
   R.out = b->d_out; R.out_total = total;
   if (total) {
     HIP_TRY(hipMemsetAsync(b->d_out, '\n', total, s));  // every separator that is not a space

@@ -54,11 +54,14 @@ __global__ __launch_bounds__(SYM_THREADS) void k_symbolize(const uint8_t *__rest
                                                     unsigned long long epoch) {
   // The run's accumulator block (totals, per-document counts, status and check words; dtk_batch_run) starts from
   // zero: the first blocks clear it here instead of a launch of its own in front (7 us of a batch's 230).  All but
-  // totals[6], which blocks of this very launch write: the number of the last run that saw an invalid byte.
+  // DtkTotalsDev::invalid_epoch, which blocks of this very launch write: the number of the last run that saw an
+  // invalid byte.
   if (acc) {
     const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    constexpr uint32_t kept16 = offsetof(DtkTotalsDev, invalid_epoch) / 16u;   // the unit of the word that is kept
+    constexpr uint32_t flags8 = offsetof(DtkTotalsDev, any_irregular) / 8u;    // its other word: cleared
     for (uint32_t i = blockIdx.x * SYM_THREADS + threadIdx.x; i < acc16; i += gridDim.x * SYM_THREADS) {
-      if (i == 3u) reinterpret_cast<unsigned long long *>(acc)[7] = 0ull;  // totals[7]; totals[6] stays
+      if (i == kept16) reinterpret_cast<unsigned long long *>(acc)[flags8] = 0ull;  // any_irregular, any_eot; invalid_epoch stays
       else acc[i] = z;
     }
   }

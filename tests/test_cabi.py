@@ -105,3 +105,21 @@ def test_python_structs_mirror_the_header(tmp_path):
         assert int(got[cname]) == ctypes.sizeof(cls), cname
         for fname, _ in cls._fields_:
             assert int(got["%s.%s" % (cname, fname)]) == getattr(cls, fname).offset, (cname, fname)
+
+
+def test_hip_resources_are_released_by_the_owning_types_only():
+    """Device memory, page-locked memory, streams and events of the library are released in csrc/dtk_own.h (DevArray,
+    PinBuf, Stream, Event) and nowhere else: a buffer cannot be forgotten in a hand-written list.  The one exception
+    is dtk_pinned_free, which frees the caller's memory."""
+    csrc = os.path.join(ROOT, "datok_amd", "csrc")
+    found = {}
+    for f in sorted(os.listdir(csrc)):
+        txt = open(os.path.join(csrc, f), encoding="utf-8", errors="replace").read()
+        for call in ("hipFree(", "hipHostFree(", "hipStreamDestroy(", "hipEventDestroy("):
+            if txt.count(call):
+                found[(f, call)] = txt.count(call)
+    elsewhere = {k: v for k, v in found.items() if k[0] != "dtk_own.h"}
+    assert elsewhere == {("dtk_pipeline.cpp", "hipHostFree("): 1}, elsewhere
+    assert {c for f, c in found if f == "dtk_own.h"} == {"hipFree(", "hipHostFree(", "hipStreamDestroy(", "hipEventDestroy("}
+    pipeline = open(os.path.join(csrc, "dtk_pipeline.cpp"), encoding="utf-8").read()
+    assert re.search(r"void dtk_pinned_free\(void \*p\) \{\s*if \(p\) \(void\)hipHostFree\(p\);\s*\}", pipeline)

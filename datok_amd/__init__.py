@@ -19,6 +19,7 @@ HIP kernels behind the C-ABI of libdatok_gpu.so (include/datok_gpu.h):
     --                                   model_info(bytes): the device layout a model file gets, host only (addition)
     --                                   Batch: many documents per launch (addition)
     --                                   unpack_blocked: token offsets from their 16-bit blocks (addition)
+    --                                   replay_list: a closure replay from the event list, Batch.R_EVENT_LIST (addition)
     --                                   Pipeline: a corpus larger than a batch, uploads overlapped (addition)
     --                                   MultiPipeline: ... sharded over several GPUs of a node (addition)
 """
@@ -26,4 +27,4 @@ from ._lib import (DatokGpuError, ST_BAD_MODEL, ST_BAD_OFFSET, ST_EMPTY_TEXT, ST
                    ST_WINDOW_OVERFLOW, build, lib)
 from .host import (NEWLINE_AFTER_EOT, NO_BYTE_OFFSETS, NO_RUNE_OFFSETS, OFFSETS_ONLY, SENTENCE_POS, SENTENCES, SIMPLE, TOKEN_POS, TOKENS, Batch,  # noqa: F401
                    BatchResult, MultiPipeline, PinnedBuffer, Pipeline, TokenWriter, Tokenizer, foma_to_datok, foma_to_matok, load_foma_file,
-                   load_tokenizer_file, model_info, new_token_writer, replay, unpack_blocked)
+                   load_tokenizer_file, model_info, new_token_writer, replay, replay_list, unpack_blocked)

@@ -61,7 +61,8 @@ class ResultView(C.Structure):
                 ("n_exact", C.c_uint32), ("exact_doc", C.c_void_p), ("exact_off", C.c_void_p),
                 ("calls", C.c_void_p), ("tok_r16", C.c_void_p),
                 ("tok_rblk", C.c_void_p), ("tok_rblk_head", C.c_void_p),
-                ("tok_bblk", C.c_void_p), ("tok_bblk_head", C.c_void_p)]
+                ("tok_bblk", C.c_void_p), ("tok_bblk_head", C.c_void_p),
+                ("evl_off", C.c_void_p), ("evl_pos", C.c_void_p), ("evl_kind", C.c_void_p)]
 
 
 SLICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)

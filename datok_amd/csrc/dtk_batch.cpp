@@ -402,6 +402,7 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
   if (b->dl_begun && !b->dl_waited) { HIP_TRY(hipEventSynchronize(b->ev_dl)); b->dl_waited = true; }  // (the last run's results on their way out)
   b->dl_begun = false;
   b->blk_pending = b->blk_failed = 0;
+  b->evl_pending = false; b->evl_need = 0;
   if (b->up_pending) {  // the kernels wait for the input's upload on the other stream
     HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_up, 0));
     b->up_pending = false;

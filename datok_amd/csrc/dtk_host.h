@@ -36,6 +36,8 @@ struct DtkDebug {
   int debug_repair = 0;  // print the lane records of documents that stay broken
   int blk_span = -1;     // what a segment of a 64-token block may span in the blocked offsets (-1 or 0: 65 535); read where
                          // k_pack_blk is launched, so that ordinary text reaches the fallback to the 32-bit arrays
+  int evl_cap = -1;      // entries the copies of DTK_R_EVENT_LIST are first sized for, in place of n_sent + n_texts (-1: off),
+                         // so that ordinary text reaches the second download of a list that outgrew the bound
 };
 extern DtkDebug g_dbg;
 
@@ -171,7 +173,7 @@ struct dtk_batch {
   // asynchronous copies on a stream of their own (dl_stream) -- the batch's own stream is free for the next kernels,
   // the copy engine for the next slice's upload (PCIe is full duplex).  `fields` (DTK_R_*) selects what is copied.
   // (one buffer per row of host_arrays, dtk_results.cpp)
-  enum { PB_R16, PB_RBLK, PB_RBLK_HEAD, PB_BBLK, PB_BBLK_HEAD, PB_RSTART, PB_REND, PB_BSTART, PB_BEND, PB_BITS, PB_TAIL, PB_SENT, PB_TTOK, PB_TSENT, PB_CSR, PB_STATUS,
+  enum { PB_R16, PB_RBLK, PB_RBLK_HEAD, PB_BBLK, PB_BBLK_HEAD, PB_RSTART, PB_REND, PB_BSTART, PB_BEND, PB_BITS, PB_EVL_POS, PB_EVL_KIND, PB_EVL_OFF, PB_TAIL, PB_SENT, PB_TTOK, PB_TSENT, PB_CSR, PB_STATUS,
          PB_N };
   PinBuf pin[PB_N];
   PinBuf h_plan;            // staging of the lane plan's tables (plan_lanes)
@@ -185,6 +187,15 @@ struct dtk_batch {
   PinBuf h_blk_flag;               // [2]
   uint32_t blk_pending = 0;        // blocked fields on their way whose flag nobody has looked at yet
   uint32_t blk_failed = 0;         // blocked fields the last run's offsets do not fit: the 32-bit arrays stand in
+  // DTK_R_EVENT_LIST: the set bits of SEPS | TEOT | SEOT as rows, compacted on the download stream (dtk_evlist.hip).  The
+  // copies are sized for n_sent + n_texts rows; the count word travels behind them, and dtk_batch_result_host copies
+  // again (evl_need rows) if the list turned out longer.
+  DevArray<uint32_t> d_evl_pos, d_evl_bit, d_evl_off, d_evl_tiles, d_evl_cnt;  // (d_evl_bit: device only; d_evl_cnt: [1])
+  DevArray<uint8_t> d_evl_kind;
+  PinBuf h_evl_cnt;                // [1]
+  uint64_t evl_copied = 0;         // rows the last enqueued copies of the list hold
+  uint64_t evl_need = 0;           // nonzero: this run's list has that many rows, more than the bound (dtk_batch_result_host saw it)
+  bool evl_pending = false;        // a list is on its way whose count nobody has looked at yet
   uint64_t max_doc_bytes = 0;     // of the current input (what decides whether the narrow form exists)
   bool max_doc_valid = false;
   Stream dl_stream;                 // created with the first download, unless the caller lends one (a pipeline's slices share one:

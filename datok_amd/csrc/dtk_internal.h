@@ -352,9 +352,32 @@ struct DtkPackBlkArgs {
   uint64_t n;     // tokens
 };
 
+// DTK_R_EVENT_LIST (dtk_evlist.hip): the set bits of SEPS | TEOT | SEOT as rows {position, kinds} with a CSR over
+// documents (include/datok_gpu.h).  Global bits are below 2^32 (the walk's EventSink counts them in 32 bits too).
+#define DTK_EVL_K_SEOT 1u  // DTK_EVL_* of datok_gpu.h
+#define DTK_EVL_K_TEOT 2u
+#define DTK_EVL_K_SEPS 4u
+struct DtkEvListArgs {
+  const uint32_t *bits;     // event bitmaps of the walk (EVB_KINDS x bit_words words)
+  uint32_t bit_words;
+  uint32_t n_docs;
+  const uint64_t *doc_off;  // n_docs + 1, on the device
+  uint64_t n_bits;          // doc_off[n_docs] + n_docs: bits at or behind it belong to no document
+  uint32_t n_tiles;         // dtk_evlist_tiles(n_bits, bit_words)
+  uint32_t cap;             // rows evl_pos / evl_kind / evl_bit hold; a larger total writes no row
+  uint32_t *tile_base;      // n_tiles: counts, then their exclusive scan
+  uint32_t *count;          // device word: the total
+  uint32_t *evl_off;        // n_docs + 1
+  uint32_t *evl_pos;        // cap
+  uint8_t *evl_kind;        // cap
+  uint32_t *evl_bit;        // cap, device only: a row's global bit (what k_evl_rows searches)
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+uint32_t dtk_evlist_tiles(uint64_t n_bits, uint32_t bit_words);
+int dtk_launch_evlist(const struct DtkEvListArgs *args, void *stream);
 int dtk_launch_to_host(const struct DtkToHostArgs *args, void *stream);
 int dtk_launch_pack_r16(const int32_t *rs, const int32_t *re, uint32_t *out, uint64_t n, void *stream);
 int dtk_launch_pack_blk(const struct DtkPackBlkArgs *args, void *stream);

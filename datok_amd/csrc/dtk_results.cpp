@@ -11,7 +11,7 @@
 namespace {
 // An array that can go to the host: `count` >= 0: totals[count] elements of `size` bytes, in a device array of `cap`
 // elements -- 0 tokens, 1 sentence ints, 2 texts, 3 (kPerBlock) blocks of 64 tokens, i.e. one element per 64 tokens,
-// rounded up; < 0: `size` bytes.
+// rounded up, 4 (kPerEvent) rows of the event list the copies are sized for; < 0: `size` bytes.
 struct HostArray {
   uint32_t field;  // DTK_R_*
   int slot;        // dtk_batch::PB_*: its page-locked buffer
@@ -25,6 +25,9 @@ struct HostArray {
 // (Only the download stream's copies use kPerBlock: launch_to_host masks the fields with DTK_R_ALL, which holds no
 // blocked field, so the kind never reaches k_to_host -- where totals[3] would be DtkTotalsDev::n_flagged.)
 constexpr int kPerBlock = 3;
+constexpr int kPerEvent = 4;  // (DTK_R_EVENT_LIST is no part of DTK_R_ALL either)
+static_assert(DTK_EVL_SEOT == DTK_EVL_K_SEOT && DTK_EVL_TEOT == DTK_EVL_K_TEOT && DTK_EVL_SEPS == DTK_EVL_K_SEPS,
+              "the kernels' kind bits are the header's");
 constexpr uint32_t kBlkFields = DTK_R_TOK_RUNE_BLK | DTK_R_TOK_BYTE_BLK;
 constexpr uint32_t kBlkField[2] = {DTK_R_TOK_RUNE_BLK, DTK_R_TOK_BYTE_BLK};
 constexpr uint32_t kBlkWide[2] = {DTK_R_TOK_RUNE, DTK_R_TOK_BYTE};  // what stands in for a pair that does not fit
@@ -47,7 +50,10 @@ std::array<HostArray, dtk_batch::PB_N> host_arrays(const dtk_batch *b) {
       {DTK_R_TOK_BYTE, dtk_batch::PB_BSTART, b->d_bstart, 4, 0, b->tok_cap, VIEW(tok_bstart)},
       {DTK_R_TOK_BYTE, dtk_batch::PB_BEND, b->d_bend, 4, 0, b->tok_cap, VIEW(tok_bend)},
       {DTK_R_EVENTS, dtk_batch::PB_BITS, b->d_bits, (uint64_t)EVB_KINDS * b->bit_words * 4, -1, 0, VIEW(ev_bits)},
-      {DTK_R_EVENTS, dtk_batch::PB_TAIL, b->d_doc_tail, nd * 4, -1, 0, VIEW(doc_tail)},
+      {DTK_R_EVENT_LIST, dtk_batch::PB_EVL_POS, b->d_evl_pos, 4, kPerEvent, b->d_evl_pos.cap, VIEW(evl_pos)},
+      {DTK_R_EVENT_LIST, dtk_batch::PB_EVL_KIND, b->d_evl_kind, 1, kPerEvent, b->d_evl_kind.cap, VIEW(evl_kind)},
+      {DTK_R_EVENT_LIST, dtk_batch::PB_EVL_OFF, b->d_evl_off, (nd + 1) * 4, -1, 0, VIEW(evl_off)},
+      {DTK_R_EVENTS | DTK_R_EVENT_LIST, dtk_batch::PB_TAIL, b->d_doc_tail, nd * 4, -1, 0, VIEW(doc_tail)},  // (with either)
       {DTK_R_SENT, dtk_batch::PB_SENT, b->d_sent, 4, 1, b->sent_cap, VIEW(sent)},
       {DTK_R_TEXTS, dtk_batch::PB_TTOK, b->d_ttok, 4, 2, b->text_cap, VIEW(text_tok_end)},
       {DTK_R_TEXTS, dtk_batch::PB_TSENT, b->d_tsent, 4, 2, b->text_cap, VIEW(text_sent_end)},
@@ -90,6 +96,33 @@ int pack_blocked(dtk_batch *b, uint32_t want, uint64_t n_tokens) {
   if (dtk_launch_pack_blk(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "pack blocked offsets");
   return DTK_OK;
 }
+
+// DTK_R_EVENT_LIST: the list of the last run's bitmaps, compacted on the download stream in front of its copies like
+// the blocked offsets.  `rows`: what the device arrays must hold and the copies will bring -- the kernels write
+// nothing if the list is longer, and the count word, which goes home behind the arrays, says so.
+int pack_event_list(dtk_batch *b, uint64_t rows) {
+  const uint64_t n_bits = b->total + b->n_docs;
+  if (n_bits > 0xFFFFFFFFull || rows > 0xFFFFFFFFull) return DTK_E_CAPACITY;
+  int rc;
+  if (!b->h_evl_cnt.p) {
+    if ((rc = b->d_evl_cnt.fit(1, 1)) || (rc = b->h_evl_cnt.fit(sizeof(uint32_t), sizeof(uint32_t)))) return rc;
+    *b->h_evl_cnt.as<uint32_t>() = 0;
+  }
+  const uint64_t cap = std::max<uint64_t>(rows + rows / 8, 64);
+  const uint32_t tiles = dtk_evlist_tiles(n_bits, b->bit_words);
+  if ((rc = b->d_evl_pos.fit(rows, cap)) || (rc = b->d_evl_kind.fit(rows, cap)) || (rc = b->d_evl_bit.fit(rows, cap)) ||
+      (rc = b->d_evl_off.fit((uint64_t)b->n_docs + 1, std::max<uint64_t>((uint64_t)b->max_docs, b->n_docs) + 1)) ||
+      (rc = b->d_evl_tiles.fit(tiles, std::max<uint64_t>(tiles + tiles / 8, 16))))
+    return rc;
+  DtkEvListArgs a{};
+  a.bits = b->d_bits; a.bit_words = b->bit_words; a.n_docs = b->n_docs; a.doc_off = b->d_off; a.n_bits = n_bits;
+  a.n_tiles = tiles; a.cap = (uint32_t)rows;
+  a.tile_base = b->d_evl_tiles; a.count = b->d_evl_cnt; a.evl_off = b->d_evl_off;
+  a.evl_pos = b->d_evl_pos; a.evl_kind = b->d_evl_kind; a.evl_bit = b->d_evl_bit;
+  if (dtk_launch_evlist(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "pack event list");
+  b->evl_copied = rows;
+  return DTK_OK;
+}
 }  // namespace
 
 extern "C" int dtk_batch_result_device(dtk_batch *b, dtk_result_view *o) {
@@ -98,6 +131,7 @@ extern "C" int dtk_batch_result_device(dtk_batch *b, dtk_result_view *o) {
   if (rc != DTK_OK) return rc;
   o->tok_r16 = nullptr;  // (host results only)
   o->tok_rblk = o->tok_bblk = nullptr; o->tok_rblk_head = o->tok_bblk_head = nullptr;
+  o->evl_off = o->evl_pos = nullptr; o->evl_kind = nullptr;
   set_outputs(b, *o);
   o->status = b->d_status; o->ev_bits = b->d_bits; o->ev_words = b->bit_words; o->doc_tail = b->d_doc_tail;
   o->n_exact = (uint32_t)b->h_exact_ids.size();
@@ -106,7 +140,7 @@ extern "C" int dtk_batch_result_device(dtk_batch *b, dtk_result_view *o) {
 }
 
 extern "C" int dtk_batch_set_result_fields(dtk_batch *b, uint32_t fields) {
-  if (!b || (fields & ~(uint32_t)(DTK_R_ALL | DTK_R_TOK_RUNE16 | DTK_R_EAGER | kBlkFields))) return DTK_E_ARG;
+  if (!b || (fields & ~(uint32_t)(DTK_R_ALL | DTK_R_TOK_RUNE16 | DTK_R_EAGER | kBlkFields | DTK_R_EVENT_LIST))) return DTK_E_ARG;
   b->fields = fields;
   return DTK_OK;
 }
@@ -157,7 +191,7 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
   if (!b) return DTK_E_ARG;
   int rc = finish(b);
   if (rc != DTK_OK) return rc;
-  uint32_t sel = b->fields & (DTK_R_ALL | DTK_R_TOK_RUNE16 | kBlkFields);
+  uint32_t sel = b->fields & (DTK_R_ALL | DTK_R_TOK_RUNE16 | kBlkFields | DTK_R_EVENT_LIST);
   if (sel & DTK_R_TOK_RUNE16) {
     // the narrow form holds every offset of a document of at most 32 767 bytes; a batch with a longer one gets the
     // 32-bit arrays in its place
@@ -178,7 +212,14 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
   if (b->dl_begun && (b->dl_fields & sel) == sel) return DTK_OK;
   const uint32_t want = sel & ~(b->dl_begun ? b->dl_fields : 0u);
   if (!dtk_batch_download_stream(b)) return hip_fail(hipGetLastError(), "download stream");
-  const uint64_t tot[4] = {b->totals.n_tokens, b->totals.n_sent, b->totals.n_texts, blocks_of(b->totals.n_tokens)};
+  uint64_t tot[5] = {b->totals.n_tokens, b->totals.n_sent, b->totals.n_texts, blocks_of(b->totals.n_tokens), 0};
+  if (want & DTK_R_EVENT_LIST) {
+    // Every SentenceEnd call appends one int (token_writer.go:108) and every TEOT is a TextEnd call: n_sent + n_texts
+    // bounds the rows of regular documents, and the count word backs the bound up (dtk_batch_result_host)
+    tot[kPerEvent] = g_dbg.evl_cap >= 0 ? (uint64_t)g_dbg.evl_cap : tot[1] + tot[2];
+    tot[kPerEvent] = std::max(tot[kPerEvent], b->evl_need);
+    if ((rc = pack_event_list(b, tot[kPerEvent])) != DTK_OK) return rc;
+  }
   const uint32_t blk_want = tot[0] ? want & kBlkFields : 0u;  // (no token: nothing to pack, empty arrays)
   if (blk_want && (rc = pack_blocked(b, blk_want, tot[0])) != DTK_OK) return rc;
   for (const HostArray &r : host_arrays(b)) {
@@ -200,6 +241,10 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
     if (blk_want & kBlkField[k])
       HIP_TRY(hipMemcpyAsync(b->h_blk_flag.as<uint32_t>() + k, b->d_blk_flag + k, sizeof(uint32_t), hipMemcpyDeviceToHost, b->dl_stream));
   b->blk_pending |= blk_want;
+  if (want & DTK_R_EVENT_LIST) {
+    HIP_TRY(hipMemcpyAsync(b->h_evl_cnt.p, b->d_evl_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, b->dl_stream));
+    b->evl_pending = true;
+  }
   if ((rc = b->ev_dl.ensure(hipEventDisableTiming)) != DTK_OK) return rc;
   HIP_TRY(hipEventRecord(b->ev_dl, b->dl_stream));
   b->dl_waited = false;
@@ -225,6 +270,19 @@ extern "C" int dtk_batch_result_host(dtk_batch *b, dtk_result_view *o) {
       b->dl_fields &= ~failed;
       if ((rc = dtk_batch_download_begin(b)) != DTK_OK) return rc;
       if (!b->dl_waited) { HIP_TRY(hipEventSynchronize(b->ev_dl)); b->dl_waited = true; }
+    }
+  }
+  if (b->evl_pending) {
+    // An event list longer than its copies were sized for (not expected of regular documents): the arrays grow to
+    // the count, the list is packed and copied again.  evl_need holds for the rest of the run.
+    b->evl_pending = false;
+    const uint64_t n = *b->h_evl_cnt.as<uint32_t>();
+    if (n > b->evl_copied) {
+      b->evl_need = n;
+      b->dl_fields &= ~(uint32_t)DTK_R_EVENT_LIST;
+      if ((rc = dtk_batch_download_begin(b)) != DTK_OK) return rc;
+      if (!b->dl_waited) { HIP_TRY(hipEventSynchronize(b->ev_dl)); b->dl_waited = true; }
+      b->evl_pending = false;
     }
   }
   memset(o, 0, sizeof(*o));

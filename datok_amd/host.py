@@ -17,6 +17,8 @@ OFFSETS_ONLY, NO_BYTE_OFFSETS, NO_RUNE_OFFSETS = 256, 512, 1024
 # calls at one cursor position, in the order they fire (flag byte of event_bytes(); datok_gpu.h DTK_EVB_* / DTK_TAIL_*)
 EV_S_EOT, EV_E_EOT, EV_TOK_END, EV_S_EPS, EV_S_EOF, EV_E_EOF = 1, 2, 4, 8, 32, 64
 EVB_END, EVB_START, EVB_SEPS, EVB_TEOT, EVB_SEOT = 0, 1, 2, 3, 4
+# bits of an event list entry's kind (datok_gpu.h DTK_EVL_*), in the order the calls fire around a Token at one cursor
+EVL_SEOT, EVL_TEOT, EVL_SEPS = 1, 2, 4
 
 
 # ------------------------------------------------------------------ UTF-8 (Go)
@@ -182,6 +184,45 @@ def replay(is_matrix, text: bytes, events, tok_bstart, tw: TokenWriter):
             tw.TextEnd(buffc() if is_matrix else 0)
 
 
+def replay_list(is_matrix, text: bytes, evl_pos, evl_kind, tail, tok_bstart, tok_bend, tw: TokenWriter):
+    """The same from one document's event list (Batch.R_EVENT_LIST: evl_pos / evl_kind, datok_gpu.h) instead of its
+    event bytes: the tokens (cursor tok_bend[k], first byte tok_bstart[k]) and the entries are merged by position; at
+    one cursor SEOT, TEOT, the Token ending there, SEPS; the tail word's SentenceEnd / TextEnd come last.  O(tokens +
+    entries).  The int arguments are replay()'s."""
+    n = len(text)
+    B = k = j = 0
+    nt, ne = len(tok_bend), len(evl_pos)
+    while k < nt or j < ne:
+        pt = int(tok_bend[k]) if k < nt else n + 1
+        pe = int(evl_pos[j]) if j < ne else n + 1
+        p = min(pt, pe)
+        e = 0
+        if pe == p:
+            e = int(evl_kind[j])
+            j += 1
+        def buffc():
+            return len(_decode_runes(text[B:p]))
+        if e & EVL_SEOT:
+            tw.SentenceEnd(buffc())
+        if e & EVL_TEOT:
+            tw.TextEnd(buffc() if is_matrix else 0)
+            if is_matrix:
+                B = p
+        if pt == p:
+            start = int(tok_bstart[k])
+            k += 1
+            tw.Token(len(_decode_runes(text[B:start])), _decode_runes(text[B:p]))
+            B = p
+        if e & EVL_SEPS:
+            tw.SentenceEnd(buffc() if is_matrix else 0)
+    tail = int(tail)
+    p = min(tail >> 2, n)
+    if tail & 1:
+        tw.SentenceEnd(len(_decode_runes(text[B:p])) if is_matrix else 0)
+    if tail & 2:
+        tw.TextEnd(len(_decode_runes(text[B:p])) if is_matrix else 0)
+
+
 def replay_calls(text: bytes, calls, tw: TokenWriter):
     """Feeds the call list of a document walked by the exact pass (dtk_result_view.calls: rows of
     (kind, a, b, c)) to the closures: kind 0 Token(offset, buf) with buf = runes of text[a:c] and offset =
@@ -309,7 +350,7 @@ class BatchResult:
     """Host copy of dtk_result_view (CSR over documents)."""
     __slots__ = ("tok_off", "sent_off", "text_off", "tok_rstart", "tok_rend", "tok_bstart",
                  "tok_bend", "sent", "text_tok_end", "text_sent_end", "status", "ev_bits", "doc_tail", "doc_off", "exact",
-                 "tok_r16", "tok_rblk", "tok_rblk_head", "tok_bblk", "tok_bblk_head")
+                 "tok_r16", "tok_rblk", "tok_rblk_head", "tok_bblk", "tok_bblk_head", "evl_off", "evl_pos", "evl_kind")
 
     def events(self, d):
         """Flag byte per cursor position of document d (event_bytes()), for replays."""
@@ -329,8 +370,9 @@ class BatchResult:
         bs, be = self.tok_bstart[a:b], self.tok_bend[a:b]
         if len(self.tok_bblk) and not len(self.tok_bstart):    # (R_TOK_BYTE_BLK)
             bs, be = (x.astype(np.uint32) for x in unpack_blocked(self.tok_bblk, self.tok_bblk_head, a, b))
+        e0, e1 = (int(self.evl_off[d]), int(self.evl_off[d + 1])) if len(self.evl_off) else (0, 0)   # (R_EVENT_LIST)
         return dict(tok_rstart=rs, tok_rend=re,
-                    tok_bstart=bs, tok_bend=be,
+                    tok_bstart=bs, tok_bend=be, evl_pos=self.evl_pos[e0:e1], evl_kind=self.evl_kind[e0:e1],
                     sent=self.sent[s0:s1], text_tok_end=self.text_tok_end[t0:t1],
                     text_sent_end=self.text_sent_end[t0:t1], status=int(self.status[d]))
 
@@ -441,6 +483,8 @@ class Batch:
     R_TOK_RUNE_BLK = 512   # the rune / byte offsets as blocks of 64 tokens with 16-bit offsets (BatchResult.tok_rblk +
     R_TOK_BYTE_BLK = 1024  # tok_rblk_head / tok_bblk + tok_bblk_head, unpack_blocked): any document length; a batch with
                            # a block that does not fit gets the 32-bit arrays in their place
+    R_EVENT_LIST = 2048    # what a closure replay needs of the event bitmaps as a list (BatchResult.evl_off / evl_pos /
+                           # evl_kind, replay_list) + doc_tail: about one 5-byte entry per sentence
 
     def set_result_fields(self, fields=R_ALL):
         """Which arrays result() brings to the host (the others come back empty)."""
@@ -484,6 +528,10 @@ class Batch:
         r.tok_rblk_head = arr(v.tok_rblk_head, 4 * n_blk, np.int32).reshape(-1, 4)
         r.tok_bblk = arr(v.tok_bblk, t["n_tokens"], np.uint32)
         r.tok_bblk_head = arr(v.tok_bblk_head, 4 * n_blk, np.int32).reshape(-1, 4)
+        r.evl_off = arr(v.evl_off, nd + 1, np.uint32)
+        n_evl = int(r.evl_off[-1]) if len(r.evl_off) else 0
+        r.evl_pos = arr(v.evl_pos, n_evl, np.uint32)
+        r.evl_kind = arr(v.evl_kind, n_evl, np.uint8)
         r.doc_off = self._doc_off
         r.exact = _exact_calls(v, arr)   # documents walked by the exact pass: id -> calls in order
         return r

@@ -150,6 +150,56 @@ inline void replay(bool is_matrix, const uint8_t *text, size_t n, const dtk_resu
   if (tail & DTK_TAIL_E) w.TextEnd(is_matrix ? buffc(pt) : 0);
 }
 
+// The same from the event list of document d (DTK_R_EVENT_LIST: evl_off / evl_pos / evl_kind) instead of the bitmaps:
+// the document's tokens and its entries are merged by cursor position -- O(tokens + entries), where replay() tests
+// four bits at every byte.  A token's cursor is tok_bend[k] and its first byte tok_bstart[k]; where only the blocked
+// byte offsets were delivered (DTK_R_TOK_BYTE_BLK) both come from dtk_blk_end / dtk_blk_start.  Order and int
+// arguments as above.
+inline void replay_list(bool is_matrix, const uint8_t *text, size_t n, const dtk_result_view &v, uint32_t d,
+                        TokenWriter &w) {
+  const uint64_t t0 = v.tok_off[d], t1 = v.tok_off[d + 1];
+  const bool blocked = !v.tok_bend && v.tok_bblk;
+  auto tok_end = [&](uint64_t i) { return blocked ? (size_t)dtk_blk_end(v.tok_bblk, v.tok_bblk_head, i) : (size_t)v.tok_bend[i]; };
+  auto tok_start = [&](uint64_t i) { return blocked ? (size_t)dtk_blk_start(v.tok_bblk, v.tok_bblk_head, i) : (size_t)v.tok_bstart[i]; };
+  uint64_t k = t0;                               // next token
+  uint32_t j = v.evl_off[d];                     // next entry
+  const uint32_t j1 = v.evl_off[d + 1];
+  size_t B = 0;                                  // byte position of the window start (last rewind)
+  std::vector<rune> buf;
+  auto buffc = [&](size_t p) { return count_runes(text + B, p - B); };
+  while (k < t1 || j < j1) {
+    const size_t none = n + 1;
+    const size_t pt = k < t1 ? tok_end(k) : none, pe = j < j1 ? (size_t)v.evl_pos[j] : none;
+    const size_t p = pt < pe ? pt : pe;
+    const uint32_t e = pe == p ? v.evl_kind[j++] : 0u;
+    if (e & DTK_EVL_SEOT) w.SentenceEnd(buffc(p));
+    if (e & DTK_EVL_TEOT) {
+      w.TextEnd(is_matrix ? buffc(p) : 0);
+      if (is_matrix) B = p;  // matrix.go:601 rewinds, datok.go:1019-1030 does not
+    }
+    if (pt == p) {
+      const size_t start = tok_start(k++);
+      buf.clear();
+      int offset = 0;
+      size_t i = B;
+      while (i < p) {
+        rune r;
+        int wd = decode_rune(text + i, n - i, &r);
+        if (i < start) offset++;
+        buf.push_back(r);
+        i += (size_t)wd;
+      }
+      w.Token(offset, buf);
+      B = p;
+    }
+    if (e & DTK_EVL_SEPS) w.SentenceEnd(is_matrix ? buffc(p) : 0);
+  }
+  const uint32_t tail = v.doc_tail[d];
+  const size_t pt = tail >> 2;
+  if (tail & DTK_TAIL_S) w.SentenceEnd(is_matrix ? buffc(pt) : 0);
+  if (tail & DTK_TAIL_E) w.TextEnd(is_matrix ? buffc(pt) : 0);
+}
+
 // The same for a document walked by the exact pass (dtk_result_view.calls): the calls are listed in
 // the reference's order with their arguments.
 inline void replay_calls(const uint8_t *text, size_t n, const dtk_call *calls, size_t n_calls, TokenWriter &w) {

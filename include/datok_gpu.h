@@ -293,6 +293,23 @@ typedef struct {
   const dtk_off_block *tok_rblk_head;
   const uint32_t *tok_bblk;
   const dtk_off_block *tok_bblk_head;
+  /* DTK_R_EVENT_LIST (host results only; NULL when not delivered): the sparse events of a closure replay as a list
+   * instead of bitmaps.  A pure function of the bitmaps above: document d has one entry for every cursor p in
+   * 0..len(d) at which bit DTK_EVENT_BIT(doc_off[d], d) + p is set in any of DTK_EVB_SEPS, DTK_EVB_TEOT,
+   * DTK_EVB_SEOT; evl_kind says in which of them (DTK_EVL_* below).  END and START are not listed: the k-th END bit
+   * of a document is at cursor tok_bend[k], and its START bit at tok_bstart[k].
+   *   evl_off   n_docs + 1: the entries of document d are [evl_off[d], evl_off[d + 1])
+   *   evl_pos   cursor position, document relative, 0..len, strictly ascending within a document
+   *   evl_kind  DTK_EVL_* bits, never 0
+   * The replay of document d merges its tokens (cursor tok_bend[k], first byte tok_bstart[k], or dtk_blk_end /
+   * dtk_blk_start on the blocked byte offsets) with its entries by position; at one cursor the calls fire in the
+   * order SEOT, TEOT, the Token ending there, SEPS.  doc_tail[d] comes last, as with the bitmaps.  The int arguments
+   * are those of the bitmap replay: the rune count since the window start, which a Token and (matrix only) a TEOT
+   * move to their cursor (include/datok.hpp, detail::replay_list).  Documents listed in exact_doc are replayed from
+   * `calls`; their entries follow the same definition and are not used. */
+  const uint32_t *evl_off;
+  const uint32_t *evl_pos;
+  const uint8_t *evl_kind;
 } dtk_result_view;
 int dtk_batch_result_device(dtk_batch *b, dtk_result_view *out);
 /* status words of the first n documents, copied to the caller's array */
@@ -314,7 +331,7 @@ enum {
   DTK_R_SENT = 8,      /* sent */
   DTK_R_TEXTS = 16,    /* text_tok_end, text_sent_end */
   DTK_R_STATUS = 32,   /* status */
-  DTK_R_EVENTS = 64,   /* ev_bits, doc_tail */
+  DTK_R_EVENTS = 64,   /* ev_bits, doc_tail (doc_tail also comes with DTK_R_EVENT_LIST) */
   DTK_R_ALL = 127,
   /* tok_r16: the rune offsets of a token as the two halves of one 32-bit word -- start in the low half, end in the
    * high half, both int16 -- half the bytes of tok_rstart / tok_rend on the link (the download is the longer leg of a
@@ -334,8 +351,18 @@ enum {
    * which pointer it got, as with tok_r16).  DTK_R_TOK_RUNE16 | DTK_R_TOK_RUNE_BLK asks for the narrowest form that
    * applies: tok_r16 for a batch of documents of up to 32 767 bytes, the blocked form for any other. */
   DTK_R_TOK_RUNE_BLK = 512,
-  DTK_R_TOK_BYTE_BLK = 1024
+  DTK_R_TOK_BYTE_BLK = 1024,
+  /* evl_off + evl_pos + evl_kind + doc_tail: what a closure replay needs of the event bitmaps beside the token
+   * offsets, as a list (dtk_result_view above) -- about one 5-byte entry per sentence where the bitmaps cost five
+   * bits per input byte.  Compacted from the bitmaps on the download stream in front of its copies.  Host results
+   * only, not part of DTK_R_ALL nor of the eager copy; works with every run flag, and may be selected together with
+   * DTK_R_EVENTS.  A closure replay then needs DTK_R_EVENT_LIST | DTK_R_TOK_BYTE (or DTK_R_TOK_BYTE_BLK) | DTK_R_CSR |
+   * DTK_R_STATUS.  The copies are enqueued for n_sent + n_texts entries, which bounds the count for regular documents;
+   * dtk_batch_result_host looks at the true count behind the download and copies again if that was too few. */
+  DTK_R_EVENT_LIST = 2048
 };
+/* bits of evl_kind; at one cursor the calls fire in the order SEOT, TEOT, the Token ending there, SEPS */
+enum { DTK_EVL_SEOT = 1, DTK_EVL_TEOT = 2, DTK_EVL_SEPS = 4 };
 int dtk_batch_set_result_fields(dtk_batch *b, uint32_t fields);
 int dtk_batch_download_begin(dtk_batch *b);
 /* The HIP stream the result copies run on: the batch creates one with its first download; a caller with several

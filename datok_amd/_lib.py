@@ -30,7 +30,7 @@ EXPORTS = [
     "dtk_pinned_alloc", "dtk_pinned_free",
     "dtk_batch_set_result_fields", "dtk_batch_download_begin", "dtk_pipeline_set_result_fields",
     "dtk_batch_set_download_stream", "dtk_batch_download_stream", "dtk_batch_done", "dtk_batch_set_streams",
-    "dtk_debug_configure", "dtk_blk_start", "dtk_blk_end",
+    "dtk_debug_configure", "dtk_batch_debug_stream", "dtk_blk_start", "dtk_blk_end",
     "dtk_multi_create", "dtk_multi_free", "dtk_multi_type", "dtk_multi_set_result_fields", "dtk_multi_set_chunking", "dtk_multi_run",
 ]
 
@@ -180,6 +180,7 @@ def lib():
     # Test hooks: the library itself never reads the environment; this harness forwards the DATOK_* switches the tests
     # and scripts set (dtk_debug_configure; unknown names are not the library's and are left alone).
     L.dtk_debug_configure.argtypes = [C.c_char_p, C.c_char_p]
+    L.dtk_batch_debug_stream.argtypes = [vp, vp, vp, C.POINTER(u32)]
     for k, v in os.environ.items():
         if k.startswith("DATOK_") and k not in ("DATOK_GPU_LIB", "DATOK_GATHER_TIMEOUT"):
             L.dtk_debug_configure(k.encode(), v.encode())

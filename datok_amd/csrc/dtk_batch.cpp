@@ -138,18 +138,19 @@ extern "C" int dtk_batch_set_input_device(dtk_batch *b, const void *d_text, cons
                                           uint32_t n_docs, uint64_t total_bytes) {
   if (!b || !d_doc_off || n_docs == 0 || (total_bytes && !d_text)) return DTK_E_ARG;
   if (n_docs > b->max_docs || total_bytes > b->max_bytes || total_bytes + n_docs + 64 >= (1ull << 32)) return DTK_E_CAPACITY;
+  // lane planning needs the offsets on the host: one copy per input, not per run.  They are checked in a copy of
+  // their own: a rejected call leaves the batch's input, its plan and its host offsets as they were.
+  std::vector<uint64_t> off((size_t)n_docs + 1);
+  HIP_TRY(hipMemcpy(off.data(), d_doc_off, ((size_t)n_docs + 1) * 8, hipMemcpyDeviceToHost));
+  if (off[0] != 0 || off[n_docs] != total_bytes) return DTK_E_ARG;
+  for (uint32_t d = 0; d < n_docs; d++)
+    if (off[d + 1] < off[d] || off[d + 1] - off[d] >= 0x7FFFFFF0ull) return DTK_E_ARG;
   b->d_text = (const uint8_t *)d_text;
   b->d_off = (const uint64_t *)d_doc_off;
   b->n_docs = n_docs;
   b->total = total_bytes;
   b->ran = false;
-  // lane planning needs the offsets on the host: one copy per input, not per run
-  b->h_doc_off.resize((size_t)n_docs + 1);
-  HIP_TRY(hipMemcpy(b->h_doc_off.data(), d_doc_off, ((size_t)n_docs + 1) * 8, hipMemcpyDeviceToHost));
-  if (b->h_doc_off[0] != 0 || b->h_doc_off[n_docs] != total_bytes) return DTK_E_ARG;
-  for (uint32_t d = 0; d < n_docs; d++)
-    if (b->h_doc_off[d + 1] < b->h_doc_off[d] || b->h_doc_off[d + 1] - b->h_doc_off[d] >= 0x7FFFFFF0ull)
-      return DTK_E_ARG;
+  b->h_doc_off.swap(off);
   b->plan_valid = false;
   b->max_doc_valid = false;
   return DTK_OK;
@@ -743,5 +744,40 @@ extern "C" int dtk_batch_status_host(dtk_batch *b, uint32_t *status, uint32_t n)
   int rc = finish(b);
   if (rc != DTK_OK) return rc;
   if (n) HIP_TRY(hipMemcpy(status, b->d_status, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return DTK_OK;
+}
+
+// Test accessor (datok_gpu.h): what k_symbolize wrote in the batch's last run, read-only and in the terms of the model
+// file -- codes go through the model's code table, the device's column index back through dtk_model::col.
+extern "C" int dtk_batch_debug_stream(dtk_batch *b, uint16_t *entries, uint32_t *rune_start_words, uint32_t *saw_invalid) {
+  if (!b || !b->ran || !b->last_model) return DTK_E_ARG;
+  { const int rc = wait_own(b); if (rc != DTK_OK) return rc; }
+  const dtk_model *m = b->last_model;
+  const size_t n = (size_t)b->total;
+  if (entries && n) {
+    if (m->sig.n_codes) {
+      std::vector<uint8_t> codes(n);
+      uint16_t table[256];
+      HIP_TRY(hipMemcpy(codes.data(), b->d_sym.p, n, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(table, m->sig.code_entry, sizeof table, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < n; i++) entries[i] = table[codes[i]];
+    } else {
+      HIP_TRY(hipMemcpy(entries, b->d_sym.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    }
+    // column -> symbol of the file (the columns are a permutation of the symbols, layout_matrix; none: the symbol itself)
+    std::vector<uint16_t> sym_of_col(DTK_SYM_MASK + 1u);
+    for (uint32_t c = 0; c <= DTK_SYM_MASK; c++) sym_of_col[c] = (uint16_t)c;
+    for (size_t a = 0; a < m->col.size(); a++)
+      if (m->col[a] <= DTK_SYM_MASK) sym_of_col[m->col[a]] = (uint16_t)a;
+    for (size_t i = 0; i < n; i++)
+      entries[i] = (uint16_t)((entries[i] & ~DTK_SYM_MASK) | sym_of_col[entries[i] & DTK_SYM_MASK]);
+  }
+  if (rune_start_words && n)
+    HIP_TRY(hipMemcpy(rune_start_words, b->d_rsbits.p, (n + 31) / 32 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (saw_invalid) {
+    uint64_t seen = 0;
+    HIP_TRY(hipMemcpy(&seen, &b->d_totals->invalid_epoch, sizeof seen, hipMemcpyDeviceToHost));
+    *saw_invalid = (n && seen == b->epoch) ? 1u : 0u;
+  }
   return DTK_OK;
 }

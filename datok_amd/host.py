@@ -417,12 +417,13 @@ class Batch:
 
     def set_input_device(self, d_text_ptr, d_doc_off_ptr, n_docs, total_bytes, keep=None, doc_off_host=None):
         """Device-resident input (e.g. torch tensors' data_ptr()); `keep` pins the owners."""
+        check(lib().dtk_batch_set_input_device(self._h, d_text_ptr, d_doc_off_ptr, int(n_docs), int(total_bytes)),
+              "dtk_batch_set_input_device")
+        # (only now: a rejected call leaves the batch, and this object, with the input they had)
         self._keep = keep
         self.n_docs = int(n_docs)
         self.total = int(total_bytes)
         self._doc_off = doc_off_host
-        check(lib().dtk_batch_set_input_device(self._h, d_text_ptr, d_doc_off_ptr, self.n_docs, self.total),
-              "dtk_batch_set_input_device")
 
     def run(self, tok: Tokenizer, flags=0):
         check(lib().dtk_batch_run(tok._h, self._h, flags), "dtk_batch_run")
@@ -455,6 +456,18 @@ class Batch:
         t = Totals()
         check(lib().dtk_batch_totals(self._h, C.byref(t)), "dtk_batch_totals")
         return {k: getattr(t, k) for k, _ in Totals._fields_}
+
+    def debug_stream(self):
+        """Test accessor (dtk_batch_debug_stream): what the symbolise kernel wrote in the last run, as (entries,
+        rune_start_words, saw_invalid) -- uint16[total] entries `symbol | width << 11 | class << 14` in the model
+        file's symbol numbering, the rune-start bitmap as uint32[(total + 31) // 32], and whether the run met an
+        invalid UTF-8 byte."""
+        entries = np.zeros(self.total, dtype=np.uint16)
+        words = np.zeros((self.total + 31) // 32, dtype=np.uint32)
+        saw = C.c_uint32(0)
+        check(lib().dtk_batch_debug_stream(self._h, entries.ctypes.data, words.ctypes.data, C.byref(saw)),
+              "dtk_batch_debug_stream")
+        return entries, words, bool(saw.value)
 
     def result_device(self) -> ResultView:
         v = ResultView()

@@ -122,6 +122,22 @@ const char *dtk_last_hip_error(void);
  * result.  Set before the models / batches it should affect are created. */
 int dtk_debug_configure(const char *key, const char *value);
 
+/* Test accessor, read-only: what the symbolise kernel wrote in the batch's last run.  Waits for that run, then copies
+ * home
+ *   entries[total]: one 16-bit entry per input byte,
+ *       bits 10..0   the symbol of the rune that starts at this byte, as the model FILE numbers it (sigmaASCII[c] /
+ *                    sigma[c] / identity, matrix.go:421-435; 0 for a net without an identity symbol),
+ *       bits 13..11  the bytes of that rune (Go DecodeRune width, 1..4); 0: no rune starts here, and the other bits
+ *                    of such an entry mean nothing,
+ *       bits 15..14  class: 0 rune < 256, 1 rune == U+0004 (EOT), 2 rune >= 256 in the sigma (ok = true),
+ *                    3 not in the sigma (ok = false),
+ *     whatever the stream's format on the device (one-byte codes are translated through the model's code table) and
+ *     the device table's column order (columns are translated back to the file's symbols);
+ *   rune_start_words[(total + 31) / 32]: bit g set: input byte g starts a rune;
+ *   *saw_invalid: 1 if the run met an invalid UTF-8 byte (it prints as U+FFFD), else 0.
+ * Any of the three may be NULL.  DTK_E_ARG before the batch's first run and between a new input and its run. */
+int dtk_batch_debug_stream(dtk_batch *b, uint16_t *entries, uint32_t *rune_start_words, uint32_t *saw_invalid);
+
 /* ---- model: replaces LoadTokenizerFile (fomafile.go:452-484), LoadMatrixFile
  *      (matrix.go:214-231), LoadDatokFile (datok.go:600-617).  gunzip, sniff
  *      "MATOK"/"DATOK", parse, build the device tables.  Immutable afterwards,

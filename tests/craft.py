@@ -93,6 +93,19 @@ def datok_from(arcs, sigma=None, size_cut=0) -> bytes:
     return gzip.compress(raw)
 
 
+def big_sigma(kind="matok"):
+    """A tokenizer whose sigma has 300 more characters (U+4E00 ..) than SIGMA: more distinct stream entries than a
+    byte can number, so the symbol stream holds the 16-bit entries themselves, and more runes >= 256 than the
+    symboliser keeps in LDS.  Forty of the new characters are letters like "a".  Returns (image, the 300 characters)."""
+    extra = [chr(0x4E00 + i) for i in range(300)]
+    arcs = _automaton(False)
+    for row in arcs.values():
+        if A in row:
+            for j in range(40):
+                row[len(SIGMA) + j] = row[A]
+    return {"matok": matok_from, "datok": datok_from}[kind](arcs, SIGMA + extra), extra
+
+
 ALPHABET = "aab b \x04.\n"
 
 

@@ -309,15 +309,8 @@ def test_symbol_stream_of_entries_for_a_sigma_beyond_the_code_table(tmp_path, ki
     them, documents that mix them with the usual letters, invalid bytes and runes outside the sigma."""
     import datok_amd
     from datok_amd import corpus
-    extra = [chr(0x4E00 + i) for i in range(300)]
-    sigma = craft.SIGMA + extra
     rng = np.random.default_rng(7)
-    arcs = craft._automaton(False)
-    for row in arcs.values():            # forty of the new characters are letters like "a"
-        if craft.A in row:
-            for j in range(40):
-                row[len(craft.SIGMA) + j] = row[craft.A]
-    blob = getattr(craft, kind + "_from")(arcs, sigma)
+    blob, extra = craft.big_sigma(kind)  # forty of the new characters are letters like "a"
     path = tmp_path / ("big." + kind)
     path.write_bytes(blob)
     tok, om = datok_amd.load_tokenizer_file(str(path)), _oracle(blob)

@@ -102,13 +102,17 @@ def test_loader_rejects_garbage(tmp_path):
         O.Model(str(q))
 
 
+# (bytes, (rune, width)); tests/test_symref.py sends the same vectors through the symboliser's reference
+GO_UTF8_VECTORS = [("ä".encode(), (0xE4, 2)), ("€".encode(), (0x20AC, 3)), ("😀".encode(), (0x1F600, 4)),
+                   (b"\x80", (0xFFFD, 1)),
+                   (b"\xc0\xaf", (0xFFFD, 1)),           # overlong
+                   (b"\xed\xa0\x80", (0xFFFD, 1)),       # surrogate
+                   (b"\xf4\x90\x80\x80", (0xFFFD, 1)),   # > U+10FFFF
+                   (b"\xe2\x82", (0xFFFD, 1))]           # truncated
+
+
 def test_go_utf8_decoder_spec():
     """Go unicode/utf8.DecodeRune: invalid -> (U+FFFD, 1). Unpinned by the reference's tests."""
-    assert O.decode_rune("ä".encode()) == (0xE4, 2)
-    assert O.decode_rune("€".encode()) == (0x20AC, 3)
-    assert O.decode_rune("😀".encode()) == (0x1F600, 4)
-    assert O.decode_rune(b"\x80") == (0xFFFD, 1)
-    assert O.decode_rune(b"\xc0\xaf") == (0xFFFD, 1)          # overlong
-    assert O.decode_rune(b"\xed\xa0\x80") == (0xFFFD, 1)      # surrogate
-    assert O.decode_rune(b"\xf4\x90\x80\x80") == (0xFFFD, 1)  # > U+10FFFF
-    assert O.decode_rune(b"\xe2\x82") == (0xFFFD, 1)          # truncated
+    assert len(GO_UTF8_VECTORS) == 8
+    for b, expected in GO_UTF8_VECTORS:
+        assert O.decode_rune(b) == expected, b

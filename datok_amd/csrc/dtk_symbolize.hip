@@ -2,21 +2,6 @@
 // clears of the run's event bitmaps and accumulators).  See dtk_walk.hip for the pipeline.
 #include "dtk_device.h"
 
-// ---------------------------------------------------------------- symbolise
-//
-// One wave per 4 KiB of input (staged in LDS), 512 bytes (8 per lane) per iteration.
-//   light: every byte < 0x80 is a complete rune: its entry comes from a 128-entry
-//          table in LDS and the lane's 8 entries leave as one 16-byte store.  Positions
-//          holding a byte >= 0x80 (a few percent of European text) are appended to a
-//          queue in LDS.
-//   heavy: once per KiB, lane i takes the i-th queued position, decodes it with Go's
-//          DecodeRune rules (matrix.go:392), decides whether that byte really
-//          starts a rune (look-back of up to 3 bytes), looks the rune up in the sigma
-//          map (runes < 256: a table; the others: binary search, both in LDS) and
-//          overwrites that one entry.  Documents never share a rune: look-back
-//          and look-ahead stop at the document boundary (reader EOF,
-//          matrix.go:394-399).
-
 // width Go's DecodeRune reports at a position (b0 first byte, `avail` bytes left in the
 // document).  Integer predicates on purpose: bool && chains become branches.
 __device__ __forceinline__ uint32_t go_width(uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3, uint32_t avail) {
@@ -33,45 +18,343 @@ __device__ __forceinline__ uint32_t go_width(uint32_t b0, uint32_t b1, uint32_t 
 
 
 #define SYM_BLOCK_BYTES DTK_SYM_BLOCK_BYTES
-#define SYM_TILE 512u
 #define SYM_SIG_LDS 64u  // runes >= 256 of the sigma kept in LDS (40 in the shipped models)
-#define SYM_HALF 1024u  // bytes per wave (its queue of bytes >= 0x80: 2 B of LDS per byte)
+#define SYM_HALF 1024u  // bytes per wave
 #define SYM_THREADS (WAVE * (SYM_BLOCK_BYTES / SYM_HALF))  // 256: four waves per 4 KiB block
 #define SYM_DOFF (SYM_BLOCK_BYTES / 16u)  // document offsets of a block kept in LDS (documents of 16 bytes on average and longer)
+#define SYM_FAR 0x10000u  // a document end this far behind the block's first byte or further: "not in this block"
 
-// SYM8: the stream holds one code per byte (DtkSigmaDev's code table) instead of the 16-bit entries; lut / lat then
-// hold codes too.
-template <bool ALIGNED4, bool SYM8>
-__global__ __launch_bounds__(SYM_THREADS) void k_symbolize(const uint8_t *__restrict__ text,
+// The run's accumulator block (totals, per-document counts, status and check words; dtk_batch_run) starts from
+// zero: the first blocks clear it here instead of a launch of its own in front (7 us of a batch's 230).  All but
+// DtkTotalsDev::invalid_epoch, which blocks of this very launch write: the number of the last run that saw an
+// invalid byte.
+__device__ __forceinline__ void sym_clear_acc(uint4 *__restrict__ acc, uint32_t acc16) {
+  if (!acc) return;
+  const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+  constexpr uint32_t kept16 = offsetof(DtkTotalsDev, invalid_epoch) / 16u;   // the unit of the word that is kept
+  constexpr uint32_t flags8 = offsetof(DtkTotalsDev, any_irregular) / 8u;    // its other word: cleared
+  for (uint32_t i = blockIdx.x * SYM_THREADS + threadIdx.x; i < acc16; i += gridDim.x * SYM_THREADS) {
+    if (i == kept16) reinterpret_cast<unsigned long long *>(acc)[flags8] = 0ull;  // any_irregular, any_eot; invalid_epoch stays
+    else acc[i] = z;
+  }
+}
+
+// The walk's event bitmaps start from zero: every block clears the words of the cursor positions of its bytes
+// (bit = byte + document index, dtk_internal.h; neighbours overlap by a word or two), the last block the rest --
+// a few stores per lane here instead of a 10 MB clear kernel in front.
+__device__ __forceinline__ void sym_clear_events(uint32_t *__restrict__ ev_bits, uint32_t bit_words, uint64_t block_start,
+                                                 uint32_t n_here, uint32_t d_lo, uint32_t d_hi) {
+  if (!ev_bits) return;
+  const uint64_t ga = block_start + d_lo, gb = block_start + n_here + d_hi + 1u;
+  // (block 0 from word 0: leading empty documents move d_lo, and with it `ga`, past the words of their positions)
+  const uint32_t wa = blockIdx.x == 0 ? 0u : (uint32_t)(ga >> 5);
+  uint32_t wb = (uint32_t)((gb + 31u) >> 5);
+  if (wb > bit_words || blockIdx.x == gridDim.x - 1) wb = bit_words;
+  for (uint32_t w = wa + threadIdx.x; w < wb; w += SYM_THREADS)
+#pragma unroll
+    for (uint32_t k = 0; k < EVB_KINDS; k++) ev_bits[(size_t)k * bit_words + w] = 0u;
+}
+
+// The host only asks whether the run saw an invalid byte (the renderer's slow path): the word holds the number of
+// the last run that did, and a wave looks before it writes.  (It used to be a count: documents cut through
+// their runes -- 64-byte pieces of running text -- made 30 000 adds to this one address queue up, 140 us of
+// a 32 MiB batch.)
+__device__ __forceinline__ void sym_saw_invalid(bool bad, unsigned long long *__restrict__ n_invalid, unsigned long long epoch) {
+  if (__ballot(bad) != 0ull && lane_id() == 0 &&
+      __hip_atomic_load(n_invalid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch)
+    atomicMax(n_invalid, epoch);
+}
+
+// ---------------------------------------------------------------- symbolise: one code per byte, decoded in registers
+//
+// The stream of every shipped model (DtkSigmaDev::n_codes != 0).  One wave per KiB, one lane per 16 consecutive
+// bytes: four words in registers from load to store.  No queue, no staging, and nothing leaves before the lane's
+// one 16-byte store.
+//   * a byte < 0x80 is its own code and starts a rune: nothing to do;
+//   * a byte >= 0xC0 always starts a rune.  Each lane walks its own such bytes, lowest first (the wave runs as
+//     many rounds as its busiest lane has: two or three in European text): the four bytes at the lead -- from the
+//     lane's words and the next lane's first word -- give Go's width; a width of two and more gives the rune and
+//     its code, which replaces the lead byte, and extends the lane's `covered` mask over the bytes behind it;
+//     a width of one is an invalid byte;
+//   * a continuation byte (0x80..0xBF) gets DTK_SYM_CONT if a sequence covers it and is an invalid byte of its own
+//     if none does: decided after the rounds, from `covered`.
+// A sequence that begins in one lane can cover up to three bytes of the next: bits 16..18 of `covered`, handed on
+// with one cross-lane move.  That spill depends on the previous lane's bytes and look-ahead only: lanes do not
+// chain.  The first lane of a wave has no lane before it and decodes the last lead byte among the three bytes in
+// front of it (a halo word) itself; the last lane looks ahead into a halo word too.  Sequences never cross a
+// document end (`avail`), so nothing looks back across one.
+// The rune-start bits of a lane are the complement of `covered`; two lanes make a word of the bitmap.
+
+// bit 7 of each of the four bytes of x: byte k -> bit k
+__device__ __forceinline__ uint32_t sym_gather7(uint32_t x) {
+  uint32_t t = x & 0x80808080u;
+  t |= t << 7;   // (bits 31, 30: bytes 3, 2;  bits 15, 14: bytes 1, 0)
+  t |= t << 14;  // (bits 29, 28: bytes 1, 0)
+  return t >> 28;
+}
+// 0xFF in every byte of x whose bit 7 is set in m (m: nothing but bits 7, 15, 23, 31)
+__device__ __forceinline__ uint32_t sym_bytes_of7(uint32_t m) { return (m << 1) - (m >> 7); }
+// bit k of a nibble -> bit 7 of byte k
+__device__ __forceinline__ uint32_t sym_spread7(uint32_t nib) {
+  uint32_t t = nib | (nib << 7);  // (bits 0, 8: k = 0, 1;  bits 2, 10: k = 2, 3)
+  t |= t << 14;                   // (bits 16, 24: k = 2, 3)
+  return (t & 0x01010101u) << 7;
+}
+// bytes p .. p + 3 of the 20 bytes w0 w1 w2 w3 nx  (p = 0..15; selects: an index into registers would go through scratch memory)
+__device__ __forceinline__ uint32_t sym_window(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t nx,
+                                                        uint32_t p) {
+  const bool k1 = (p & 4u) != 0u, k2 = (p & 8u) != 0u;
+  const uint32_t lo = k2 ? (k1 ? w3 : w2) : (k1 ? w1 : w0), hi = k2 ? (k1 ? nx : w3) : (k1 ? w2 : w1);
+  return __builtin_amdgcn_alignbyte(hi, lo, p & 3u);
+}
+// byte p of the 16 bytes w0 .. w3 := code
+__device__ __forceinline__ void sym_patch(uint32_t &w0, uint32_t &w1, uint32_t &w2, uint32_t &w3, uint32_t p,
+                                                   uint32_t code) {
+  const uint32_t sh = 8u * (p & 3u), keep = ~(0xFFu << sh), c = code << sh, k = p >> 2;
+  w0 = k == 0u ? (w0 & keep) | c : w0;
+  w1 = k == 1u ? (w1 & keep) | c : w1;
+  w2 = k == 2u ? (w2 & keep) | c : w2;
+  w3 = k == 3u ? (w3 & keep) | c : w3;
+}
+// the rune of a valid sequence of w >= 2 bytes in x (first byte lowest)
+__device__ __forceinline__ uint32_t sym_rune(uint32_t x, uint32_t w) {
+  const uint32_t b0 = x & 0xFFu, b1 = (x >> 8) & 0x3Fu, b2 = (x >> 16) & 0x3Fu, b3 = (x >> 24) & 0x3Fu;
+  const uint32_t r2 = ((b0 & 0x1Fu) << 6) | b1;
+  const uint32_t r3 = ((b0 & 0x0Fu) << 12) | (b1 << 6) | b2;
+  const uint32_t r4 = ((b0 & 0x07u) << 18) | (b1 << 12) | (b2 << 6) | b3;
+  return w == 2u ? r2 : (w == 3u ? r3 : r4);
+}
+
+template <bool ALIGNED4>
+__global__ __launch_bounds__(SYM_THREADS) void k_symbolize8(const uint8_t *__restrict__ text,
+                                                     const uint64_t *__restrict__ doc_off,
+                                                     uint32_t n_docs, uint64_t total, DtkSigmaDev sig,
+                                                     uint8_t *__restrict__ sym8,
+                                                     const uint32_t *__restrict__ blk_doc,
+                                                     unsigned long long *__restrict__ n_invalid,
+                                                     uint32_t *__restrict__ rs_bits,
+                                                     uint32_t *__restrict__ ev_bits, uint32_t bit_words,
+                                                     uint4 *__restrict__ acc, uint32_t acc16,
+                                                     unsigned long long epoch) {
+  sym_clear_acc(acc, acc16);
+  __shared__ uint32_t s_lat[64];              // code of a rune < 256 (four to a word; used from 128 on: two bytes wide)
+  __shared__ uint32_t s_runes[SYM_SIG_LDS];   // sigma map (runes >= 256) if it has fewer entries than this, padded
+  __shared__ uint8_t s_codes[SYM_SIG_LDS];    // their codes
+  __shared__ uint64_t s_doff[SYM_DOFF];       // the offsets of the documents of this block (if they are that few)
+  const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1u);
+  const uint64_t block_start = (uint64_t)blockIdx.x * SYM_BLOCK_BYTES;
+  const uint32_t n_here = (uint32_t)min((uint64_t)SYM_BLOCK_BYTES, total - block_start);
+  const uint32_t i0 = tid * 16u;  // my 16 bytes (offset in the block)
+  const uint64_t g0 = block_start + i0;
+
+  // ---- my four words, and for the wave's first and last lane the word in front and behind.  No byte outside
+  //      [text, text + total) of a caller's buffer is read: 4-byte loads only where address and size allow them
+  //      (ALIGNED4), else byte loads; both feed the same registers, bytes from `total` on are zero.
+  auto load4 = [&](uint64_t g) -> uint32_t {  // bytes g..g+3, zero outside [0, total)
+    uint32_t x = 0;
+    if (ALIGNED4) {
+      if (g < total) {
+        x = *reinterpret_cast<const uint32_t *>(text + g);
+        if (total - g < 4u) x &= (1u << (8u * (uint32_t)(total - g))) - 1u;  // (the padding of the batch's own buffer)
+      }
+    } else {
+      for (int k = 0; k < 4; k++)
+        if (g + k < total) x |= (uint32_t)text[g + k] << (8 * k);
+    }
+    return x;
+  };
+  uint32_t w0, w1, w2, w3, halo = 0;
+  if (ALIGNED4 && total - block_start >= SYM_BLOCK_BYTES + 4u) {  // block-uniform: every load lies inside
+    const uint32_t *t4 = reinterpret_cast<const uint32_t *>(text + g0);
+    w0 = t4[0]; w1 = t4[1]; w2 = t4[2]; w3 = t4[3];
+    if (lane == 0 && g0 >= 4u) halo = t4[-1];
+    if (lane == WAVE - 1u) halo = t4[4];
+  } else {
+    w0 = load4(g0); w1 = load4(g0 + 4u); w2 = load4(g0 + 8u); w3 = load4(g0 + 12u);
+    if (lane == 0 && g0 >= 4u) halo = load4(g0 - 4u);
+    if (lane == WAVE - 1u) halo = load4(g0 + 16u);
+  }
+
+  // ---- the small tables, while the text is on its way
+  const bool sig_lds = sig.n_runes < SYM_SIG_LDS;
+  if (tid < 64u) s_lat[tid] = reinterpret_cast<const uint32_t *>(sig.code_lt256)[tid];
+  if (sig_lds && tid < SYM_SIG_LDS) {  // (behind the map's runes: one that no rune reaches)
+    s_runes[tid] = tid < sig.n_runes ? sig.runes[tid] : 0xFFFFFFFFu;
+    if (tid < sig.n_runes) s_codes[tid] = sig.code_runes[tid];
+  }
+  // documents that can own bytes of this block: host-computed (document of each block's
+  // first byte), so no lane walks the offset table from scratch
+  const uint32_t d_lo = blk_doc[blockIdx.x];
+  const uint32_t d_hi = min(blk_doc[blockIdx.x + 1], n_docs - 1);
+  // their offsets, doc_off[d_lo .. d_hi + 1], in LDS: a block of tiny documents otherwise searches the table in memory
+  // once per lead byte (six dependent loads each; 64-byte documents: 203 us of symbolising per 32 MiB)
+  const uint32_t n_off = d_hi - d_lo + 2u;
+  if (n_off <= SYM_DOFF && tid < n_off) s_doff[tid] = doc_off[d_lo + tid];
+  const uint64_t lo_start = doc_off[d_lo], lo_end = doc_off[d_lo + 1];  // the block's first document
+  // (ends as offsets in the block: 32 bits; a block inside one document never looks further than this one)
+  const uint32_t lo_end_rel = (uint32_t)min(lo_end - block_start, (uint64_t)SYM_FAR);
+  sym_clear_events(ev_bits, bit_words, block_start, n_here, d_lo, d_hi);
+  __syncthreads();
+
+  if ((tid & ~(WAVE - 1u)) * 16u >= n_here) return;  // wave-uniform: nothing of this wave's KiB is input
+  // end (offset in the block) of the document that owns byte `pos` of the block, a document behind the block's first
+  auto doc_end_rel = [&](uint32_t pos) -> uint32_t {
+    const uint64_t g = block_start + pos;
+    uint64_t dend;
+    if (n_off <= SYM_DOFF) {
+      uint32_t lo = 0, hi = n_off - 1u;  // largest i with s_doff[i] <= g  (s_doff[0] <= g < s_doff[n_off - 1])
+      while (hi - lo > 1u) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (s_doff[mid] <= g) lo = mid; else hi = mid;
+      }
+      dend = s_doff[lo + 1u];
+    } else {
+      dend = doc_off[doc_of(doc_off, d_lo, d_hi + 1, g) + 1u];
+    }
+    return (uint32_t)min(dend - block_start, (uint64_t)SYM_FAR);
+  };
+
+  const uint32_t nval = i0 < n_here ? min(n_here - i0, 16u) : 0u;  // my bytes that are input
+  uint32_t covered = 0;  // bit i: a sequence that begins before my byte i covers it (bits 16..18: the next lane's)
+  if (__ballot(((w0 | w1 | w2 | w3) & 0x80808080u) != 0u) != 0ull) {  // wave-uniform: else the text is its stream
+    // the word that follows my bytes: the next lane's first, the halo for the last lane   (wave_shl:1)
+    const uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp((int)halo, (int)w0, 0x130, 0xF, 0xF, false);
+    const uint32_t hi16 = sym_gather7(w0) | (sym_gather7(w1) << 4) | (sym_gather7(w2) << 8) | (sym_gather7(w3) << 12);
+    uint32_t lead = sym_gather7(w0 & (w0 << 1)) | (sym_gather7(w1 & (w1 << 1)) << 4) |
+                    (sym_gather7(w2 & (w2 << 1)) << 8) | (sym_gather7(w3 & (w3 << 1)) << 12);  // bytes >= 0xC0
+    const uint32_t cont16 = hi16 & ~lead;
+    // the continuation bytes where they stand (bit 7 of the byte): the rounds put codes in place of lead bytes
+    const uint32_t c0 = w0 & ~(w0 << 1) & 0x80808080u, c1 = w1 & ~(w1 << 1) & 0x80808080u,
+                   c2 = w2 & ~(w2 << 1) & 0x80808080u, c3 = w3 & ~(w3 << 1) & 0x80808080u;
+    const uint32_t invalid_code = sig.code_fffd1;  // U+FFFD, one byte wide (the identity's code if the sigma has no U+FFFD)
+    bool bad = false;
+    uint32_t dend = lo_end_rel;  // end of the document of the lead byte at hand
+    // width Go reports for the sequence x that begins at byte `pos` of the block, in its document
+    auto width_at = [&](uint32_t x, uint32_t pos) -> uint32_t {
+      if (pos >= dend) dend = doc_end_rel(pos);  // (never in a block inside one document)
+      return go_width(x & 0xFFu, (x >> 8) & 0xFFu, (x >> 16) & 0xFFu, x >> 24, min(dend - pos, 4u));
+    };
+    // The first lane has no lane before it: what the sequence in front covers of its bytes it decodes itself, from the
+    // last lead byte among the three bytes in front (halo = bytes -4 .. -1), and only if its first byte can be covered.
+    uint32_t spill0 = 0;
+    if (lane == 0 && (cont16 & 1u) && g0 >= 4u) {
+      const uint32_t k = halo >= 0xC0000000u ? 1u : ((halo & 0x00C00000u) == 0x00C00000u ? 2u : ((halo & 0x0000C000u) == 0x0000C000u ? 3u : 0u));
+      if (k) {
+        const uint32_t x = __builtin_amdgcn_alignbyte(w0, halo, 4u - k);  // bytes -k .. 3 - k
+        const uint64_t g = g0 - k;
+        uint64_t de = lo_end;  // end of the document of that lead byte: it can lie in front of the block's first
+        if (g < lo_start) de = doc_off[doc_of(doc_off, 0, d_lo, g) + 1u];
+        else if (g >= lo_end) de = block_start + doc_end_rel(i0 - k);
+        const uint32_t w = go_width(x & 0xFFu, (x >> 8) & 0xFFu, (x >> 16) & 0xFFu, x >> 24, (uint32_t)min(de - g, (uint64_t)4u));
+        spill0 = w > k ? (1u << (w - k)) - 1u : 0u;
+      }
+    }
+    for (; __builtin_amdgcn_ballot_w64(lead != 0u) != 0ull; lead &= lead - 1u) {
+      if (lead == 0u) continue;
+      const uint32_t p = (uint32_t)__builtin_ctz(lead);
+      const uint32_t x = sym_window(w0, w1, w2, w3, nx, p);
+      const uint32_t w = width_at(x, i0 + p);
+      uint32_t code = invalid_code;
+      if (w >= 2u) {
+        const uint32_t rune = sym_rune(x, w);
+        if (rune < 256u) {
+          code = (s_lat[rune >> 2] >> (8u * (rune & 3u))) & 0xFFu;
+        } else {  // matrix.go:427-435: a, ok = sigma[char]; !ok -> identity
+          // (selects: a per-lane index into the kernel argument would go through scratch memory)
+          code = w == 2u ? sig.code_ident[2] : (w == 3u ? sig.code_ident[3] : sig.code_ident[4]);
+          // how many runes of the sorted map are <= rune, in steps that are the same for every lane
+          if (sig_lds) {  // (padded with 0xFFFFFFFF to 64 entries, fewer than 64 runes: six steps)
+            uint32_t n = 0;
+#pragma unroll
+            for (uint32_t step = SYM_SIG_LDS / 2u; step; step >>= 1) n += s_runes[n + step - 1u] <= rune ? step : 0u;
+            if (n && s_runes[n - 1u] == rune) code = s_codes[n - 1u];
+          } else {
+            uint32_t base = 0;  // the last rune <= rune, if there is one
+            for (uint32_t len = sig.n_runes; len > 1u;) {
+              const uint32_t half = len >> 1;
+              base = sig.runes[base + half] <= rune ? base + half : base;
+              len -= half;
+            }
+            if (sig.runes[base] == rune) code = sig.code_runes[base];
+          }
+        }
+      }
+      sym_patch(w0, w1, w2, w3, p, code);
+      covered |= ((1u << w) - 2u) << p;  // bytes p + 1 .. p + w - 1
+      bad |= w == 1u;  // prints as U+FFFD, three bytes (the renderer's slow path)
+    }
+    // what the previous lane's last sequence covers of my bytes: its bits 16..18 are my bits 0..2   (wave_shr:1)
+    uint32_t spill = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(covered >> 16), 0x138, 0xF, 0xF, false);
+    if (lane == 0) spill = spill0;
+    covered = (covered | spill) & 0xFFFFu;
+    // continuation bytes: DTK_SYM_CONT, all of them ...
+    static_assert(DTK_SYM_CONT == 0xFFu, "a continuation byte becomes DTK_SYM_CONT by setting all its bits");
+    w0 |= sym_bytes_of7(c0); w1 |= sym_bytes_of7(c1); w2 |= sym_bytes_of7(c2); w3 |= sym_bytes_of7(c3);
+    // ... but those that no sequence covers: each an invalid byte of its own (none in well-formed text: wave-uniform)
+    const uint32_t stray = cont16 & ~covered;
+    if (__ballot(stray != 0u) != 0ull) {
+      const uint32_t flip = (DTK_SYM_CONT ^ invalid_code) * 0x01010101u;
+      w0 ^= sym_bytes_of7(sym_spread7(stray & 15u)) & flip;
+      w1 ^= sym_bytes_of7(sym_spread7((stray >> 4) & 15u)) & flip;
+      w2 ^= sym_bytes_of7(sym_spread7((stray >> 8) & 15u)) & flip;
+      w3 ^= sym_bytes_of7(sym_spread7(stray >> 12)) & flip;
+      bad |= stray != 0u;
+    }
+    sym_saw_invalid(bad, n_invalid, epoch);
+  }
+
+  // ---- the lane's one store (a whole lane, 16-byte aligned), or its bytes one by one at the batch's ragged end
+  if (nval == 16u && ((reinterpret_cast<uintptr_t>(sym8) + block_start) & 15u) == 0) {
+    *reinterpret_cast<uint4 *>(sym8 + g0) = make_uint4(w0, w1, w2, w3);
+  } else {
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; j++) {
+      const uint32_t wj = j < 4u ? w0 : (j < 8u ? w1 : (j < 12u ? w2 : w3));
+      if (j < nval) sym8[g0 + j] = (uint8_t)(wj >> (8u * (j & 3u)));
+    }
+  }
+  // the rune-start bitmap (bit g of the array = input byte g; the compaction counts runes with it instead of reading
+  // the stream again): my bytes that no sequence covers; the even lane stores the word of two lanes   (row_shl:1)
+  const uint32_t starts = ((1u << nval) - 1u) & ~covered;
+  const uint32_t upper = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)starts, 0x101, 0xF, 0xF, true);
+  if (!(lane & 1u) && nval) rs_bits[(block_start >> 5) + (tid >> 1)] = starts | (upper << 16);
+}
+
+// ---------------------------------------------------------------- symbolise: 16-bit entries
+//
+// Models whose entries do not fit the code table (more than 255 of them).  Every byte < 0x80 needs a table read, so
+// this kernel stages its block.  One wave per KiB of a 4 KiB block (staged in LDS), 512 bytes (8 per lane) per
+// iteration.
+//   light: every byte < 0x80 is a complete rune: its entry comes from a 128-entry
+//          table in LDS and the lane's 8 entries leave as one 16-byte store.  Positions
+//          holding a byte >= 0x80 (a few percent of European text) are appended to a
+//          queue in LDS.
+//   heavy: once per KiB, lane i takes the i-th queued position, decodes it with Go's
+//          DecodeRune rules (matrix.go:392), decides whether that byte really
+//          starts a rune (look-back of up to 3 bytes), looks the rune up in the sigma
+//          map (runes < 256: a table; the others: binary search, both in LDS) and
+//          overwrites that one entry.  Documents never share a rune: look-back
+//          and look-ahead stop at the document boundary (reader EOF,
+//          matrix.go:394-399).
+#define SYM_TILE 512u
+
+template <bool ALIGNED4>
+__global__ __launch_bounds__(SYM_THREADS) void k_symbolize16(const uint8_t *__restrict__ text,
                                                     const uint64_t *__restrict__ doc_off,
                                                     uint32_t n_docs, uint64_t total, DtkSigmaDev sig,
-                                                    void *__restrict__ sym_,
+                                                    uint16_t *__restrict__ sym,
                                                     const uint32_t *__restrict__ blk_doc,
                                                     unsigned long long *__restrict__ n_invalid,
                                                     uint32_t *__restrict__ rs_bits,
                                                     uint32_t *__restrict__ ev_bits, uint32_t bit_words,
                                                     uint4 *__restrict__ acc, uint32_t acc16,
                                                     unsigned long long epoch) {
-  // The run's accumulator block (totals, per-document counts, status and check words; dtk_batch_run) starts from
-  // zero: the first blocks clear it here instead of a launch of its own in front (7 us of a batch's 230).  All but
-  // DtkTotalsDev::invalid_epoch, which blocks of this very launch write: the number of the last run that saw an
-  // invalid byte.
-  if (acc) {
-    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-    constexpr uint32_t kept16 = offsetof(DtkTotalsDev, invalid_epoch) / 16u;   // the unit of the word that is kept
-    constexpr uint32_t flags8 = offsetof(DtkTotalsDev, any_irregular) / 8u;    // its other word: cleared
-    for (uint32_t i = blockIdx.x * SYM_THREADS + threadIdx.x; i < acc16; i += gridDim.x * SYM_THREADS) {
-      if (i == kept16) reinterpret_cast<unsigned long long *>(acc)[flags8] = 0ull;  // any_irregular, any_eot; invalid_epoch stays
-      else acc[i] = z;
-    }
-  }
-  uint16_t *__restrict__ sym = static_cast<uint16_t *>(sym_);
-  uint8_t *__restrict__ sym8 = static_cast<uint8_t *>(sym_);
+  sym_clear_acc(acc, acc16);
   __shared__ uint32_t s_rs[SYM_BLOCK_BYTES / 32];  // bit i: byte i of the block starts a rune
   __shared__ uint16_t lut[128];       // symbol | class | width 1 for the runes < 128 (index = byte)
   __shared__ uint16_t lat[256];       // symbol | class for runes < 256 (heavy path, Latin-1)
   __shared__ uint32_t s_runes[SYM_SIG_LDS];   // sigma map (runes >= 256), if it fits
-  __shared__ uint16_t s_syms[SYM_SIG_LDS];  // (SYM8: their codes)
+  __shared__ uint16_t s_syms[SYM_SIG_LDS];
   __shared__ uint32_t s_txt[SYM_BLOCK_BYTES / 4 + 4];  // the block's bytes, one dword of halo either side
   __shared__ uint16_t s_qs[SYM_BLOCK_BYTES / SYM_HALF][SYM_HALF];  // per wave: positions (offset in the block) of the bytes >= 0x80 of its quarter
   __shared__ uint64_t s_doff[SYM_DOFF];  // the offsets of the documents of this block (if they are that few)
@@ -81,15 +364,10 @@ __global__ __launch_bounds__(SYM_THREADS) void k_symbolize(const uint8_t *__rest
   for (uint32_t i = tid; i < SYM_BLOCK_BYTES / 32; i += SYM_THREADS) s_rs[i] = 0;
   for (uint32_t i = tid; i < 256u; i += SYM_THREADS) {
     // matrix.go:421-426: runes < 256 go through sigmaASCII; rune 4 is EOT
-    if (SYM8) {
-      lat[i] = sig.code_lt256[i];  // (lut is not used: the code of a byte < 128 is the byte)
-      if (sig_lds && i < sig.n_runes) { s_runes[i] = sig.runes[i]; s_syms[i] = sig.code_runes[i]; }
-    } else {
-      const uint32_t e = (sig.ascii[i] & DTK_SYM_MASK) | (i == DTK_EOT ? (1u << DTK_SYM_CLS_SHIFT) : 0u);
-      lat[i] = (uint16_t)e;
-      if (i < 128u) lut[i] = (uint16_t)(e | (1u << DTK_SYM_W_SHIFT));
-      if (sig_lds && i < sig.n_runes) { s_runes[i] = sig.runes[i]; s_syms[i] = sig.syms[i]; }
-    }
+    const uint32_t e = (sig.ascii[i] & DTK_SYM_MASK) | (i == DTK_EOT ? (1u << DTK_SYM_CLS_SHIFT) : 0u);
+    lat[i] = (uint16_t)e;
+    if (i < 128u) lut[i] = (uint16_t)(e | (1u << DTK_SYM_W_SHIFT));
+    if (sig_lds && i < sig.n_runes) { s_runes[i] = sig.runes[i]; s_syms[i] = sig.syms[i]; }
   }
   const uint64_t block_start = (uint64_t)blockIdx.x * SYM_BLOCK_BYTES;
   const uint32_t n_here = (uint32_t)min((uint64_t)SYM_BLOCK_BYTES, total - block_start);
@@ -125,21 +403,9 @@ __global__ __launch_bounds__(SYM_THREADS) void k_symbolize(const uint8_t *__rest
   const uint8_t *__restrict__ sb = reinterpret_cast<const uint8_t *>(s_txt) + 4;  // sb[i] = text[block_start + i]
 
   const uint64_t lo_start = doc_off[d_lo], lo_end = doc_off[d_lo + 1];  // the block's first document
-  if (ev_bits) {
-    // The walk's event bitmaps start from zero: every block clears the words of the cursor positions of its bytes
-    // (bit = byte + document index, dtk_internal.h; neighbours overlap by a word or two), the last block the rest --
-    // a few stores per lane here instead of a 10 MB clear kernel in front.
-    const uint64_t ga = block_start + d_lo, gb = block_start + n_here + d_hi + 1u;
-    // (block 0 from word 0: leading empty documents move d_lo, and with it `ga`, past the words of their positions)
-    const uint32_t wa = blockIdx.x == 0 ? 0u : (uint32_t)(ga >> 5);
-    uint32_t wb = (uint32_t)((gb + 31u) >> 5);
-    if (wb > bit_words || blockIdx.x == gridDim.x - 1) wb = bit_words;
-    for (uint32_t w = wa + tid; w < wb; w += SYM_THREADS)
-#pragma unroll
-      for (uint32_t k = 0; k < EVB_KINDS; k++) ev_bits[(size_t)k * bit_words + w] = 0u;
-  }
-  // (the light path's vector stores: 8 entries = 16 bytes, or 8 codes = 8 bytes)
-  const bool sym16 = ((reinterpret_cast<uintptr_t>(sym_) + (SYM8 ? 1ull : 2ull) * block_start) & (SYM8 ? 7u : 15u)) == 0;
+  sym_clear_events(ev_bits, bit_words, block_start, n_here, d_lo, d_hi);
+  // (the light path's vector stores: 8 entries = 16 bytes)
+  const bool sym16 = ((reinterpret_cast<uintptr_t>(sym) + 2ull * block_start) & 15u) == 0;
 
   // (the four quarters used to be one wave's four rounds: a chain of load -> light -> wait for the stores -> heavy,
   //  four times over, with four waves per SIMD to hide it; now the rounds are four waves)
@@ -155,25 +421,16 @@ __global__ __launch_bounds__(SYM_THREADS) void k_symbolize(const uint8_t *__rest
       const uint32_t w0 = s_txt[1 + (i0 >> 2)], w1 = s_txt[2 + (i0 >> 2)];
       uint32_t left = 8u;
       if (!FULL) left = i0 < n_here ? (n_here - i0 >= 8u ? 8u : n_here - i0) : 0u;
-      if (SYM8) {
-        // the code of a byte < 128 is the byte itself (upload()): the light path is a copy
-        if (FULL || (left == 8u && sym16)) {
-          *reinterpret_cast<uint2 *>(sym8 + block_start + i0) = make_uint2(w0, w1);
-        } else {
-          for (uint32_t j = 0; j < left; j++) sym8[block_start + i0 + j] = (uint8_t)((j < 4u ? w0 >> (8u * j) : w1 >> (8u * j - 32u)));
-        }
+      const uint32_t e0 = lut[w0 & 0x7Fu], e1 = lut[(w0 >> 8) & 0x7Fu];
+      const uint32_t e2 = lut[(w0 >> 16) & 0x7Fu], e3 = lut[(w0 >> 24) & 0x7Fu];
+      const uint32_t e4 = lut[w1 & 0x7Fu], e5 = lut[(w1 >> 8) & 0x7Fu];
+      const uint32_t e6 = lut[(w1 >> 16) & 0x7Fu], e7 = lut[(w1 >> 24) & 0x7Fu];
+      if (FULL || (left == 8u && sym16)) {
+        *reinterpret_cast<uint4 *>(sym + block_start + i0) =
+            make_uint4(e0 | (e1 << 16), e2 | (e3 << 16), e4 | (e5 << 16), e6 | (e7 << 16));
       } else {
-        const uint32_t e0 = lut[w0 & 0x7Fu], e1 = lut[(w0 >> 8) & 0x7Fu];
-        const uint32_t e2 = lut[(w0 >> 16) & 0x7Fu], e3 = lut[(w0 >> 24) & 0x7Fu];
-        const uint32_t e4 = lut[w1 & 0x7Fu], e5 = lut[(w1 >> 8) & 0x7Fu];
-        const uint32_t e6 = lut[(w1 >> 16) & 0x7Fu], e7 = lut[(w1 >> 24) & 0x7Fu];
-        if (FULL || (left == 8u && sym16)) {
-          *reinterpret_cast<uint4 *>(sym + block_start + i0) =
-              make_uint4(e0 | (e1 << 16), e2 | (e3 << 16), e4 | (e5 << 16), e6 | (e7 << 16));
-        } else {
-          const uint32_t o[8] = {e0, e1, e2, e3, e4, e5, e6, e7};
-          for (uint32_t j = 0; j < left; j++) sym[block_start + i0 + j] = (uint16_t)o[j];
-        }
+        const uint32_t o[8] = {e0, e1, e2, e3, e4, e5, e6, e7};
+        for (uint32_t j = 0; j < left; j++) sym[block_start + i0 + j] = (uint16_t)o[j];
       }
       // one bit per byte: bytes < 0x80 start a rune (the others are decided one by one below)
       auto nib = [](uint32_t x) { return ((x >> 7) & 1u) | ((x >> 14) & 2u) | ((x >> 21) & 4u) | ((x >> 28) & 8u); };
@@ -258,41 +515,28 @@ __global__ __launch_bounds__(SYM_THREADS) void k_symbolize(const uint8_t *__rest
         const uint32_t r3 = ((b0 & 0x0Fu) << 12) | ((b1 & 0x3Fu) << 6) | (b2 & 0x3Fu);
         const uint32_t r4 = ((b0 & 0x07u) << 18) | ((b1 & 0x3Fu) << 12) | ((b2 & 0x3Fu) << 6) | (b3 & 0x3Fu);
         const uint32_t rune = wd == 1 ? 0xFFFDu : (wd == 2 ? r2 : (wd == 3 ? r3 : r4));
-        uint32_t a_cls;  // (SYM8: the code of the rune in the width it has here)
+        uint32_t a_cls;
         if (rune < 256u) {
           a_cls = lat[rune];  // (two bytes wide: 128..255)
         } else {  // matrix.go:427-435: a, ok = sigma[char]; !ok -> identity
           int l = 0, h = (int)sig.n_runes - 1;
           a_cls = (sig.identity & DTK_SYM_MASK) | (3u << DTK_SYM_CLS_SHIFT);
-          if (SYM8)  // (selects: a per-lane index into the kernel argument would go through scratch memory)
-            a_cls = wd == 1u ? sig.code_ident[1] : (wd == 2u ? sig.code_ident[2] : (wd == 3u ? sig.code_ident[3] : sig.code_ident[4]));
           while (l <= h) {
             const int m = (l + h) >> 1;
             const uint32_t r = sig_lds ? s_runes[m] : sig.runes[m];
             if (r == rune) {
-              if (SYM8)  // (U+FFFD itself in the sigma: three bytes wide as a rune, one as an invalid byte)
-                a_cls = wd == 1u ? (uint32_t)sig.code_fffd1 : (sig_lds ? (uint32_t)s_syms[m] : (uint32_t)sig.code_runes[m]);
-              else
-                a_cls = ((sig_lds ? (uint32_t)s_syms[m] : (uint32_t)sig.syms[m]) & DTK_SYM_MASK) |
-                        (2u << DTK_SYM_CLS_SHIFT);
+              a_cls = ((sig_lds ? (uint32_t)s_syms[m] : (uint32_t)sig.syms[m]) & DTK_SYM_MASK) | (2u << DTK_SYM_CLS_SHIFT);
               break;
             }
             if (r < rune) l = m + 1; else h = m - 1;
           }
         }
-        if (SYM8) sym8[g] = (uint8_t)(start ? a_cls : DTK_SYM_CONT);
-        else sym[g] = (uint16_t)(a_cls | (start ? wd << DTK_SYM_W_SHIFT : 0u));
+        sym[g] = (uint16_t)(a_cls | (start ? wd << DTK_SYM_W_SHIFT : 0u));
         if (start) atomicOr(&s_rs[pos >> 5], 1u << (pos & 31u));
         // a byte that decodes to U+FFFD with width 1 prints as three bytes (the renderer's slow path)
         bad = start && wd == 1u;
       }
-      // The host only asks whether the run saw such a byte (the renderer's slow path): the word holds the number of
-      // the last run that did, and a wave looks before it writes.  (It used to be a count: documents cut through
-      // their runes -- 64-byte pieces of running text -- made 30 000 adds to this one address queue up, 140 us of
-      // a 32 MiB batch.)
-      if (__ballot(bad) != 0ull && lane == 0 &&
-          __hip_atomic_load(n_invalid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch)
-        atomicMax(n_invalid, epoch);
+      sym_saw_invalid(bad, n_invalid, epoch);
     }
   }
   // the block's rune-start bitmap (bit g of the array = input byte g): the compaction counts
@@ -314,13 +558,14 @@ extern "C" int dtk_launch_symbolize(const uint8_t *text, const uint64_t *doc_off
   // ALIGNED4 may read up to 3 bytes past `total`: true for the batch's own (padded) buffer;
   // a caller-owned device buffer only qualifies when its size is a multiple of 4
   const bool al4 = (((uintptr_t)text) & 3u) == 0 && (padded || (total & 3u) == 0);
-  auto go = [&](auto k) {
+  auto go = [&](auto k, auto *out) {
     hipLaunchKernelGGL(k, dim3(blocks), dim3(SYM_THREADS), 0, (hipStream_t)stream, text, doc_off, n_docs,
-                       total, *sig, sym, blk_doc, n_invalid, rs_bits, ev_bits, bit_words, (uint4 *)acc, (uint32_t)(acc_bytes / 16),
+                       total, *sig, out, blk_doc, n_invalid, rs_bits, ev_bits, bit_words, (uint4 *)acc, (uint32_t)(acc_bytes / 16),
                        (unsigned long long)epoch);
   };
-  if (sig->n_codes) { if (al4) go(k_symbolize<true, true>); else go(k_symbolize<false, true>); }
-  else { if (al4) go(k_symbolize<true, false>); else go(k_symbolize<false, false>); }
+  // (one kernel per format of the stream: codes -- every shipped model --, or the 16-bit entries)
+  if (sig->n_codes) { if (al4) go(k_symbolize8<true>, (uint8_t *)sym); else go(k_symbolize8<false>, (uint8_t *)sym); }
+  else { if (al4) go(k_symbolize16<true>, (uint16_t *)sym); else go(k_symbolize16<false>, (uint16_t *)sym); }
   return (int)hipGetLastError();
 }
 

@@ -43,7 +43,7 @@ extern "C" int dtk_batch_create(uint64_t max_bytes, uint32_t max_docs, dtk_batch
   int rc = b->stream.create();
   if (rc != DTK_OK) return rc;
   if (g_dbg.round_limit >= 0) b->round_limit = (uint32_t)g_dbg.round_limit;
-  const uint64_t pad = 256, nd1 = (uint64_t)max_docs + 1;
+  const uint64_t pad = DTK_STREAM_PAD, nd1 = (uint64_t)max_docs + 1;
   auto make = [](auto &a, uint64_t n) { return a.fit(n, n); };  // (elements, not bytes)
   if ((rc = make(b->d_text_own, max_bytes + pad)) || (rc = make(b->d_off_own, nd1)) ||
       (rc = make(b->d_sym, max_bytes + pad)) || (rc = make(b->d_rsbits, (max_bytes + pad) / 8 + 64)) ||

@@ -20,7 +20,8 @@
 // whole suite over each of them; only dtk_debug_configure sets them (the Python harness forwards DATOK_* variables
 // to it, datok_amd/_lib.py -- the shipped entry points never look).  None of them changes a result.
 struct DtkDebug {
-  int sym16 = 0;         // 16-bit stream entries (and the general loop) although the model's entries fit a code table
+  int sym16 = 0;         // 16-bit stream entries although the model's entries fit a code table
+  int general16 = 0;     // a stream of 16-bit entries is walked by the general loop (as before the lean loop read them): A/B timing
   int force_wide = 0;    // 32-bit plain cells for any model (MatrixTrans<uint32_t>)
   int file_columns = 0;  // keep the file's column order
   int no_fused = 0;      // plain cells (uint16, uint32 from 32 767 states on): no fused epsilon + rune cells
@@ -51,6 +52,7 @@ struct dtk_model {
   uint32_t dense_states = 0;   // double array laid out as a matrix (densify in build_datok): its states; 0: the pairs are walked
   uint64_t array_len = 0;
   uint32_t n_eps_states = 0, max_eps_chain = 0, unknown_used = 0;
+  uint32_t lean_walk = 0;      // dtk_batch_run walks this model with the lean loop (build_images)
   uint64_t device_bytes = 0;
   int device = 0;
   bool host_only = false;      // dtk_model_info_mem: the host images are built and measured, nothing is copied to a device

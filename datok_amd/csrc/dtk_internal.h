@@ -33,6 +33,22 @@
 #ifndef DTK_WIN8
 #define DTK_WIN8 32u  // positions in a lean-walk row of codes (a multiple of 16; the row has 8 bytes more: 40 B)
 #endif
+// The lean walk's row over a stream of 16-bit entries (a model with more than 255 of them): DTK_WIN16 entries, a
+// multiple of 8; DTK_ROW_PAD16 bytes between the lanes' rows (a multiple of 8); DTK_WALK_OCC16 waves per SIMD the
+// first pass is built for -- what the LDS of a wave admits.  Build knobs of the recorded A/B; what
+// they must keep is checked at compile time (WinChecked, dtk_walk_core.h).
+#ifndef DTK_WIN16
+#define DTK_WIN16 16u
+#endif
+#ifndef DTK_ROW_PAD16
+#define DTK_ROW_PAD16 0u
+#endif
+#ifndef DTK_WALK_OCC16
+#define DTK_WALK_OCC16 7
+#endif
+// Elements behind max_bytes that a batch's stream (and text) buffers are allocated with (dtk_batch_create): the lean
+// loop reads up to a row behind the batch's last byte (the static_asserts behind WinEntries, dtk_walk_core.h)
+#define DTK_STREAM_PAD 256u
 struct DtkSym {
   const void *base;     // uint8_t codes if lut, else uint16_t entries
   const uint16_t *lut;  // [256] entry of a code (lut[DTK_SYM_CONT] has width 0), or null
@@ -152,6 +168,7 @@ struct DtkTableDev {
   uint32_t da_size;      // array[1].check & RESTBIT (datok.go:333-335)
   uint32_t da_base1;     // device base word of index 1
   uint32_t epsilon, unknown, identity;
+  uint32_t lean16;       // a stream of 16-bit entries is walked by the lean loop too (0: test hook GENERAL16, the general loop)
 };
 
 // ---- speculative chunk lanes

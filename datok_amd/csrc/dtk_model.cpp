@@ -54,7 +54,7 @@ extern "C" int dtk_debug_configure(const char *key, const char *value) {
   if (!key) return DTK_E_ARG;
   const int v = value ? atoi(value) : 1;
   const struct { const char *name; int *field; bool flag; } tab[] = {
-      {"SYM16", &g_dbg.sym16, true}, {"FORCE_WIDE", &g_dbg.force_wide, true}, {"FILE_COLUMNS", &g_dbg.file_columns, true},
+      {"SYM16", &g_dbg.sym16, true}, {"GENERAL16", &g_dbg.general16, true}, {"FORCE_WIDE", &g_dbg.force_wide, true}, {"FILE_COLUMNS", &g_dbg.file_columns, true},
       {"NO_FUSED", &g_dbg.no_fused, true}, {"WIDE_FUSED", &g_dbg.wide_fused, true}, {"NO_DENSE", &g_dbg.no_dense, true}, {"SMALL_MAX", &g_dbg.small_max, false},
       {"LDS_BITS", &g_dbg.lds_bits, false}, {"SPLIT_START", &g_dbg.split_start, false}, {"DEV_ROUNDS", &g_dbg.dev_rounds, false},
       {"COMPACT_FULL", &g_dbg.compact_full, true}, {"CLEAR_KERNEL", &g_dbg.clear_kernel, true},
@@ -226,6 +226,11 @@ static void build_images(dtk_model *m, size_t tab_bytes, HostImages &im) {
   m->tab.unknown = m->unknown < 0 ? (uint32_t)m->unknown : colof(m, m->unknown);
   m->tab.identity = m->identity < 0 ? (uint32_t)m->identity : colof(m, m->identity);
   if (m->tab.ident_guard != 0xFFFFFFFFu) m->tab.ident_guard = colof(m, (int)m->tab.ident_guard);
+  // Which loop (with_trans, dtk_walk_core.h): the lean one for fused cells without an arc on `unknown`, over codes
+  // or over 16-bit entries alike.
+  m->tab.lean16 = g_dbg.general16 ? 0u : 1u;
+  m->lean_walk = (m->tab.kind == DTK_KIND_MATRIX && m->tab.fused && m->tab.ident_guard == 0xFFFFFFFFu &&
+                  (m->sig.n_codes != 0 || m->tab.lean16)) ? 1u : 0u;
 }
 
 static int copy_images(dtk_model *m, const void *tab, size_t tab_bytes, const HostImages &im) {
@@ -648,5 +653,6 @@ extern "C" int dtk_model_get_info(const dtk_model *m, dtk_model_info *o) {
   o->entry_bytes = m->tab.entry_bytes; o->device_bytes = m->device_bytes; o->unknown_used = m->unknown_used;
   o->dense_states = m->dense_states;
   o->stream_codes = m->sig.n_codes;
+  o->lean_walk = m->lean_walk;
   return DTK_OK;
 }

@@ -93,12 +93,28 @@ struct MatrixFused64Trans : FusedTransOf<FusedCell64> {};  // ... and beyond
 // The same tables walked by the lean loop (walk_fused): chosen by the launcher when no state has an
 // arc on `unknown` (separate types so that the kernels only carry one loop: fewer registers).
 // (k_spec_both is built for DTK_WALK_OCC waves per SIMD with either: the wide loop needs no more registers)
+// `window`: the format of the symbol stream the loop reads -- one-byte codes (WinCodes), or the 16-bit entries
+// themselves for a model with more than 255 of them (WinEntries); both below, in front of walk_fused.
+struct WinCodes;
+struct WinEntries;
 struct MatrixLeanTrans : MatrixFusedTrans {
   typedef MatrixFusedTrans general;
+  typedef WinCodes window;
   static constexpr bool LEAN = true;
 };
 struct MatrixLean64Trans : MatrixFused64Trans {
   typedef MatrixFused64Trans general;
+  typedef WinCodes window;
+  static constexpr bool LEAN = true;
+};
+struct MatrixLeanE16Trans : MatrixFusedTrans {
+  typedef MatrixFusedTrans general;
+  typedef WinEntries window;
+  static constexpr bool LEAN = true;
+};
+struct MatrixLean64E16Trans : MatrixFused64Trans {
+  typedef MatrixFused64Trans general;
+  typedef WinEntries window;
   static constexpr bool LEAN = true;
 };
 
@@ -359,19 +375,69 @@ __device__ __forceinline__ void win_fill(dtk_u16a *row, const DtkSym &S, uint64_
   }
 }
 
-// the lean loop's row: DTK_WIN8 codes
-__device__ __forceinline__ void win_fill8(dtk_u8a *row, const uint8_t *__restrict__ from) {
+// The lean loop's window, one of two stream formats (a policy's `window`).  What the loop asks of it: the row's element
+// type, the entries a row holds (WIN), the alignment of a row's first element in the stream (ALIGN elements = 16
+// bytes: rows are filled with 16-byte loads), fill(), and entry(): the stream entry of a row element.  What the
+// kernels ask: the row's size in LDS, the code table's, and the waves per SIMD the kernel is built for.
+#ifndef DTK_ROW_PAD
+#define DTK_ROW_PAD 0u  // bytes between the lanes' rows of codes.  (8 until round 3, to stagger the banks: without them a wave's LDS is 5728 B at 128-byte chunks and seven waves per SIMD fit a CU; the conflicts of the one-byte reads cost nothing measurable: walk 53.8 -> 51.9 us saturated)
+#endif
+#ifndef DTK_WALK_OCC
+#define DTK_WALK_OCC 7  // the lean loop in 72 VGPRs (the allocator finds them without another spill): 7 waves per SIMD where LDS allows (three batches in flight: walk -5 %)
+#endif
+// a row of N16 * 16 bytes of the stream into LDS
+template <uint32_t N16>
+__device__ __forceinline__ void win_fill_row(void *row, const void *__restrict__ from) {
   const uint4 *__restrict__ g = reinterpret_cast<const uint4 *>(from);
-  uint4 v[DTK_WIN8 / 16u];
+  uint4 v[N16];
 #pragma unroll
-  for (uint32_t i = 0; i < DTK_WIN8 / 16u; i++) v[i] = g[i];  // all loads before the first LDS write
+  for (uint32_t i = 0; i < N16; i++) v[i] = g[i];  // all loads before the first LDS write
   dtk_u2a *r = reinterpret_cast<dtk_u2a *>(row);
 #pragma unroll
-  for (uint32_t i = 0; i < DTK_WIN8 / 16u; i++) {
+  for (uint32_t i = 0; i < N16; i++) {
     r[2 * i] = make_uint2(v[i].x, v[i].y);
     r[2 * i + 1] = make_uint2(v[i].z, v[i].w);
   }
 }
+// codes: DTK_WIN8 one-byte codes per row, the entry of a code from the model's table in LDS
+struct WinCodes {
+  typedef dtk_u8a elem;
+  typedef uint8_t mem;
+  static constexpr uint32_t WIN = DTK_WIN8, ALIGN = 16u, ROW_U16 = (DTK_WIN8 + DTK_ROW_PAD) / 2u, LUT = 256u;
+  static constexpr int OCC = DTK_WALK_OCC;
+  static __device__ __forceinline__ void fill(elem *row, const mem *__restrict__ from) { win_fill_row<DTK_WIN8 / 16u>(row, from); }
+  static __device__ __forceinline__ uint32_t entry(const uint16_t *lut, uint32_t c) { return lut[c]; }
+};
+// entries: a model with more than 255 of them.  DTK_WIN16 16-bit entries per row, read as they are: no table in LDS,
+// no second dependent LDS read.  (Whatever lies in the stream behind a document is then handed to the loop as it is,
+// not as a table entry: see walk_fused.)
+struct WinEntries {
+  typedef dtk_u16a elem;
+  typedef uint16_t mem;
+  static constexpr uint32_t WIN = DTK_WIN16, ALIGN = 8u, ROW_U16 = DTK_WIN16 + DTK_ROW_PAD16 / 2u, LUT = 0u;
+  static constexpr int OCC = DTK_WALK_OCC16;
+  static __device__ __forceinline__ void fill(elem *row, const mem *__restrict__ from) { win_fill_row<DTK_WIN16 / 8u>(row, from); }
+  static __device__ __forceinline__ uint32_t entry(const uint16_t *, uint32_t e) { return e; }
+};
+// What the build knobs above must keep (a row length or pad given with -D is checked here, not on the device).
+template <typename W>
+struct WinChecked {
+  // rows are filled with whole 16-byte loads and written to LDS as 8-byte words
+  static_assert(W::ALIGN * sizeof(typename W::mem) == 16u, "a row starts at a multiple of 16 bytes of the stream");
+  static_assert(W::WIN >= W::ALIGN && W::WIN % W::ALIGN == 0u, "a row is a whole number of 16-byte loads");
+  static_assert(W::ROW_U16 * 2u >= W::WIN * sizeof(typename W::mem) && (W::ROW_U16 * 2u) % 8u == 0u,
+                "a lane's row in LDS holds WIN elements and starts at a multiple of 8 bytes");
+  // the last row a lane fills starts at or in front of position len + 7 (a raw word's width field reads up to 7), at
+  // most ALIGN - 1 elements further for the alignment: it must end inside the padding behind the batch (walk_fused)
+  static_assert(W::ALIGN - 1u + 7u + W::WIN <= DTK_STREAM_PAD, "a refill behind the batch's last byte stays in d_sym's padding");
+  // the wave's LDS at the bench's 128-byte chunks -- rows, code table, three event bitmaps -- OCC times per SIMD
+  // of a CU with 160 KiB
+  static constexpr uint32_t WAVE_LDS = 64u * W::ROW_U16 * 2u + W::LUT * 2u + 3u * 4u * DTK_LDS_BIT_WORDS(128u);
+  static_assert(4u * (uint32_t)W::OCC * WAVE_LDS <= 160u * 1024u, "OCC waves per SIMD do not fit the CU's LDS");
+  static constexpr bool ok = true;
+};
+static_assert(WinChecked<WinCodes>::ok && WinChecked<WinEntries>::ok, "window formats");
+static_assert(DTK_ROW_PAD16 % 8u == 0u && DTK_ROW_PAD % 8u == 0u, "rows stay 8-byte aligned");
 
 // The walk of matrix.go:348-698 / datok.go:781-1135 for one lane.
 // Returns through `fin`: p == 0xFFFFFFFF means "ran to EOF" (MODE_START: no
@@ -625,13 +691,24 @@ __device__ __forceinline__ void walk_fused(const TRANS &tr, const DtkSym &sym,
   uint32_t budget = cap;  // lookups left; the one that finds none left sets ST_STEP_LIMIT
   fin.p = 0xFFFFFFFFu; fin.t = 0; fin.aux = 0; fin.flags = 0;  // p stays "ran to EOF" unless the lane stops
   bool done = false;
-  // the lane's window of the symbol stream: the CODE of position q at row[q - wb7], q - wb7 in [0, DTK_WIN8); its
-  // entry is lut[code] (the model's code table, in LDS)
-  dtk_u8a *row = reinterpret_cast<dtk_u8a *>(win_row);
-  const uint32_t o7 = (uint32_t)(off & 15u);  // (windows start at multiples of 16 codes: 16-byte loads)
-  const uint8_t *__restrict__ aligned = static_cast<const uint8_t *>(sym.base) + (off - o7);
-#define DTK_ENTRY(q_) ((uint32_t)lut[row[(q_) - wb7]])
-#define DTK_REFILL(q_) { wb7 = (((q_) + o7) & ~15u) - o7; win_fill8(row, aligned + (wb7 + o7)); }
+  // the lane's window of the symbol stream: the element of position q at row[q - wb7], q - wb7 in [0, WIN) -- a CODE,
+  // whose entry is lut[code] (the model's code table, in LDS), or the entry itself (the policy's `window`)
+  // What lies in the stream behind a document: the rotated loop fetches the entry at p_n before the test p >= len, and
+  // behind the batch's last document that is no entry anybody wrote.  A code always names a table entry (width 0..4);
+  // a raw 16-bit word (WinEntries) has any symbol, a width of 0..7 and any class.  It is used for nothing but
+  //   - the request DTK_TAB, which masks the symbol: the 2048 slack cells behind the table (build_images);
+  //   - the position pn_n <= len + 7 of the entry behind it and a refill there: the stream is padded by DTK_STREAM_PAD
+  //     elements (dtk_batch_create), a row ends at most ALIGN - 1 + 7 + WIN elements behind the batch (WinChecked);
+  // and the rare block of the same iteration (p >= len) replaces e and en before the loop reads width, class or hi
+  // from them: eof_drain ends the lane or hands it the bare epsilon symbol, and the block asks again.
+  // A backward refill starts at (q + o7) & ~(ALIGN - 1) >= 0 counted from the aligned start of the document, which
+  // is at or behind the stream's element 0.
+  typedef typename TRANS::window WINF;     // the stream format: WinCodes / WinEntries
+  typename WINF::elem *row = reinterpret_cast<typename WINF::elem *>(win_row);
+  const uint32_t o7 = (uint32_t)(off & (WINF::ALIGN - 1u));  // (windows start at multiples of 16 bytes of the stream: 16-byte loads)
+  const typename WINF::mem *__restrict__ aligned = static_cast<const typename WINF::mem *>(sym.base) + (off - o7);
+#define DTK_ENTRY(q_) ((uint32_t)WINF::entry(lut, row[(q_) - wb7]))
+#define DTK_REFILL(q_) { wb7 = (((q_) + o7) & ~(WINF::ALIGN - 1u)) - o7; WINF::fill(row, aligned + (wb7 + o7)); }
   uint32_t wb7;
   DTK_REFILL(p)
   // The entry the next lookup is made with: the stream entry of the rune at p -- or, right after a backtrack,
@@ -700,7 +777,7 @@ __device__ __forceinline__ void walk_fused(const TRANS &tr, const DtkSym &sym,
   if (!done) {
     x = DTK_TAB(t, e);
     const uint32_t pn0 = p + ((e >> DTK_SYM_W_SHIFT) & 7u);
-    if (pn0 - wb7 >= DTK_WIN8) DTK_REFILL(pn0)
+    if (pn0 - wb7 >= WINF::WIN) DTK_REFILL(pn0)
     en = DTK_ENTRY(pn0);
   }
 #ifdef DTK_PROBE
@@ -742,7 +819,7 @@ __device__ __forceinline__ void walk_fused(const TRANS &tr, const DtkSym &sym,
     {
       const uint32_t pn_n = p_n + ((e_n >> DTK_SYM_W_SHIFT) & 7u);
       uint32_t iw = pn_n - wb7;
-      if (__builtin_amdgcn_ballot_w64(iw >= DTK_WIN8) != 0ull) {  // also a backtrack to before the window
+      if (__builtin_amdgcn_ballot_w64(iw >= WINF::WIN) != 0ull) {  // also a backtrack to before the window
 #ifdef DTK_PROBE
         const unsigned long long r0_ = clock64();
 #endif
@@ -788,7 +865,7 @@ __device__ __forceinline__ void walk_fused(const TRANS &tr, const DtkSym &sym,
     eps_t = he2 ? via : ((backtrack || epsE) ? 0u : eps_t);
     eps_p = he2 ? p_old : eps_p;
     const uint32_t e_cur = e, e_next = en;
-    p = p_n; t = t_n; e = e_n; x = x_n; en = lut[code_n];
+    p = p_n; t = t_n; e = e_n; x = x_n; en = WINF::entry(lut, code_n);
     // everything that happens less than once per token: hard fail, EOT, the first rewind at or behind the end of
     // the chunk (a fused cell's too: the lane then ends BEFORE the cell's rune), the window limit, the lookup cap,
     // the reader at EOF
@@ -858,7 +935,7 @@ __device__ __forceinline__ void walk_fused(const TRANS &tr, const DtkSym &sym,
       if (!done) {  // ask again: state, position or entry may have changed
         x = DTK_TAB(t, e);
         const uint32_t pn2 = p + ((e >> DTK_SYM_W_SHIFT) & 7u);
-        if (pn2 - wb7 >= DTK_WIN8) DTK_REFILL(pn2)
+        if (pn2 - wb7 >= WINF::WIN) DTK_REFILL(pn2)
         en = DTK_ENTRY(pn2);
       }
     }
@@ -933,15 +1010,19 @@ __device__ __forceinline__ void add_steps(unsigned long long *counter, uint32_t 
 }
 
 // the lanes' windows of the symbol stream and, for the lean loop, the model's code table (one wave per block)
-#ifndef DTK_ROW_PAD
-#define DTK_ROW_PAD 0u  // bytes between the lanes' rows of codes.  (8 until round 3, to stagger the banks: without them a wave's LDS is 5728 B at 128-byte chunks and seven waves per SIMD fit a CU; the conflicts of the one-byte reads cost nothing measurable: walk 53.8 -> 51.9 us saturated)
-#endif
+template <typename TRANS, bool LEAN = TRANS::LEAN>
+struct WinOf {  // the general loop: rows of entries, no table
+  static constexpr uint32_t ROW_U16 = DTK_WIN_ROW, LUT = 0u;
+  static constexpr int OCC = 1;
+};
+template <typename TRANS>
+struct WinOf<TRANS, true> : TRANS::window {};
 #define DTK_WINDOWS(TRANS, SYM)                                                                       \
-  constexpr uint32_t WIN_ROW_ = TRANS::LEAN ? (DTK_WIN8 + DTK_ROW_PAD) / 2u : DTK_WIN_ROW;            \
+  constexpr uint32_t WIN_ROW_ = WinOf<TRANS>::ROW_U16;                                                \
   __shared__ uint16_t s_win[WAVE * WIN_ROW_];                                                         \
-  __shared__ uint16_t s_lut[TRANS::LEAN ? 256 : 1];                                                   \
+  __shared__ uint16_t s_lut[WinOf<TRANS>::LUT ? WinOf<TRANS>::LUT : 1];                               \
   uint16_t *win_row = s_win + threadIdx.x * WIN_ROW_;                                                 \
-  if constexpr (TRANS::LEAN) {                                                                        \
+  if constexpr (WinOf<TRANS>::LUT != 0u) {                                                            \
     for (uint32_t i_ = threadIdx.x; i_ < 256u; i_ += WAVE) s_lut[i_] = (SYM).lut[i_];                 \
     __syncthreads();                                                                                  \
   }
@@ -954,18 +1035,22 @@ static int with_trans(const DtkTableDev *tab, bool codes, F &&f) {
       // (da_dense: a double-array tokenizer laid out as a fused matrix -- the table's walk, datok.go's EOT rules)
       auto call = [&](auto t) { if (tab->da_dense) f(t, std::false_type{}); else f(t, std::true_type{}); };
       // the general loop's policy `gen`, or the lean one `lean` where that loop applies
-      auto pick = [&](auto gen, auto lean) {
+      // (a stream of entries: the lean loop unless the model was built to keep the general one, DtkTableDev::lean16)
+      auto pick = [&](auto gen, auto lean, auto lean16) {
         gen.tab = (decltype(gen.tab))tab->tab;
         gen.stride = tab->stride; gen.n_eps = tab->n_eps; gen.start = tab->start; gen.ident_guard = tab->ident_guard;
         if (tab->ident_guard == 0xFFFFFFFFu && codes) {
           static_cast<decltype(gen) &>(lean) = gen;
           call(lean);
+        } else if (tab->ident_guard == 0xFFFFFFFFu && tab->lean16) {
+          static_cast<decltype(gen) &>(lean16) = gen;
+          call(lean16);
         } else {
           call(gen);
         }
       };
-      if (tab->entry_bytes == 8) pick(MatrixFused64Trans{}, MatrixLean64Trans{});  // 64-bit cells (32 767 states and more)
-      else pick(MatrixFusedTrans{}, MatrixLeanTrans{});
+      if (tab->entry_bytes == 8) pick(MatrixFused64Trans{}, MatrixLean64Trans{}, MatrixLean64E16Trans{});  // 64-bit cells (32 767 states and more)
+      else pick(MatrixFusedTrans{}, MatrixLeanTrans{}, MatrixLeanE16Trans{});
     } else if (tab->entry_bytes == 2) {
       MatrixTrans<uint16_t> tr{(const uint16_t *)tab->tab, tab->stride, tab->n_eps, tab->start};
       f(tr, std::true_type{});

@@ -703,7 +703,8 @@ def foma_to_datok(foma_gz: bytes) -> bytes:
 def model_info(gz_bytes: bytes) -> dict:
     """dtk_model_info_mem: what Tokenizer.info would say for this image (.matok, .datok or Foma net) -- kind, states,
     the device table's cell size (`entry_bytes`: 4 fused cells with 15-bit state ids, 8 fused 64-bit cells from 32 767
-    states on), `dense_states`, `stream_codes`, `device_bytes` -- decided exactly as the loader decides it.  Host only:
+    states on), `dense_states`, `stream_codes` (0: the stream holds 16-bit entries), `lean_walk` (1: the lean loop walks
+    it), `device_bytes` -- decided exactly as the loader decides it.  Host only:
     needs no device.  Raises DatokGpuError (E_FORMAT, E_MODEL) for an image the loader would reject."""
     info = ModelInfo()
     check(lib().dtk_model_info_mem(bytes(gz_bytes), len(gz_bytes), C.byref(info)), "model_info")

@@ -397,6 +397,7 @@ inline std::unique_ptr<Tokenizer> LoadTokenizerFile(const std::string &file) {
 
 // Which table and loop a model image (.matok / .datok / Foma net, gzip'd) gets on the device, decided as the loader
 // decides it and without a device (dtk_model_info_mem): false + log line for an image the loader would reject.
+// out->lean_walk says which loop (1: the lean one), out->stream_codes which stream format (0: 16-bit entries).
 inline bool ModelInfo(const void *gz_bytes, size_t n, dtk_model_info *out) {
   const int rc = dtk_model_info_mem(gz_bytes, n, out);
   if (rc != DTK_OK) std::fprintf(stderr, "datok: model image: %s\n", dtk_strerror(rc));

@@ -174,7 +174,12 @@ typedef struct {
   uint32_t dense_states; /* double array only: its states, if its transitions were laid out as a matrix on the
                           * device at load (entry_bytes is then 4 or 8, see there); 0: the {base, check} pairs are walked */
   uint32_t stream_codes; /* distinct symbol-stream entries of the model if they fit a byte (the stream is then one
-                          * code per input byte and the lean loop may apply); 0: 16-bit entries, general loop */
+                          * code per input byte); 0: more than 255 of them, the stream holds the 16-bit entries
+                          * themselves.  The format of the stream only: which loop walks it is lean_walk */
+  uint32_t lean_walk;    /* 1: dtk_batch_run walks this model with the lean loop -- fused cells (entry_bytes 4 or 8 of a
+                          * matrix, or of a double array with dense_states != 0) and unknown_used == 0, over codes or
+                          * over 16-bit entries alike; 0: the general loop, at about half the walk rate (an arc on
+                          * `unknown`, plain cells, a double array walked as pairs, the test hook GENERAL16) */
 } dtk_model_info;
 int dtk_model_get_info(const dtk_model *m, dtk_model_info *out);
 /* The same answer for an image that is not loaded: parses gz_bytes and decides the device layout exactly as

@@ -471,7 +471,7 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
     // round trip.  (Not done blindly: ten empty launches cost a clean corpus some 15 us per batch.)
     b->dev_rounds = g_dbg.dev_rounds >= 0 ? (uint32_t)g_dbg.dev_rounds : (b->expect_repairs ? 2u : 0u);
     if (b->dev_rounds > 3u) b->dev_rounds = 3u;
-    fix_in_scan = b->n_docs <= 8192u && b->dev_rounds == 0;  // k_spec_fix's step rides in the one-block scan kernel
+    fix_in_scan = b->n_docs <= DTK_SCAN_TILES_MAX_DOCS && b->dev_rounds == 0;  // k_spec_fix's step rides in the one-launch scan
 #define SPEC(stage)                                                                               \
   do {                                                                                            \
     if (dtk_launch_spec(&m->tab, &w, &sp, stage, cmp_mask_of(m), b->d_redo, nb, s))               \

@@ -858,85 +858,95 @@ __global__ __launch_bounds__(WAVE) void k_seg_scan(DtkCompactArgs A, const uint3
 
 // ------------------------------------------------------- exclusive scan (x3)
 //
-// Turns the per-document counts into CSR row offsets (totals at [n_docs]) and
-// counts flagged documents.  One 1024-thread block; each thread
-// owns a contiguous slice, a block-level scan links the slices.
+// Turns the per-document counts into CSR row offsets (totals at [n_docs]) and counts flagged documents.
 
-// One block: per-document counts -> CSR offsets (three arrays) + the number of flagged documents.
-// Each thread adds up a few consecutive documents, the 16 waves scan with shuffles, one barrier
-// links them.  With `fix` set it also does k_spec_fix's per-document step (one launch less on the
-// batch's critical path).
-#define SCAN1_TB 1024u
-__global__ __launch_bounds__(SCAN1_TB) void k_scan3(const uint64_t *ca, const uint64_t *cb, const uint64_t *cc,
-                                                uint64_t *a, uint64_t *b, uint64_t *c, uint32_t n,
-                                                uint64_t *totals, const uint32_t *status, DtkSpecArgs S,
-                                                uint32_t *redo_out, uint32_t *n_bad, int fix, const uint32_t *skip_if) {
-  if (skip_if && *skip_if != 0u) return;
-  __shared__ uint64_t wsum[3][SCAN1_TB / WAVE];
-  __shared__ uint32_t wfl[SCAN1_TB / WAVE];
-  const uint32_t T = blockDim.x, tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
-  const uint32_t per = (n + T - 1) / T;
-  const uint32_t lo = tid * per < n ? tid * per : n;
-  const uint32_t hi = lo + per < n ? lo + per : n;
-  uint64_t sa = 0, sb = 0, sc = 0;
-  uint32_t fl = 0;
-  // four documents at a time: their loads first, one wait -- a loop of dependent round trips was most of this kernel's
-  // 15 us.  (Not all eight of a thread in registers: a 1024-thread block with 100 VGPRs per lane has to wait for a
-  // whole CU to drain while other batches' walks fill the chip -- three batches in flight lost 10 %.)
-  constexpr uint32_t G = 4u;
-  for (uint32_t i0 = lo; i0 < hi; i0 += G) {
-    uint64_t va[G], vb[G], vc[G];
-    uint32_t vs[G], vf[G];
-#pragma unroll
-    for (uint32_t j = 0; j < G; j++) {
-      const uint32_t i = i0 + j;
-      const bool ok = i < hi;
-      va[j] = ok ? ca[i] : 0ull; vb[j] = ok ? cb[i] : 0ull; vc[j] = ok ? cc[i] : 0ull;
-      vs[j] = ok ? status[i] : 0u;
-      vf[j] = (ok && fix) ? S.fail_lane[i] : 0u;
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < G; j++) {
-      sa += va[j]; sb += vb[j]; sc += vc[j]; fl += vs[j] != 0u;
-      if (fix && i0 + j < hi) {
-        const uint32_t bad = ~vf[j];
-        if (bad == 0xFFFFFFFFu) redo_out[i0 + j] = 0xFFFFFFFFu; else mark_redo(S, i0 + j, bad, redo_out, n_bad);
-      }
-    }
-  }
-  uint64_t xa = sa, xb = sb, xc = sc;
-  uint32_t xf = fl;
-#pragma unroll
-  for (int o = 1; o < WAVE; o <<= 1) {
-    const uint64_t ya = __shfl_up(xa, o), yb = __shfl_up(xb, o), yc = __shfl_up(xc, o);
-    const uint32_t yf = __shfl_up(xf, o);
-    if ((int)lane >= o) { xa += ya; xb += yb; xc += yc; xf += yf; }
-  }
-  if (lane == WAVE - 1) { wsum[0][wid] = xa; wsum[1][wid] = xb; wsum[2][wid] = xc; wfl[wid] = xf; }
+#define SCAN_TB 256u
+
+// exclusive prefix sum of one 64-bit value per thread over a block of SCAN_TB threads; total = the block's sum.
+// sh: one word per wave (a second call may reuse it at once)
+__device__ __forceinline__ uint64_t scan_block_excl(uint64_t v, uint64_t *sh, uint64_t &total) {
+  const uint32_t lane = lane_id(), wid = threadIdx.x >> 6;
+  const uint64_t x = wave_incl_scan64(v);
+  if (lane == WAVE - 1) sh[wid] = x;
   __syncthreads();
-  uint64_t ba = 0, bb = 0, bc = 0;
-  uint32_t bf = 0;
-  for (uint32_t w = 0; w < wid; w++) { ba += wsum[0][w]; bb += wsum[1][w]; bc += wsum[2][w]; bf += wfl[w]; }
-  uint64_t ra = ba + xa - sa, rb = bb + xb - sb, rc = bc + xc - sc;
-  for (uint32_t i0 = lo; i0 < hi; i0 += G) {
-    uint64_t va[G], vb[G], vc[G];
+  uint64_t base = 0, tot = 0;
 #pragma unroll
-    for (uint32_t j = 0; j < G; j++) {
-      const uint32_t i = i0 + j;
-      const bool ok = i < hi;
-      va[j] = ok ? ca[i] : 0ull; vb[j] = ok ? cb[i] : 0ull; vc[j] = ok ? cc[i] : 0ull;
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < G; j++) {
-      const uint32_t i = i0 + j;
-      if (i < hi) { a[i] = ra; b[i] = rb; c[i] = rc; }
-      ra += va[j]; rb += vb[j]; rc += vc[j];
-    }
+  for (uint32_t w = 0; w < SCAN_TB / WAVE; w++) {
+    const uint64_t s = sh[w];
+    if (w < wid) base += s;
+    tot += s;
   }
-  if (tid == T - 1) {
+  __syncthreads();
+  total = tot;
+  return base + x - v;
+}
+
+// Up to DTK_SCAN_TILES_MAX_DOCS documents, one launch: tile t (a block of 256 threads, one wave slot per SIMD: it
+// finds a place while other batches' walks fill the chip) owns documents [256 t, 256 t + 256), one per thread, and
+// adds up the counts of all tiles below it itself -- coalesced loads from L2, 90 KB for the last of 16 tiles.  No tile
+// waits for another.  The last tile also counts the flagged documents below it and writes the totals.
+// With `fix` set a thread also does k_spec_fix's step for its document (one launch less on the batch's critical
+// path).  That step counts the broken documents in *n_bad, the very word `skip_if` points at then (it is zero before
+// the launch: nothing else counts there), so with `fix` the kernel does not look at it: a tile that started late
+// would take another tile's count for a reason to leave its documents alone.
+__global__ __launch_bounds__(SCAN_TB) void k_scan3_tiles(const uint64_t *ca, const uint64_t *cb, const uint64_t *cc,
+                                                         uint64_t *a, uint64_t *b, uint64_t *c, uint32_t n,
+                                                         uint64_t *totals, const uint32_t *status, DtkSpecArgs S,
+                                                         uint32_t *redo_out, uint32_t *n_bad, int fix,
+                                                         const uint32_t *skip_if) {
+  if (!fix && skip_if && *skip_if != 0u) return;
+  constexpr uint32_t NW = SCAN_TB / WAVE;
+  __shared__ uint64_t wsum[2][3][NW];  // per wave: [0] its share of the tiles below, [1] its own documents
+  __shared__ uint32_t wfl[2][NW];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
+  const uint32_t below = blockIdx.x * SCAN_TB, i = below + tid;
+  const bool last = blockIdx.x == gridDim.x - 1, in = i < n;
+  // the thread's own document first: these loads are under way while the loop below runs
+  const uint64_t ma = in ? ca[i] : 0ull, mb = in ? cb[i] : 0ull, mc = in ? cc[i] : 0ull;
+  const uint32_t ms = in ? status[i] : 0u;
+  const uint32_t mf = (in && fix) ? S.fail_lane[i] : 0u;
+  // the tiles below, eight rows of 256 documents per round trip (four rows: 13.7 instead of 13.0 us per launch with
+  // three batches in flight; sixteen: 14.3)
+  uint64_t pa = 0, pb = 0, pc = 0;
+  uint32_t pf = 0;
+  constexpr uint32_t G = 8u;
+  for (uint32_t j0 = tid; j0 < below; j0 += G * SCAN_TB) {
+    uint64_t va[G], vb[G], vc[G];
+    uint32_t vs[G];
+#pragma unroll
+    for (uint32_t q = 0; q < G; q++) {
+      const uint32_t j = j0 + q * SCAN_TB;
+      const bool ok = j < below;
+      va[q] = ok ? ca[j] : 0ull; vb[q] = ok ? cb[j] : 0ull; vc[q] = ok ? cc[j] : 0ull;
+      vs[q] = (ok && last) ? status[j] : 0u;
+    }
+#pragma unroll
+    for (uint32_t q = 0; q < G; q++) { pa += va[q]; pb += vb[q]; pc += vc[q]; pf += vs[q] != 0u; }
+  }
+  const uint64_t xa = wave_incl_scan64(ma), xb = wave_incl_scan64(mb), xc = wave_incl_scan64(mc);
+  const uint64_t ya = wave_incl_scan64(pa), yb = wave_incl_scan64(pb), yc = wave_incl_scan64(pc);
+  const uint32_t xf = popc(__ballot(ms != 0u)), yf = wave_sum(pf);
+  if (lane == WAVE - 1) {
+    wsum[0][0][wid] = ya; wsum[0][1][wid] = yb; wsum[0][2][wid] = yc; wfl[0][wid] = yf;
+    wsum[1][0][wid] = xa; wsum[1][1][wid] = xb; wsum[1][2][wid] = xc; wfl[1][wid] = xf;
+  }
+  __syncthreads();
+  uint64_t ba = 0, bb = 0, bc = 0;  // the tiles below + the tile's lower waves
+  uint32_t bf = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < NW; w++) {
+    ba += wsum[0][0][w]; bb += wsum[0][1][w]; bc += wsum[0][2][w]; bf += wfl[0][w] + wfl[1][w];
+    if (w < wid) { ba += wsum[1][0][w]; bb += wsum[1][1][w]; bc += wsum[1][2][w]; }
+  }
+  if (in) { a[i] = ba + xa - ma; b[i] = bb + xb - mb; c[i] = bc + xc - mc; }
+  if (last && tid == SCAN_TB - 1u) {  // (documents at n and behind count zero: this thread's sums are the batch's)
     a[n] = ba + xa; b[n] = bb + xb; c[n] = bc + xc;
     totals[0] = ba + xa; totals[1] = bb + xb; totals[2] = bc + xc;  // DtkTotalsDev: n_tok, n_sent, n_text,
-    totals[3] = bf + xf;                                            // n_flagged (its first four words, asserted there)
+    totals[3] = bf;                                                 // n_flagged (its first four words, asserted there)
+  }
+  if (fix && in) {
+    const uint32_t bad = ~mf;
+    if (bad == 0xFFFFFFFFu) redo_out[i] = 0xFFFFFFFFu; else mark_redo(S, i, bad, redo_out, n_bad);
   }
 }
 
@@ -1091,30 +1101,13 @@ extern "C" int dtk_launch_seg_prepare(const DtkCompactArgs *args, const uint32_t
 }
 
 // Many documents: the same scan in three launches (tile sums, scan of the sums, tiles).
-#define SCAN_TB 256u
 #define SCAN_PER 8u
 #define SCAN_TILE (SCAN_TB * SCAN_PER)
-
-__device__ __forceinline__ uint64_t scan_block_excl(uint64_t v, uint64_t *sh, uint64_t &total) {
-  const uint32_t tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (uint32_t o = 1; o < SCAN_TB; o <<= 1) {
-    const uint64_t x = tid >= o ? sh[tid - o] : 0;
-    __syncthreads();
-    sh[tid] += x;
-    __syncthreads();
-  }
-  total = sh[SCAN_TB - 1];
-  const uint64_t ex = sh[tid] - v;
-  __syncthreads();
-  return ex;
-}
 
 __global__ __launch_bounds__(SCAN_TB) void k_scan3_sums(const uint64_t *ca, const uint64_t *cb, const uint64_t *cc,
                                                         const uint32_t *status, uint32_t n, uint64_t *ws, const uint32_t *skip_if) {
   if (skip_if && *skip_if != 0u) return;
-  __shared__ uint64_t sh[SCAN_TB];
+  __shared__ uint64_t sh[SCAN_TB / WAVE];
   const uint32_t i0 = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_PER;
   uint64_t s[4] = {0, 0, 0, 0};
   for (uint32_t i = i0; i < i0 + SCAN_PER && i < n; i++) { s[0] += ca[i]; s[1] += cb[i]; s[2] += cc[i]; s[3] += status[i] != 0; }
@@ -1128,7 +1121,7 @@ __global__ __launch_bounds__(SCAN_TB) void k_scan3_sums(const uint64_t *ca, cons
 __global__ __launch_bounds__(SCAN_TB) void k_scan3_mid(uint64_t *ws, uint32_t nb, uint64_t *a, uint64_t *b, uint64_t *c,
                                                        uint32_t n, uint64_t *totals, const uint32_t *skip_if) {
   if (skip_if && *skip_if != 0u) return;
-  __shared__ uint64_t sh[SCAN_TB];
+  __shared__ uint64_t sh[SCAN_TB / WAVE];
   const uint32_t tid = threadIdx.x;
   const uint32_t per = (nb + SCAN_TB - 1) / SCAN_TB;
   const uint32_t lo = min(tid * per, nb), hi = min(lo + per, nb);
@@ -1151,7 +1144,7 @@ __global__ __launch_bounds__(SCAN_TB) void k_scan3_apply(const uint64_t *ca, con
                                                          uint64_t *a, uint64_t *b, uint64_t *c, uint32_t n,
                                                          const uint64_t *ws, const uint32_t *skip_if) {
   if (skip_if && *skip_if != 0u) return;
-  __shared__ uint64_t sh[SCAN_TB];
+  __shared__ uint64_t sh[SCAN_TB / WAVE];
   const uint32_t i0 = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_PER;
   const uint64_t *src[3] = {ca, cb, cc};
   uint64_t *dst[3] = {a, b, c};
@@ -1167,17 +1160,16 @@ __global__ __launch_bounds__(SCAN_TB) void k_scan3_apply(const uint64_t *ca, con
   }
 }
 
-// fix_spec != nullptr: also k_spec_fix's per-document step (only done in the one-block case: returns 1 if it was)
+// fix_spec != nullptr: also k_spec_fix's per-document step (only done in the one-launch case: -1 otherwise)
 extern "C" int dtk_launch_scan3(const uint64_t *ca, const uint64_t *cb, const uint64_t *cc, uint64_t *a,
                                 uint64_t *b, uint64_t *c, uint32_t n_docs, uint64_t *totals,
                                 const uint32_t *status, uint64_t *ws, const DtkSpecArgs *fix_spec,
                                 uint32_t *redo_out, uint32_t *n_bad, const uint32_t *skip_if, void *stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (n_docs <= 8192u || !ws) {
+  if (n_docs <= DTK_SCAN_TILES_MAX_DOCS || !ws) {
     DtkSpecArgs none{};
-    // 1024 threads: the kernel's time is the threads' serial loops over their documents (512: 23 instead of 16 us
-    // for 4096 documents, 256: 32 us)
-    hipLaunchKernelGGL(k_scan3, dim3(1), dim3(SCAN1_TB), 0, s, ca, cb, cc, a, b, c, n_docs, totals, status,
+    const uint32_t tiles = n_docs ? (n_docs + SCAN_TB - 1u) / SCAN_TB : 1u;  // (no documents: the totals all the same)
+    hipLaunchKernelGGL(k_scan3_tiles, dim3(tiles), dim3(SCAN_TB), 0, s, ca, cb, cc, a, b, c, n_docs, totals, status,
                        fix_spec ? *fix_spec : none, redo_out, n_bad, fix_spec ? 1 : 0, skip_if);
   } else {
     if (fix_spec) return -1;  // the caller runs k_spec_fix itself for that many documents

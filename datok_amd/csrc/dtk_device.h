@@ -1,5 +1,5 @@
 // dtk_device.h -- what the kernel units share: wave helpers, the windows macro of the walk kernels, the per-document
-// repair step (used by the verification's fix kernel and by the one-block scan).
+// repair step (used by the verification's fix kernel and by the one-launch scan).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,6 +33,19 @@ __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t &total) 
   x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false); // row_bcast:31 -> rows 2, 3
   total = (uint32_t)__builtin_amdgcn_readlane((int)x, WAVE - 1);
   return x - v;
+}
+
+// inclusive prefix sum of a 64-bit value over the 64 lanes (lane 63 holds the wave's sum): the scan kernels' row
+// offsets, a few calls per wave -- a shuffle ladder, the DPP forms move 32 bits
+__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v) {
+  const uint32_t lane = lane_id();
+  uint64_t x = v;
+#pragma unroll
+  for (uint32_t o = 1; o < WAVE; o <<= 1) {
+    const uint64_t y = __shfl_up(x, o);
+    if (lane >= o) x += y;
+  }
+  return x;
 }
 
 // minimum / maximum over the 64 lanes, the same DPP ladder: a lane without a source keeps its own value (`old` is the

@@ -125,7 +125,7 @@ enum { DTK_KIND_MATRIX = 0, DTK_KIND_DA = 1 };
 
 // The totals block at the head of a batch's accumulators, with its page-locked mirror on the host.
 struct DtkTotalsDev {
-  uint64_t n_tok, n_sent, n_text, n_flagged;  // k_scan3: tokens, sentence ints, texts, documents with a status
+  uint64_t n_tok, n_sent, n_text, n_flagged;  // the scan: tokens, sentence ints, texts, documents with a status
   uint64_t unused_4[2];
   uint64_t invalid_epoch;              // k_symbolize: number of the last run that saw an invalid UTF-8 byte
   uint32_t any_irregular, any_eot;     // the compaction: some document is ST_IRREGULAR / is left to k_compact_eot
@@ -135,7 +135,7 @@ struct DtkTotalsDev {
   uint64_t unused_12[4];
 };
 static_assert(sizeof(struct DtkTotalsDev) == DTK_TOTALS_BYTES - DTK_STEP_STRIPES * 128u, "the block is 128 bytes");
-// k_scan3 writes totals[0..3]; k_compact*, k_to_host read totals[0..2]
+// the scan (k_scan3_tiles / k_scan3_mid) writes totals[0..3]; k_compact*, k_to_host read totals[0..2]
 static_assert(offsetof(struct DtkTotalsDev, n_tok) == 0 && offsetof(struct DtkTotalsDev, n_sent) == 8 &&
               offsetof(struct DtkTotalsDev, n_text) == 16 && offsetof(struct DtkTotalsDev, n_flagged) == 24,
               "the scan's four totals are the first four words");
@@ -420,6 +420,20 @@ int dtk_launch_seg_prepare(const struct DtkCompactArgs *args, const uint32_t *do
 int dtk_launch_render(const struct DtkRenderArgs *args, int stage, void *stream);
 uint32_t dtk_render_tiles(uint64_t n);
 int dtk_launch_clear2(void *a, uint64_t a_bytes, void *b, uint64_t b_bytes, void *stream);
+// Up to this many documents the row offsets come from one launch of independent 256-document tiles (k_scan3_tiles,
+// which can also do k_spec_fix's per-document step); above it from three launches.  Every tile adds up the counts
+// of all tiles below it, so the reads grow with the square of the document count.  The scan stage of one batch alone
+// (stage events, 64-byte documents, median of 40 runs, us; in brackets scan + fix stages: the three-launch path needs
+// k_spec_fix's launch beside it, and an empty stage still measures 5.2), tiles against three launches:
+//    8 192 documents  16.7 (21.8)  against  19.5 (26.1)
+//   16 384            25.9 (31.1)           19.6 (26.2)
+//   32 768            44.5 (49.7)           20.2 (26.8)
+//   65 536            83.8 (89.0)           20.1 (26.7)
+// The crossover lies between the first two sizes (near 12 000 documents by a straight line between them): the limit
+// stays at the largest size measured at which the tiles win.
+#ifndef DTK_SCAN_TILES_MAX_DOCS
+#define DTK_SCAN_TILES_MAX_DOCS 8192u
+#endif
 int dtk_launch_scan3(const uint64_t *ca, const uint64_t *cb, const uint64_t *cc, uint64_t *a, uint64_t *b,
                      uint64_t *c, uint32_t n_docs, uint64_t *totals, const uint32_t *status, uint64_t *ws,
                      const struct DtkSpecArgs *fix_spec, uint32_t *redo_out, uint32_t *n_bad, const uint32_t *skip_if,

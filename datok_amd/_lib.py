@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("DATOK_GPU_LIB") or os.path.join(_HERE, "libdatok_gpu.
 
 # error codes / flags (datok_gpu.h)
 OK, E_IO, E_FORMAT, E_NO_DEVICE, E_HIP, E_ARG, E_MODEL, E_CAPACITY, E_STATE, E_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7, -8, -9
+E_IRREGULAR = -10
 ST_WINDOW_OVERFLOW, ST_EMPTY_TEXT, ST_BAD_MODEL, ST_IRREGULAR, ST_STEP_LIMIT, ST_INTERNAL = 1, 2, 4, 8, 16, 32
 ST_BAD_OFFSET = 64
 
@@ -32,6 +33,8 @@ EXPORTS = [
     "dtk_batch_set_download_stream", "dtk_batch_download_stream", "dtk_batch_done", "dtk_batch_set_streams",
     "dtk_debug_configure", "dtk_batch_debug_stream", "dtk_blk_start", "dtk_blk_end",
     "dtk_multi_create", "dtk_multi_free", "dtk_multi_type", "dtk_multi_set_result_fields", "dtk_multi_set_chunking", "dtk_multi_run",
+    "dtk_stream_create", "dtk_stream_free", "dtk_stream_set_chunking", "dtk_stream_set_result_fields", "dtk_stream_run",
+    "dtk_stream_transduce",
 ]
 
 
@@ -66,6 +69,16 @@ class ResultView(C.Structure):
 
 
 SLICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)
+
+
+class StreamSlice(C.Structure):
+    """dtk_stream_slice: one slice of dtk_stream_run (positions relative to the window, whose byte 0 is stream byte base)."""
+    _fields_ = [("base", C.c_uint64), ("first", C.c_uint32), ("cut", C.c_uint32), ("len", C.c_uint32),
+                ("last", C.c_uint32), ("status", C.c_uint32), ("text", C.c_void_p), ("view", ResultView)]
+
+
+READ_FN = C.CFUNCTYPE(C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t)
+STREAM_SLICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(StreamSlice))
 
 
 class RenderView(C.Structure):
@@ -171,6 +184,13 @@ def lib():
     L.dtk_multi_set_result_fields.argtypes = [vp, u32]
     L.dtk_multi_set_chunking.argtypes = [vp, u32, u32]
     L.dtk_multi_run.argtypes = [vp, vp, vp, u32, u32, SLICE_FN, vp]
+    L.dtk_stream_create.argtypes = [u64, u32, C.POINTER(vp)]
+    L.dtk_stream_free.argtypes = [vp]
+    L.dtk_stream_free.restype = None
+    L.dtk_stream_set_chunking.argtypes = [vp, u32, u32]
+    L.dtk_stream_set_result_fields.argtypes = [vp, u32]
+    L.dtk_stream_run.argtypes = [vp, vp, READ_FN, vp, u32, STREAM_SLICE_FN, vp, C.POINTER(u32)]
+    L.dtk_stream_transduce.argtypes = [vp, vp, READ_FN, vp, u32, C.POINTER(vp), C.POINTER(sz), C.POINTER(u32)]
     for f in (L.dtk_blk_start, L.dtk_blk_end):
         f.argtypes, f.restype = [vp, vp, u64], C.c_int32
     L.dtk_pinned_alloc.restype = vp

@@ -1,18 +1,21 @@
 // datok_cli.cpp -- the reference's command line (cmd/datok.go:18-134) over the C-ABI.
 //
 //   datok tokenize -t <tokenizer> [--[no-]tokens] [--[no-]sentences] [-p|--token-positions]
-//                  [--sentence-positions] [--newline-after-eot] <file | ->
+//                  [--sentence-positions] [--newline-after-eot] [--slice-bytes N] <file | ->
 //   datok convert  -i <foma.fst> -o <tokenizer> [-d]
 //
-// `tokenize` walks and renders on the GPU (dtk_transduce); the input stream is one document,
-// U+0004 ends a text inside it.  `convert` is host only; -d: the double array (ToDoubleArray, datok.go:82-238).
+// `tokenize` reads its input as ONE stream of any length (cmd/datok.go:120-133), U+0004 ends a text inside it: the
+// stream is read and walked on the GPU in slices of --slice-bytes (default 16 MiB, a multiple of 256 from 16 384 on;
+// dtk_stream_run: the input is never held whole) and every slice is replayed into the one NewTokenWriter on standard
+// output as it comes home.  `convert` is host only; -d: the double array (ToDoubleArray, datok.go:82-238).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iostream>
 #include <string>
 #include <vector>
 
-#include "../../include/datok_gpu.h"
+#include "../../include/datok.hpp"
 
 static int usage(const char *msg) {
   if (msg) std::fprintf(stderr, "datok: error: %s\n", msg);
@@ -20,7 +23,8 @@ static int usage(const char *msg) {
                "Usage: datok <command>\n\nFSA based tokenizer\n\nCommands:\n"
                "  convert --foma=STRING --tokenizer=STRING\n"
                "    Convert a compiled foma FST file to a Matrix or Double Array tokenizer\n\n"
-               "  tokenize --tokenizer=STRING <input>\n    Tokenize a text\n");
+               "  tokenize --tokenizer=STRING [--slice-bytes=N] <input>\n    Tokenize a text (a file, or - for STDIN), read as one\n"
+               "    stream in slices of N bytes (default 16777216; a multiple of 256, at least 16384)\n");
   return 1;
 }
 
@@ -80,11 +84,18 @@ static int cmd_convert(int argc, char **argv) {
 }
 
 static int cmd_tokenize(int argc, char **argv) {
-  std::string tok, input;
+  std::string tok, input, slice_arg;
+  uint64_t slice_bytes = 16u << 20;
   bool tokens = true, sentences = true, tpos = false, spos = false, nl = false, have_input = false;
   for (int i = 2; i < argc; i++) {
     const std::string a = argv[i];
     if (opt_value(argc, argv, i, "tokenizer", 't', tok)) continue;
+    if (a.rfind("--slice-bytes", 0) == 0 && opt_value(argc, argv, i, "slice-bytes", '\0', slice_arg)) {
+      char *end = nullptr;
+      slice_bytes = std::strtoull(slice_arg.c_str(), &end, 10);
+      if (slice_arg.empty() || *end) return usage("--slice-bytes expects a number");
+      continue;
+    }
     if (a == "--tokens") tokens = true;
     else if (a == "--no-tokens") tokens = false;
     else if (a == "--sentences") sentences = true;
@@ -112,25 +123,44 @@ static int cmd_tokenize(int argc, char **argv) {
   if (sentences) flags |= DTK_SENTENCES;
   if (spos) flags |= DTK_SENTENCE_POS;
   if (nl) flags |= DTK_NEWLINE_AFTER_EOT;
-  std::vector<uint8_t> text;
   FILE *f = input == "-" ? stdin : std::fopen(input.c_str(), "rb");
-  if (!f || !read_all(f, text)) {
+  if (!f) {
     std::perror(input.c_str());
     dtk_model_free(m);
     return 1;
   }
-  if (f != stdin) std::fclose(f);
-  char *out = nullptr;
-  size_t n = 0;
+  dtk_stream *st = nullptr;
+  rc = dtk_stream_create(slice_bytes, 3, &st);
   uint32_t status = 0;
-  rc = dtk_transduce(m, text.data(), text.size(), flags, &out, &n, &status);
+  bool read_failed = false;
+  if (rc == DTK_OK) {
+    struct Ctx { FILE *f; datok::TokenWriter *w; bool is_matrix, *read_failed; };
+    auto tw = datok::NewTokenWriter(std::cout, (datok::Bits)flags);
+    Ctx c{f, tw.get(), std::strcmp(dtk_model_type(m), "MATOK") == 0, &read_failed};
+    auto rd = [](void *u, uint8_t *buf, size_t cap) -> size_t {
+      Ctx *c = static_cast<Ctx *>(u);
+      const size_t k = std::fread(buf, 1, cap, c->f);
+      if (k == 0 && std::ferror(c->f)) *c->read_failed = true;
+      return k;
+    };
+    auto on_slice = [](void *u, const dtk_stream_slice *sl) -> int {
+      Ctx *c = static_cast<Ctx *>(u);
+      datok::detail::replay_list(c->is_matrix, sl->text, sl->len, sl->view, 0, *c->w, sl->first, sl->last != 0);
+      return DTK_OK;
+    };
+    rc = dtk_stream_run(st, m, rd, &c, 0, on_slice, &c, &status);
+    tw->Flush();
+  }
+  dtk_stream_free(st);
+  if (f != stdin) std::fclose(f);
   dtk_model_free(m);
+  if (read_failed) { std::perror(input.c_str()); return 1; }
   if (rc != DTK_OK) {
-    std::fprintf(stderr, "datok: %s %s\n", dtk_strerror(rc), dtk_last_hip_error());
+    std::fprintf(stderr, "datok: %s %s\n", dtk_strerror(rc), rc == DTK_E_HIP ? dtk_last_hip_error() : "");
     return 1;
   }
-  std::fwrite(out, 1, n, stdout);
-  dtk_free(out);
+  // an empty text only breaks the position modes (token_writer.go:108,135,145)
+  if (!(flags & (DTK_TOKEN_POS | DTK_SENTENCE_POS))) status &= ~(uint32_t)DTK_ST_EMPTY_TEXT;
   if (status) {  // the reference panics here (1024-rune window, positions of a text without tokens)
     std::fprintf(stderr, "datok: input outside the reference's contract (status %u)\n", status);
     return 2;

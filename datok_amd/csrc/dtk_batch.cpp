@@ -323,7 +323,43 @@ DtkWalkArgs walk_args(dtk_batch *b) {
   w.tok_cnt = b->d_tok_cnt; w.sent_cnt = b->d_sent_cnt; w.text_cnt = b->d_text_cnt;
   w.steps = (unsigned long long *)dtk_step_stripe(b->d_totals, 0);
   w.step_factor = 2048;  // look-ahead is bounded by the 1024-rune window (matrix.go:365)
+  w.init_rec = b->has_carry ? b->d_init_rec.p : nullptr;  // a slice of a stream (batch_set_slice)
+  w.open_stop = b->open_slice; w.open_fin = b->d_open_fin;
   return w;
+}
+
+// ---- a slice of one long stream (dtk_streamer.cpp)
+int batch_set_slice(dtk_batch *b, uint32_t open_slice, const DtkLaneState *carry) {
+  int rc;
+  if ((open_slice || carry) && !b->h_init_rec.p) {
+    if ((rc = b->d_init_rec.fit(1, 1)) || (rc = b->d_open_fin.fit(1, 1)) ||
+        (rc = b->h_init_rec.fit(sizeof(DtkLaneState), sizeof(DtkLaneState))))
+      return rc;
+  }
+  // (called between runs: the last run, which copied the record from h_init_rec, has been finished by its results' reader)
+  b->open_slice = open_slice;
+  b->has_carry = carry != nullptr;
+  if (carry) *b->h_init_rec.as<DtkLaneState>() = *carry;
+  return DTK_OK;
+}
+
+static int launch_stream_cut(dtk_batch *b, const uint32_t *skip_if) {
+  DtkStreamCutArgs x{};
+  x.slice = b->open_slice; x.init_rec = b->has_carry ? b->d_init_rec.p : nullptr;
+  x.chunk = b->chunk; x.n_lanes = b->n_lanes;
+  x.lane_start = b->d_lane_start; x.lane_cnt = b->d_lane_cnt; x.open_fin = b->d_open_fin;
+  x.bits = b->d_bits; x.bit_words = b->bit_words; x.doc_tail = b->d_doc_tail; x.status = b->d_status;
+  x.tok_cnt = b->d_tok_cnt; x.sent_cnt = b->d_sent_cnt; x.text_cnt = b->d_text_cnt;
+  x.skip_if = skip_if; x.out = &b->d_totals->cut;
+  if (dtk_launch_stream_cut(&x, b->stream)) return hip_fail(hipGetLastError(), "stream cut");
+  return DTK_OK;
+}
+
+int batch_cut(dtk_batch *b, DtkStreamCut *out) {
+  const int rc = finish(b);
+  if (rc != DTK_OK) return rc;
+  *out = b->h_totals->cut;
+  return DTK_OK;
 }
 
 static DtkSpecArgs spec_args(dtk_batch *b, bool redo) {
@@ -398,6 +434,9 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
   if (!m || !b) return DTK_E_ARG;
   if (b->n_docs == 0 || !b->d_off) return DTK_E_STATE;
   if (m->device != b->device) return DTK_E_ARG;
+  // a slice of a stream is one document, and an open end has bytes behind it
+  const bool slice = b->open_slice != 0 || b->has_carry;
+  if (slice && (b->n_docs != 1 || b->total <= b->open_slice)) return DTK_E_ARG;
   int prc = plan_lanes(b);
   if (prc != DTK_OK) return prc;
   if (b->dl_begun && !b->dl_waited) { HIP_TRY(hipEventSynchronize(b->ev_dl)); b->dl_waited = true; }  // (the last run's results on their way out)
@@ -452,6 +491,8 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
                            ++b->epoch, s))
     return hip_fail(hipGetLastError(), "symbolize");
   STAGE(2);
+  if (b->has_carry)
+    HIP_TRY(hipMemcpyAsync(b->d_init_rec, b->h_init_rec.p, sizeof(DtkLaneState), hipMemcpyHostToDevice, s));
   DtkWalkArgs w = walk_args(b);
   bool fix_in_scan = false;
   DtkSpecArgs sp_first{};
@@ -471,7 +512,9 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
     // round trip.  (Not done blindly: ten empty launches cost a clean corpus some 15 us per batch.)
     b->dev_rounds = g_dbg.dev_rounds >= 0 ? (uint32_t)g_dbg.dev_rounds : (b->expect_repairs ? 2u : 0u);
     if (b->dev_rounds > 3u) b->dev_rounds = 3u;
-    fix_in_scan = b->n_docs <= DTK_SCAN_TILES_MAX_DOCS && b->dev_rounds == 0;  // k_spec_fix's step rides in the one-launch scan
+    // k_spec_fix's step rides in the one-launch scan (not for a slice of a stream: k_stream_cut, in front of the scan,
+    // has to know whether the document is broken)
+    fix_in_scan = b->n_docs <= DTK_SCAN_TILES_MAX_DOCS && b->dev_rounds == 0 && !slice;
 #define SPEC(stage)                                                                               \
   do {                                                                                            \
     if (dtk_launch_spec(&m->tab, &w, &sp, stage, cmp_mask_of(m), b->d_redo, nb, s))               \
@@ -498,6 +541,10 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
   c.bits = b->d_bits; c.bit_words = b->bit_words; c.doc_tail = b->d_doc_tail; c.status = b->d_status;
   c.flags = flags & DTK_NEWLINE_AFTER_EOT; c.kind = m->kind;
   c.totals = &b->d_totals->n_tok;
+  if (slice) {  // the slice's document ends at its cut (dtk_streamcut.hip)
+    const int rc_ = launch_stream_cut(b, b->chunk ? n_bad_now(b) : nullptr);
+    if (rc_ != DTK_OK) return rc_;
+  }
   // rows are sized by the walk's own counts (no counting pass)
   if (dtk_launch_scan3(b->d_tok_cnt, b->d_sent_cnt, b->d_text_cnt, b->d_tok_off, b->d_sent_off, b->d_text_off,
                        b->n_docs, &b->d_totals->n_tok, b->d_status, b->d_scan_ws, fix_in_scan ? &sp_first : nullptr, b->d_redo,
@@ -674,6 +721,10 @@ int finish(dtk_batch *b) {
           return rc;
         }
       }
+      if (b->open_slice != 0 || b->has_carry) {  // (the run's k_stream_cut found the document broken and did nothing)
+        const int rc_ = launch_stream_cut(b, nullptr);
+        if (rc_ != DTK_OK) return rc_;
+      }
       if (dtk_launch_scan3(b->d_tok_cnt, b->d_sent_cnt, b->d_text_cnt, b->d_tok_off, b->d_sent_off, b->d_text_off,
                          b->n_docs, &b->d_totals->n_tok, b->d_status, b->d_scan_ws, nullptr, nullptr, nullptr, nullptr, s))
         return hip_fail(hipGetLastError(), "scan");
@@ -706,6 +757,9 @@ int finish(dtk_batch *b) {
   // documents whose calls are not in position order (ST_IRREGULAR): their rows come from the exact pass
   b->h_exact_ids.clear(); b->h_exact_off.assign(1, 0); b->h_calls.clear();
   if (b->h_totals->any_irregular != 0) {
+    // (the exact pass walks a document from its beginning in a new writer's terms: not from a carried record, and
+    //  not up to a cut)
+    if (b->open_slice != 0 || b->has_carry) return DTK_E_IRREGULAR;
     b->results_changed = true;
     int rc = run_exact(b);
     if (rc != DTK_OK) return rc;

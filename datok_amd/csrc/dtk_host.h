@@ -210,6 +210,13 @@ struct dtk_batch {
   hipStream_t up_stream = nullptr;  // null: uploads run on `stream`
   Event ev_up;
   bool up_pending = false;          // an upload on up_stream has not been waited for yet
+  // A slice of one long stream (dtk_streamer.cpp, batch_set_slice): the batch's one document is a window of the stream.
+  // open_slice != 0: the window's end is not the stream's -- k_stream_cut ends the document at the first sync point at
+  // or behind that many bytes; has_carry: the walk starts from the record in h_init_rec (the previous slice's cut).
+  uint32_t open_slice = 0;
+  bool has_carry = false;
+  DevArray<DtkLaneState> d_init_rec, d_open_fin;  // [1] each
+  PinBuf h_init_rec;
   uint32_t eager_fields = 0;  // the last run's k_to_host was asked for these (0: none); finish() decides whether it counts
   bool results_changed = false;  // finish() had to touch the result arrays after the run (repair, growth, EOT kernel, exact pass)
   Event ev_dl;                 // behind the batch's copies on the (possibly shared) download stream
@@ -223,6 +230,10 @@ DtkSym sym_of(const dtk_batch *b);
 DtkWalkArgs walk_args(dtk_batch *b);
 int finish(dtk_batch *b);
 int launch_to_host(dtk_batch *b);
+// The next runs of a one-document batch walk a slice of a stream: open_slice (0: the window ends where the stream
+// does) and the record to start from (null: the stream's beginning).  batch_cut: the last run's cut block, behind finish().
+int batch_set_slice(dtk_batch *b, uint32_t open_slice, const DtkLaneState *carry);
+int batch_cut(dtk_batch *b, DtkStreamCut *out);
 
 // The DTK_R_* arrays the last run wrote: DTK_NO_RUNE_OFFSETS / DTK_NO_BYTE_OFFSETS leave theirs alone.
 inline uint32_t run_fields(const dtk_batch *b) {

@@ -123,6 +123,19 @@ enum { DTK_KIND_MATRIX = 0, DTK_KIND_DA = 1 };
 #define DTK_STEP_STRIPES 32u
 #define DTK_TOTALS_BYTES (128u + DTK_STEP_STRIPES * 128u)  // a batch's totals block + the counters behind it
 
+// A slice of one long stream (dtk_stream_run): the window [0, S + T) is walked as one document, and
+// the verified start record of the first lane behind S -- the reference's exact loop state at its first rewind at or
+// behind S -- is the cut.  Calls in front of it are the slice's; the next slice, whose window begins S bytes later,
+// starts from the record.  Written by k_stream_cut (dtk_streamcut.hip), cleared with the totals block.
+struct DtkStreamCut {
+  uint32_t p, t, aux, flags;  // the carry: a DtkLaneState, its position relative to the next window (cut - S)
+  uint32_t cut;               // window-relative position of the cut; 0xFFFFFFFF: the walk closed the document in front of S
+  uint32_t valid;             // 1: the kernel ran
+  // The one lane that walks from a carried record takes the writer for new (LANE_F_FRESH), so its DTK_ST_EMPTY_TEXT may
+  // be wrong: its status is kept out of the document's and reported here, with the position its walk ended at
+  // (0xFFFFFFFF: the document's end) -- the host decides the bit from the calls up to there and the stream's own state.
+  uint32_t walker_status, walker_end;
+};
 // The totals block at the head of a batch's accumulators, with its page-locked mirror on the host.
 struct DtkTotalsDev {
   uint64_t n_tok, n_sent, n_text, n_flagged;  // the scan: tokens, sentence ints, texts, documents with a status
@@ -132,7 +145,7 @@ struct DtkTotalsDev {
   uint32_t n_bad[4];                   // documents to repair after the first pass / after each device-side round
   uint64_t render_total;               // host copy only: bytes of the rendering (dtk_results.cpp)
   uint64_t to_host_epoch;              // k_to_host: number of the run whose results it copied
-  uint64_t unused_12[4];
+  struct DtkStreamCut cut;             // k_stream_cut: where a stream's slice ends and what the next one starts from
 };
 static_assert(sizeof(struct DtkTotalsDev) == DTK_TOTALS_BYTES - DTK_STEP_STRIPES * 128u, "the block is 128 bytes");
 // the scan (k_scan3_tiles / k_scan3_mid) writes totals[0..3]; k_compact*, k_to_host read totals[0..2]
@@ -177,6 +190,8 @@ struct DtkTableDev {
 #define LANE_F_OK 4u       // sticky ok (matrix.go:352)
 #define LANE_F_DROPPED 8u  // the lane produced an event outside its window
 #define LANE_F_IDLE 16u
+#define LANE_F_FRESH 32u   // start records only: the writer behind this record is new (a slice's carried record, which
+                           // the compaction takes for a document's start: no token yet, in the text or at all)
 enum { PLAN_OFF = 0, PLAN_CHAINED = 1, PLAN_LAST = 2 };
 
 // Loop state at a "sync point" = right after the reference rewinds its window
@@ -233,6 +248,29 @@ struct DtkWalkArgs {
   uint64_t *tok_cnt, *sent_cnt, *text_cnt;  // per document: what the writer would have collected
   unsigned long long *steps;  // global lookup counter
   uint32_t step_factor;     // cap = step_factor * (len + 2) lookups per document
+  // A slice of a stream (one document): the record its walk starts from in place of {0, start state} -- every lane
+  // whose chunk does not begin behind it has this record -- or null; and for the walk with one lane per document,
+  // which has no lane records, the open end: it stops at the first sync point at or behind open_stop (0: walks to
+  // EOF) and leaves the record there in *open_fin.
+  const struct DtkLaneState *init_rec;
+  uint32_t open_stop;
+  struct DtkLaneState *open_fin;
+};
+
+// k_stream_cut (dtk_streamcut.hip): ends document 0 of a one-document batch at its cut.
+struct DtkStreamCutArgs {
+  uint32_t slice;                       // S: the cut is the start record of lane ceil(S / chunk); 0: the stream's last slice, no cut
+  const struct DtkLaneState *init_rec;  // the record the slice started from, or null (the stream's first slice)
+  uint32_t chunk, n_lanes;              // chunk 0: one lane per document, the record is *open_fin and nothing lies behind it
+  const struct DtkLaneState *lane_start;
+  struct DtkLaneCount *lane_cnt;
+  const struct DtkLaneState *open_fin;
+  uint32_t *bits;
+  uint32_t bit_words;
+  uint32_t *doc_tail, *status;
+  uint64_t *tok_cnt, *sent_cnt, *text_cnt;
+  const uint32_t *skip_if;              // documents still to repair: the kernel does nothing unless this is 0 (null: run)
+  struct DtkStreamCut *out;
 };
 
 struct DtkCompactArgs {
@@ -413,6 +451,7 @@ int dtk_launch_spec(const struct DtkTableDev *tab, const struct DtkWalkArgs *arg
 int dtk_launch_spec_check(const struct DtkWalkArgs *args, const struct DtkSpecArgs *spec, int stage, uint32_t cmp_mask,
                           uint32_t *redo_out, uint32_t *n_bad, void *stream);
 int dtk_launch_redo_clear(const struct DtkWalkArgs *args, const struct DtkSpecArgs *spec, void *stream);
+int dtk_launch_stream_cut(const struct DtkStreamCutArgs *args, void *stream);
 int dtk_launch_compact(const struct DtkCompactArgs *args, uint32_t small_max, const uint32_t *big_docs, uint32_t n_big,
                        int which, void *stream);
 int dtk_launch_exact(const struct DtkTableDev *tab, const struct DtkExactArgs *args, void *stream);

@@ -33,6 +33,7 @@ extern "C" const char *dtk_strerror(int code) {
     case DTK_E_CAPACITY: return "batch exceeds the capacity it was created with";
     case DTK_E_STATE: return "call out of order";
     case DTK_E_NOMEM: return "out of host memory";
+    case DTK_E_IRREGULAR: return "a slice of the stream needs the exact pass: tokenize the text as one document";
     default: return "unknown error";
   }
 }

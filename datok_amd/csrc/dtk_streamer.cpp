@@ -1,0 +1,248 @@
+// dtk_streamer.cpp -- one stream of any length (dtk_stream_run).  The reference tokenizes whatever
+// its reader delivers (bufio.Reader, matrix.go:373); here the stream is read into `depth` page-locked buffers of S + T
+// bytes and walked in slices: slice k is the window [k * S, k * S + S + T) as one document of one batch, from the
+// record slice k - 1 carried over, up to its cut (k_stream_cut).  Uploads, kernels and downloads of neighbouring slices
+// run on three streams like a dtk_pipeline's; the walks are serialised on what the host knows: slice k is enqueued
+// once slice k - 1 is finished (finish(): repairs, the EOT kernel, larger arrays included) and its cut block is home,
+// so no stale record is ever fed forward.
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "dtk_host.h"
+
+namespace {
+constexpr uint32_t kTail = 8192u;  // T: look-ahead behind S, so that the first sync point at or behind S (below S + DTK_WINDOW_BYTES)
+                                   // and everything in front of it is walked without a sight of the window's end
+static_assert(kTail >= 2u * DTK_WINDOW_BYTES - 16u && kTail % 256u == 0u, "the tail holds a window behind the latest cut");
+constexpr uint32_t kForced = DTK_R_CSR | DTK_R_STATUS | DTK_R_TEXTS | DTK_R_EVENT_LIST;
+}  // namespace
+
+struct dtk_stream {
+  uint64_t S = 0;
+  uint32_t depth = 0;
+  uint32_t fields = kForced | DTK_R_TOK_BYTE;
+  Stream s_up, s_run, s_down;
+  std::vector<dtk_batch *> slots;
+  std::vector<std::unique_ptr<PinBuf>> buf;  // depth x (S + T)
+  ~dtk_stream() {
+    for (dtk_batch *b : slots) dtk_batch_free(b);
+    for (hipStream_t st : {s_up.s, s_run.s, s_down.s})
+      if (st) (void)hipStreamSynchronize(st);
+  }
+};
+
+extern "C" int dtk_stream_create(uint64_t slice_bytes, uint32_t depth, dtk_stream **out) {
+  if (!out) return DTK_E_ARG;
+  *out = nullptr;
+  if (slice_bytes < 16384u || slice_bytes % 256u != 0 || slice_bytes >= 0x7FFF0000ull || depth < 2 || depth > 16) return DTK_E_ARG;
+  if (dtk_device_count() <= 0) return DTK_E_NO_DEVICE;
+  std::unique_ptr<dtk_stream> s(new dtk_stream());
+  s->S = slice_bytes;
+  s->depth = depth;
+  int rc;
+  if ((rc = s->s_up.create()) || (rc = s->s_run.create()) || (rc = s->s_down.create())) return rc;
+  for (uint32_t i = 0; i < depth; i++) {
+    dtk_batch *b = nullptr;
+    if ((rc = dtk_batch_create(slice_bytes + kTail, 1, &b)) != DTK_OK) return rc;
+    s->slots.push_back(b);
+    if ((rc = dtk_batch_set_streams(b, s->s_run, s->s_up)) != DTK_OK ||
+        (rc = dtk_batch_set_download_stream(b, s->s_down)) != DTK_OK ||
+        (rc = dtk_batch_set_result_fields(b, s->fields)) != DTK_OK)
+      return rc;
+    s->buf.emplace_back(new PinBuf());
+    if ((rc = s->buf.back()->fit(slice_bytes + kTail, slice_bytes + kTail)) != DTK_OK) return rc;
+  }
+  *out = s.release();
+  return DTK_OK;
+}
+
+extern "C" void dtk_stream_free(dtk_stream *s) { delete s; }
+
+extern "C" int dtk_stream_set_chunking(dtk_stream *s, uint32_t chunk_bytes, uint32_t warm_bytes) {
+  if (!s) return DTK_E_ARG;
+  // (the cut is the record of the first lane at or behind S: with chunks of up to 2048 bytes it lies below
+  //  S + 2048 + DTK_WINDOW_BYTES, and the walk up to it ends in front of the window's end)
+  if (chunk_bytes != 0 && chunk_bytes != 0xFFFFFFFFu && (chunk_bytes < 16 || chunk_bytes > 2048)) return DTK_E_ARG;
+  for (dtk_batch *b : s->slots) {
+    const int rc = dtk_batch_set_chunking(b, chunk_bytes, warm_bytes);
+    if (rc != DTK_OK) return rc;
+  }
+  return DTK_OK;
+}
+
+extern "C" int dtk_stream_set_result_fields(dtk_stream *s, uint32_t fields) {
+  if (!s || !(fields & (DTK_R_TOK_BYTE | DTK_R_TOK_BYTE_BLK))) return DTK_E_ARG;
+  if (fields & (DTK_R_TOK_RUNE | DTK_R_TOK_RUNE16 | DTK_R_TOK_RUNE_BLK | DTK_R_SENT | DTK_R_EAGER)) return DTK_E_ARG;  // the host writer's
+  fields |= kForced;
+  for (dtk_batch *b : s->slots) {
+    const int rc = dtk_batch_set_result_fields(b, fields);
+    if (rc != DTK_OK) return rc;
+  }
+  s->fields = fields;
+  return DTK_OK;
+}
+
+namespace {
+// DTK_ST_EMPTY_TEXT for the calls of a slice up to the cursor `upto`, in the stream's terms: SentenceEnd / TextEnd while
+// the current text has no token (token_writer.go:108,135,145); has_tok: what the stream carried in.
+bool empty_text_upto(const dtk_result_view &v, uint32_t upto, bool last, bool has_tok) {
+  const uint64_t nt = v.tok_off[1];
+  const bool blocked = !v.tok_bend && v.tok_bblk;
+  auto tok_end = [&](uint64_t i) { return blocked ? (uint32_t)dtk_blk_end(v.tok_bblk, v.tok_bblk_head, i) : v.tok_bend[i]; };
+  uint64_t k = 0;
+  uint32_t j = v.evl_off[0];
+  const uint32_t j1 = v.evl_off[1];
+  bool bad = false;
+  while (k < nt || j < j1) {
+    const uint32_t none = 0xFFFFFFFFu;
+    const uint32_t pt = k < nt ? tok_end(k) : none, pe = j < j1 ? v.evl_pos[j] : none;
+    const uint32_t p = pt < pe ? pt : pe;
+    if (p > upto) break;
+    const uint32_t e = pe == p ? v.evl_kind[j++] : 0u;
+    if ((e & DTK_EVL_SEOT) && !has_tok) bad = true;
+    if (e & DTK_EVL_TEOT) { if (!has_tok) bad = true; has_tok = false; }
+    if (pt == p) { has_tok = true; k++; }
+    if ((e & DTK_EVL_SEPS) && !has_tok) bad = true;
+  }
+  if (last && upto == 0xFFFFFFFFu && (v.doc_tail[0] & 3u) && !has_tok) bad = true;
+  return bad;
+}
+
+struct Run {
+  dtk_stream *s = nullptr;
+  dtk_read_fn read_fn = nullptr; void *read_user = nullptr;
+  dtk_stream_slice_fn slice_fn = nullptr; void *slice_user = nullptr;
+  bool eof = false;
+  std::vector<uint32_t> len;     // bytes in each slot's buffer
+  std::vector<uint8_t> touched;  // the slot's batch may have work in flight
+  // the stream's state between slices
+  bool have_carry = false;
+  DtkLaneState carry{};
+  bool has_tok = false;          // the current text has had a token
+  uint32_t status = 0;
+
+  uint8_t *bytes(uint32_t slot) { return s->buf[slot]->as<uint8_t>(); }
+
+  // window k into its slot: the tail of window k - 1 (null: the stream's beginning), then fresh bytes.  Returns the
+  // fresh bytes read.
+  uint64_t fill(uint32_t slot, const uint8_t *prev_tail) {
+    const uint64_t W = s->S + kTail;
+    uint64_t at = 0;
+    if (prev_tail) { memcpy(bytes(slot), prev_tail, kTail); at = kTail; }
+    const uint64_t at0 = at;
+    while (!eof && at < W) {
+      const size_t n = read_fn(read_user, bytes(slot) + at, (size_t)(W - at));
+      if (n == 0 || n > W - at) { eof = true; break; }
+      at += n;
+    }
+    len[slot] = (uint32_t)at;
+    return at - at0;
+  }
+  int upload(uint32_t slot) {
+    const uint64_t off[2] = {0, len[slot]};
+    touched[slot] = 1;
+    return dtk_batch_set_input(s->slots[slot], bytes(slot), off, 1);
+  }
+
+  // a slice that has been enqueued
+  struct Slice {
+    uint32_t slot = 0, first = 0;
+    uint64_t base = 0;
+    bool open = false, ended = false, carried = false;
+    DtkStreamCut c{};
+  };
+  // Finishes the slice (finish(): repairs, the EOT kernel, larger arrays), takes its cut block -- what the next slice
+  // starts from -- and starts its results on their way home.
+  int take_cut(Slice &x) {
+    dtk_batch *b = s->slots[x.slot];
+    int rc = batch_cut(b, &x.c);
+    if (rc != DTK_OK) return rc;
+    if ((x.open || x.carried) && !x.c.valid) return DTK_E_STATE;
+    // (no cut although bytes follow: the walk closed the document in front of S -- a window overflow, a walk that left
+    //  the table -- as the reference ends there)
+    x.ended = !x.open || x.c.cut == 0xFFFFFFFFu;
+    if (!x.ended) {
+      carry = DtkLaneState{x.c.p, x.c.t, x.c.aux, x.c.flags};
+      have_carry = true;
+    }
+    return dtk_batch_download_begin(b);
+  }
+  // hands the slice over (its successor may be walking meanwhile)
+  int deliver(const Slice &x) {
+    dtk_batch *b = s->slots[x.slot];
+    dtk_stream_slice sl{};
+    sl.base = x.base; sl.first = x.first; sl.len = len[x.slot]; sl.text = bytes(x.slot);
+    sl.last = x.ended ? 1u : 0u;
+    sl.cut = x.ended ? sl.len : x.c.cut;
+    int rc = dtk_batch_result_host(b, &sl.view);
+    if (rc != DTK_OK) return rc;
+    if (sl.view.n_exact) return DTK_E_IRREGULAR;
+    uint32_t st = sl.view.status[0];
+    if (x.carried) {
+      // the lane that walked from the carried record took the writer for new: its bit is decided here
+      st |= x.c.walker_status & ~(uint32_t)DTK_ST_EMPTY_TEXT;
+      if ((x.c.walker_status & DTK_ST_EMPTY_TEXT) && empty_text_upto(sl.view, x.c.walker_end, x.ended, has_tok))
+        st |= DTK_ST_EMPTY_TEXT;
+    }
+    sl.status = st;
+    status |= st;
+    // "the current text has had a token" behind this slice
+    const uint64_t nt = sl.view.tok_off[1], nx = sl.view.text_off[1];
+    const uint64_t n_teot = nx - ((x.ended && (sl.view.doc_tail[0] & DTK_TAIL_E)) ? 1u : 0u);
+    has_tok = n_teot ? nt > sl.view.text_tok_end[n_teot - 1] : (has_tok || nt > 0);
+    return slice_fn ? slice_fn(slice_user, &sl) : DTK_OK;
+  }
+};
+}  // namespace
+
+extern "C" int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn read_fn, void *read_user, uint32_t flags,
+                              dtk_stream_slice_fn slice_fn, void *slice_user, uint32_t *status) {
+  if (!s || !m || !read_fn || (flags & ~(uint32_t)31u)) return DTK_E_ARG;
+  if (status) *status = 0;
+  const uint32_t depth = s->depth;
+  Run r;
+  r.s = s; r.read_fn = read_fn; r.read_user = read_user; r.slice_fn = slice_fn; r.slice_user = slice_user;
+  r.len.assign(depth, 0);
+  r.touched.assign(depth, 0);
+  // (the writer's rune offsets are the host's: the compaction writes the byte offsets only)
+  const uint32_t run_flags = DTK_NO_RUNE_OFFSETS;
+  r.fill(0, nullptr);
+  int rc = r.upload(0);
+  Run::Slice prev;
+  for (uint64_t k = 0; rc == DTK_OK; k++) {
+    const uint32_t slot = (uint32_t)(k % depth), next = (uint32_t)((k + 1) % depth);
+    // with two buffers window k + 1 goes where slice k - 1 lies: that one is handed over first
+    if (k > 0 && depth == 2 && ((rc = r.take_cut(prev)) != DTK_OK || (rc = r.deliver(prev)) != DTK_OK || prev.ended)) break;
+    bool open = false;
+    if (r.len[slot] == s->S + kTail && !r.eof) {
+      open = r.fill(next, r.bytes(slot) + s->S) > 0;
+      if (open && (rc = r.upload(next)) != DTK_OK) break;
+    }
+    // the predecessor's cut: slice k starts from it
+    if (k > 0 && depth > 2) {
+      if ((rc = r.take_cut(prev)) != DTK_OK) break;
+      if (prev.ended) { rc = r.deliver(prev); break; }
+    }
+    Run::Slice cur;
+    cur.slot = slot; cur.base = k * s->S; cur.open = open;
+    cur.carried = r.have_carry; cur.first = r.have_carry ? r.carry.p : 0u;
+    if ((rc = batch_set_slice(s->slots[slot], open ? (uint32_t)s->S : 0u, r.have_carry ? &r.carry : nullptr)) != DTK_OK ||
+        (rc = dtk_batch_run(m, s->slots[slot], run_flags)) != DTK_OK)
+      break;
+    if (k > 0 && depth > 2 && (rc = r.deliver(prev)) != DTK_OK) break;  // (under the walk of slice k)
+    if (!open) {  // the stream's last slice
+      if ((rc = r.take_cut(cur)) == DTK_OK) rc = r.deliver(cur);
+      break;
+    }
+    prev = cur;
+  }
+  // nothing of this run stays in flight (an error, or a slice that ended the stream early with its successor uploaded)
+  for (uint32_t q = 0; q < depth; q++)
+    if (r.touched[q]) {
+      (void)dtk_batch_sync(s->slots[q]);
+      (void)batch_set_slice(s->slots[q], 0u, nullptr);
+    }
+  if (status) *status = r.status;
+  return rc;
+}

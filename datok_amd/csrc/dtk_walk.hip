@@ -151,12 +151,21 @@ __global__ __launch_bounds__(WAVE) void k_walk_doc(TRANS tr, DtkWalkArgs A, uint
   if (d < A.n_docs) {
     const uint64_t off = A.doc_off[d];
     const uint32_t len = (uint32_t)(A.doc_off[d + 1] - off);
-    EventSink sink;
-    sink.init(A, off, d, 0u, 0xFFFFFFFFu);  // (documents of any length: the bits go straight to memory)
     DtkLaneState init{0u, tr.start_state(), tr.start_aux(), 0u}, fin;
+    if (A.init_rec) { init = A.init_rec[d]; init.flags |= LANE_F_FRESH; }  // a slice of a stream: its carried record
+    EventSink sink;
+    sink.init(A, off, d, init.p, 0xFFFFFFFFu);  // (documents of any length: the bits go straight to memory)
     uint32_t st;
-    walk_any<TRANS, IS_MATRIX, MODE_DOC>(tr, A.sym, off, len, init, 0u, sink, epsilon, unknown,
-                                          identity, step_cap(A.step_factor, len), fin, st, steps, win_row, s_lut);
+    if (A.open_stop) {
+      // a slice with an open end: up to the first sync point at or behind the stop, which is the slice's cut
+      walk_any<TRANS, IS_MATRIX, MODE_CHUNK>(tr, A.sym, off, len, init, A.open_stop, sink, epsilon, unknown,
+                                              identity, step_cap(A.step_factor, len), fin, st, steps, win_row, s_lut);
+      fin.flags &= (LANE_F_SENT | LANE_F_TEXT | LANE_F_OK);
+      A.open_fin[d] = fin;
+    } else {
+      walk_any<TRANS, IS_MATRIX, MODE_DOC>(tr, A.sym, off, len, init, 0u, sink, epsilon, unknown,
+                                            identity, step_cap(A.step_factor, len), fin, st, steps, win_row, s_lut);
+    }
     A.status[d] = st | sink.st;
     A.tok_cnt[d] = sink.c_tok; A.sent_cnt[d] = sink.c_sent; A.text_cnt[d] = sink.c_text;
   }
@@ -193,11 +202,15 @@ extern "C" int dtk_phase_read(unsigned long long *out, int reset) {
 // the start record of lane k >= 0 of document d (k_spec_start, k_spec_both)
 template <typename TRANS, bool IS_MATRIX>
 __device__ __forceinline__ DtkLaneState start_record(const TRANS &tr, const DtkWalkArgs &A, const DtkSpecArgs &S,
-                                                     uint32_t k, uint64_t off, uint32_t len, uint32_t epsilon,
+                                                     uint32_t d, uint32_t k, uint64_t off, uint32_t len, uint32_t epsilon,
                                                      uint32_t unknown, uint32_t identity, uint16_t *win_row,
                                                      const uint16_t *s_lut, uint32_t &steps) {
   DtkLaneState rec{0u, tr.start_state(), tr.start_aux(), 0u};
-  if (k > 0) {
+  // A slice of a stream starts from the record its predecessor's cut carried over.  A lane whose
+  // chunk does not begin behind that record has the record itself: what lies in front of it has been reported, and
+  // the lane owns nothing (rec.p >= stop in k_spec_both).
+  if (A.init_rec) { rec = A.init_rec[d]; rec.flags |= LANE_F_FRESH; }
+  if (k * S.chunk > rec.p) {
     const uint32_t kc = k * S.chunk;
     uint32_t sp = kc > S.warm ? kc - S.warm : 0u;
     if (sp > 0 && S.warm_extend && S.text) {
@@ -271,7 +284,7 @@ __device__ __forceinline__ DtkLaneState start_record(const TRANS &tr, const DtkW
       walk_any<TRANS, IS_MATRIX, MODE_START>(tr, A.sym, off, len, init, kc, sink, epsilon, unknown,
                                               identity, step_cap(A.step_factor, len), rec, st, steps, win_row, s_lut);
     } else {
-      // sp == 0: the walk from the true initial state; its first sync point at/after kc
+      // sp == 0: the walk from the true initial state (or the slice's carried record); its first sync point at/after kc
       walk_any<TRANS, IS_MATRIX, MODE_START>(tr, A.sym, off, len, rec, kc, sink, epsilon, unknown,
                                               identity, step_cap(A.step_factor, len), rec, st, steps, win_row, s_lut);
     }
@@ -291,7 +304,7 @@ __global__ __launch_bounds__(WAVE) void k_spec_start(TRANS tr, DtkWalkArgs A, Dt
     const uint32_t k = L - S.chunk_off[d];
     const uint64_t off = A.doc_off[d];
     const uint32_t len = (uint32_t)(A.doc_off[d + 1] - off);
-    S.lane_start[L] = start_record<TRANS, IS_MATRIX>(tr, A, S, k, off, len, epsilon, unknown, identity, win_row, s_lut, steps);
+    S.lane_start[L] = start_record<TRANS, IS_MATRIX>(tr, A, S, d, k, off, len, epsilon, unknown, identity, win_row, s_lut, steps);
   }
   add_steps(A.steps, steps);
 }
@@ -324,7 +337,7 @@ __global__ __launch_bounds__(WAVE, WinOf<TRANS>::OCC) void k_spec_both(TRANS tr,
     const uint64_t off = A.doc_off[d];
     const uint32_t len = (uint32_t)(A.doc_off[d + 1] - off);
     const DtkLaneState rec =
-        start_record<TRANS, IS_MATRIX>(tr, A, S, k, off, len, epsilon, unknown, identity, win_row, s_lut, steps);
+        start_record<TRANS, IS_MATRIX>(tr, A, S, d, k, off, len, epsilon, unknown, identity, win_row, s_lut, steps);
 #ifdef DTK_PROBE
     pt1 = clock64();
 #endif

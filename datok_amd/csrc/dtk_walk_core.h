@@ -477,8 +477,11 @@ __device__ __forceinline__ void walk_lane(const TRANS &tr, const DtkSym &sym,
   // NewTokenWriter state that the counts need.  A lane starts right after a rewind:
   // p > 0 means a token was flushed or an EOT fired there, so "a token exists in the
   // document" is p > 0 and "in the current text" additionally needs !textEnd.
-  bool any_tok = init.p > 0;               // some Token call happened (else sentB is still true)
-  bool has_tok = init.p > 0 && !text_end;  // pos[] of the current text is not empty
+  // (LANE_F_FRESH: a stream slice's carried record -- the slice is compacted like a document of its own, whose writer
+  //  has seen no token, whatever the position)
+  const bool written = init.p > 0 && !(init.flags & LANE_F_FRESH);
+  bool any_tok = written;               // some Token call happened (else sentB is still true)
+  bool has_tok = written && !text_end;  // pos[] of the current text is not empty
 
   uint32_t wbase = (init.p + o7) & ~7u;
   win_fill(row, sym, aligned + wbase);
@@ -684,8 +687,10 @@ __device__ __forceinline__ void walk_fused(const TRANS &tr, const DtkSym &sym,
   uint32_t eps_t = 0, eps_p = 0;
   // F: 1 sentenceEnd, 2 textEnd (matrix.go:360-363), 4 some Token call happened in this document,
   //    8 the current text has a token (what NewTokenWriter's sentB / pos need)
-  uint32_t F = (init.flags & (LANE_F_SENT | LANE_F_TEXT)) | (init.p > 0 ? 4u : 0u);
-  F |= (init.p > 0 && !(init.flags & LANE_F_TEXT)) ? 8u : 0u;
+  //    (neither behind LANE_F_FRESH: a stream slice's carried record, whose writer is the compaction's new one)
+  const bool written = init.p > 0 && !(init.flags & LANE_F_FRESH);
+  uint32_t F = (init.flags & (LANE_F_SENT | LANE_F_TEXT)) | (written ? 4u : 0u);
+  F |= (written && !(init.flags & LANE_F_TEXT)) ? 8u : 0u;
   static_assert(LANE_F_SENT == 1u && LANE_F_TEXT == 2u, "flag layout");
   uint32_t st = 0;
   uint32_t budget = cap;  // lookups left; the one that finds none left sets ST_STEP_LIMIT

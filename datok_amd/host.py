@@ -24,6 +24,8 @@ EVL_SEOT, EVL_TEOT, EVL_SEPS = 1, 2, 4
 # ------------------------------------------------------------------ UTF-8 (Go)
 def _decode_runes(b: bytes):
     """Go's rune iteration: invalid bytes become U+FFFD of width 1."""
+    if isinstance(b, bytes) and b.isascii():
+        return list(b)
     out, i, n = [], 0, len(b)
     while i < n:
         b0 = b[i]
@@ -223,6 +225,68 @@ def replay_list(is_matrix, text: bytes, evl_pos, evl_kind, tail, tok_bstart, tok
         tw.TextEnd(len(_decode_runes(text[B:p])) if is_matrix else 0)
 
 
+class SliceView:
+    """One slice of a stream (dtk_stream_slice, datok_gpu.h) in host arrays.  All positions are relative to the
+    slice's window `text`, whose byte 0 is stream byte `base`: the slice's calls begin with the reference's window
+    start (buffer[0]) at `first` and end at `cut`; `tail` (doc_tail) counts on the `last` slice only."""
+    __slots__ = ("base", "first", "cut", "text", "last", "status", "tok_bstart", "tok_bend", "evl_pos", "evl_kind", "tail")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k, 0))
+
+
+def slice_calls(is_matrix, sl: SliceView):
+    """The reference's calls of one slice, in its order: ('T', B, start, end) for Token(offset, buf) with buf =
+    text[B:end] and buf[offset:] = text[start:end]; ('S', B, p) / ('E', B, p) for SentenceEnd / TextEnd at cursor p
+    (B: the window start then).  replay_list()'s merge, with the window start beginning at sl.first instead of 0."""
+    n = len(sl.text)
+    B = int(sl.first)
+    k = j = 0
+    nt, ne = len(sl.tok_bend), len(sl.evl_pos)
+    while k < nt or j < ne:
+        pt = int(sl.tok_bend[k]) if k < nt else n + 1
+        pe = int(sl.evl_pos[j]) if j < ne else n + 1
+        p = min(pt, pe)
+        e = 0
+        if pe == p:
+            e = int(sl.evl_kind[j])
+            j += 1
+        if e & EVL_SEOT:
+            yield ("S", B, p, True)
+        if e & EVL_TEOT:
+            yield ("E", B, p, is_matrix)
+            if is_matrix:
+                B = p
+        if pt == p:
+            yield ("T", B, int(sl.tok_bstart[k]), p)
+            k += 1
+            B = p
+        if e & EVL_SEPS:
+            yield ("S", B, p, is_matrix)
+    if sl.last:
+        tail = int(sl.tail)
+        p = min(tail >> 2, n)
+        if tail & 1:
+            yield ("S", B, p, is_matrix)
+        if tail & 2:
+            yield ("E", B, p, is_matrix)
+
+
+def replay_slice(is_matrix, sl: SliceView, tw: TokenWriter):
+    """Feeds one slice of a stream to the closures of the stream's ONE writer (posC, sentB and init of NewTokenWriter
+    run across cuts, token_writer.go:38-42).  The int arguments are replay()'s."""
+    text = sl.text
+    for c in slice_calls(is_matrix, sl):
+        if c[0] == "T":
+            _, B, start, end = c
+            tw.Token(len(_decode_runes(text[B:start])), _decode_runes(text[B:end]))
+        else:
+            kind, B, p, counted = c
+            arg = len(_decode_runes(text[B:p])) if counted else 0
+            (tw.SentenceEnd if kind == "S" else tw.TextEnd)(arg)
+
+
 def replay_calls(text: bytes, calls, tw: TokenWriter):
     """Feeds the call list of a document walked by the exact pass (dtk_result_view.calls: rows of
     (kind, a, b, c)) to the closures: kind 0 Token(offset, buf) with buf = runes of text[a:c] and offset =
@@ -277,8 +341,21 @@ class Tokenizer:
         """matrix.go:340-342: TransduceTokenWriter(r, NewTokenWriter(w, SIMPLE))."""
         return self.transduce_token_writer(r, new_token_writer(w, SIMPLE))
 
-    def transduce_token_writer(self, r, tw: TokenWriter) -> bool:
-        """matrix.go:348-698 / datok.go:781-1135. One reader = one document."""
+    def transduce_token_writer(self, r, tw: TokenWriter, slice_bytes=None) -> bool:
+        """matrix.go:348-698 / datok.go:781-1135. One reader = one document.
+
+        slice_bytes: the reader is a stream of unknown (any) length -- it is read and walked in slices of that many
+        bytes with bounded memory (Stream, dtk_stream_run) and replayed slice by slice into the one writer."""
+        if slice_bytes is not None:
+            is_matrix = self.type() == "MATOK"
+            try:
+                with Stream(slice_bytes) as st:
+                    self.last_status = st.run(self, r, on_slice=lambda sl: replay_slice(is_matrix, sl, tw))
+            except _lib.DatokGpuError as e:        # the reference returns false
+                print("datok_amd:", e, file=sys.stderr)
+                return False
+            tw.Flush()
+            return not (self.last_status & _FATAL)
         text = r.read() if hasattr(r, "read") else bytes(r)
         if isinstance(text, str):
             text = text.encode("utf-8")
@@ -606,6 +683,116 @@ class Pipeline:
         if err:
             raise err[0]
         check(rc, "dtk_pipeline_run")
+
+
+class Stream:
+    """dtk_stream: ONE stream of any length, read through a reader and walked in slices of slice_bytes with bounded host
+    memory (depth * (slice_bytes + 8192) page-locked bytes).  run() calls on_slice(SliceView) for every slice in order;
+    the calls of the slices, one after the other, are the reference's calls for the whole stream (slice_calls,
+    replay_slice)."""
+
+    def __init__(self, slice_bytes=16 << 20, depth=3):
+        self._h = C.c_void_p()
+        check(lib().dtk_stream_create(int(slice_bytes), int(depth), C.byref(self._h)), "dtk_stream_create")
+        self.slice_bytes = int(slice_bytes)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib().dtk_stream_free(h)
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_chunking(self, chunk_bytes=0xFFFFFFFF, warm_bytes=8):
+        check(lib().dtk_stream_set_chunking(self._h, int(chunk_bytes), int(warm_bytes)), "dtk_stream_set_chunking")
+
+    def set_result_fields(self, fields):
+        """Batch.R_* of every slice's view: R_TOK_BYTE or R_TOK_BYTE_BLK, optionally R_EVENTS; the event list, the row
+        offsets, the texts and the status always come."""
+        check(lib().dtk_stream_set_result_fields(self._h, int(fields)), "dtk_stream_set_result_fields")
+
+    @staticmethod
+    def _reader_fn(reader, err):
+        if not hasattr(reader, "read"):
+            reader = io.BytesIO(reader.encode("utf-8") if isinstance(reader, str) else bytes(reader))
+
+        def rd(_user, buf, cap):
+            try:
+                data = reader.read(cap)
+                if isinstance(data, str):
+                    raise TypeError("the reader must deliver bytes")
+                if not data:
+                    return 0
+                C.memmove(buf, bytes(data), len(data))
+                return len(data)
+            except Exception as e:  # noqa: BLE001  (do not unwind through the C frame: the stream ends here)
+                err.append(e)
+                return 0
+        return _lib.READ_FN(rd)
+
+    def transduce(self, tok, reader, flags=SIMPLE):
+        """dtk_stream_transduce: what the reference writes for the stream with a stock NewTokenWriter(w, flags), every
+        slice replayed into the one writer of the C++ mirror.  Returns (output, status)."""
+        err = []
+        out, n, st = C.c_void_p(), C.c_size_t(), C.c_uint32()
+        rc = lib().dtk_stream_transduce(self._h, tok._h, self._reader_fn(reader, err), None, int(flags), C.byref(out),
+                                        C.byref(n), C.byref(st))
+        if err:
+            raise err[0]
+        check(rc, "dtk_stream_transduce")
+        try:
+            return C.string_at(out, n.value), st.value
+        finally:
+            lib().dtk_free(out)
+
+    def run(self, tok, reader, flags=0, on_slice=None) -> int:
+        """reader: bytes, or an object with read(n) (b"" at the end; short reads are fine).  Returns the stream's status."""
+        err = []
+        rd = self._reader_fn(reader, err)
+
+        def cb(_user, p):
+            if on_slice is None:
+                return 0
+            try:
+                on_slice(_slice_view(p.contents))
+                return 0
+            except Exception as e:  # noqa: BLE001
+                err.append(e)
+                return _lib.E_STATE
+        st = C.c_uint32(0)
+        rc = lib().dtk_stream_run(self._h, tok._h, rd, None, int(flags), _lib.STREAM_SLICE_FN(cb), None, C.byref(st))
+        if err:
+            raise err[0]
+        check(rc, "dtk_stream_run")
+        return int(st.value)
+
+
+def _slice_view(s) -> SliceView:
+    """Host copies of a dtk_stream_slice (its buffers are only valid inside the callback)."""
+    v = s.view
+
+    def arr(ptr, n, dt):
+        if n == 0 or not ptr:
+            return np.zeros(0, dt)
+        return np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(ptr), dtype=dt).copy()
+    nt = int(arr(v.tok_off, 2, np.uint64)[1])
+    if v.tok_bend:
+        bs, be = arr(v.tok_bstart, nt, np.uint32), arr(v.tok_bend, nt, np.uint32)
+    else:                                              # (R_TOK_BYTE_BLK)
+        bs, be = (x.astype(np.uint32) for x in
+                  unpack_blocked(arr(v.tok_bblk, nt, np.uint32), arr(v.tok_bblk_head, 4 * ((nt + 63) // 64), np.int32)))
+    off = arr(v.evl_off, 2, np.uint32)
+    ne = int(off[1])
+    return SliceView(base=int(s.base), first=int(s.first), cut=int(s.cut), last=int(s.last), status=int(s.status),
+                     text=C.string_at(s.text, int(s.len)) if s.len else b"",
+                     tok_bstart=bs, tok_bend=be, evl_pos=arr(v.evl_pos, ne, np.uint32)[int(off[0]):],
+                     evl_kind=arr(v.evl_kind, ne, np.uint8)[int(off[0]):], tail=int(arr(v.doc_tail, 1, np.uint32)[0]))
 
 
 def _slice_callback(on_slice, doc_off, err):

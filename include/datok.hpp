@@ -155,8 +155,10 @@ inline void replay(bool is_matrix, const uint8_t *text, size_t n, const dtk_resu
 // four bits at every byte.  A token's cursor is tok_bend[k] and its first byte tok_bstart[k]; where only the blocked
 // byte offsets were delivered (DTK_R_TOK_BYTE_BLK) both come from dtk_blk_end / dtk_blk_start.  Order and int
 // arguments as above.
+// A slice of a stream (dtk_stream_slice) is replayed the same way into the stream's one writer: the window start
+// begins at the slice's `first` instead of 0, and the tail word counts on the last slice only.
 inline void replay_list(bool is_matrix, const uint8_t *text, size_t n, const dtk_result_view &v, uint32_t d,
-                        TokenWriter &w) {
+                        TokenWriter &w, size_t first = 0, bool with_tail = true) {
   const uint64_t t0 = v.tok_off[d], t1 = v.tok_off[d + 1];
   const bool blocked = !v.tok_bend && v.tok_bblk;
   auto tok_end = [&](uint64_t i) { return blocked ? (size_t)dtk_blk_end(v.tok_bblk, v.tok_bblk_head, i) : (size_t)v.tok_bend[i]; };
@@ -164,7 +166,7 @@ inline void replay_list(bool is_matrix, const uint8_t *text, size_t n, const dtk
   uint64_t k = t0;                               // next token
   uint32_t j = v.evl_off[d];                     // next entry
   const uint32_t j1 = v.evl_off[d + 1];
-  size_t B = 0;                                  // byte position of the window start (last rewind)
+  size_t B = first;                              // byte position of the window start (last rewind)
   std::vector<rune> buf;
   auto buffc = [&](size_t p) { return count_runes(text + B, p - B); };
   while (k < t1 || j < j1) {
@@ -194,6 +196,7 @@ inline void replay_list(bool is_matrix, const uint8_t *text, size_t n, const dtk
     }
     if (e & DTK_EVL_SEPS) w.SentenceEnd(is_matrix ? buffc(p) : 0);
   }
+  if (!with_tail) return;
   const uint32_t tail = v.doc_tail[d];
   const size_t pt = tail >> 2;
   if (tail & DTK_TAIL_S) w.SentenceEnd(is_matrix ? buffc(pt) : 0);
@@ -376,6 +379,35 @@ class GpuTokenizer final : public Tokenizer {
         return false;
     }
     return ok;
+  }
+  // The same for a reader of any length, as the reference reads it through a bufio.Reader (matrix.go:373): the stream
+  // is read and walked in slices of slice_bytes (dtk_stream_run: host memory stays at depth * (slice_bytes + 8192)
+  // bytes) and replayed slice by slice into the one writer.  false also for a stream a slice of which needs the exact
+  // pass (DTK_E_IRREGULAR: crafted models only).
+  bool TransduceStream(std::istream &r, TokenWriter &w, uint64_t slice_bytes = 16u << 20, uint32_t depth = 3) {
+    last_status_ = 0;
+    dtk_stream *s = nullptr;
+    if (dtk_stream_create(slice_bytes, depth, &s) != DTK_OK) return false;
+    const int rc = RunStream(s, r, w);
+    dtk_stream_free(s);
+    w.Flush();  // `defer w.Flush()`, matrix.go:374
+    return rc == DTK_OK &&
+           !(last_status_ & (DTK_ST_WINDOW_OVERFLOW | DTK_ST_BAD_MODEL | DTK_ST_STEP_LIMIT | DTK_ST_INTERNAL | DTK_ST_IRREGULAR));
+  }
+  // ... on a dtk_stream the caller keeps (and has configured); returns dtk_stream_run's code
+  int RunStream(dtk_stream *s, std::istream &r, TokenWriter &w) {
+    struct Ctx { std::istream *r; TokenWriter *w; bool is_matrix; } c{&r, &w, Type() == "MATOK"};
+    auto rd = [](void *u, uint8_t *buf, size_t cap) -> size_t {
+      Ctx *c = static_cast<Ctx *>(u);
+      c->r->read(reinterpret_cast<char *>(buf), (std::streamsize)cap);
+      return (size_t)c->r->gcount();
+    };
+    auto on_slice = [](void *u, const dtk_stream_slice *sl) -> int {
+      Ctx *c = static_cast<Ctx *>(u);
+      detail::replay_list(c->is_matrix, sl->text, sl->len, sl->view, 0, *c->w, sl->first, sl->last != 0);
+      return DTK_OK;
+    };
+    return dtk_stream_run(s, m_, rd, &c, 0, on_slice, &c, &last_status_);
   }
   uint32_t last_status() const { return last_status_; }
 

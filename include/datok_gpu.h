@@ -37,7 +37,9 @@ enum {
                            or a Foma net ParseFoma rejects (fomafile.go:159-167,283-310) */
   DTK_E_CAPACITY = -7,  /* batch larger than the dtk_batch was created for */
   DTK_E_STATE = -8,     /* call order (e.g. result requested before a run) */
-  DTK_E_NOMEM = -9      /* host allocation failed */
+  DTK_E_NOMEM = -9,     /* host allocation failed */
+  DTK_E_IRREGULAR = -10 /* dtk_stream_run: a slice needs the exact pass (calls that are not in position order, which
+                           only crafted models produce); tokenize the text as one document (dtk_transduce*, dtk_batch) */
 };
 
 /* ---- Bits, token_writer.go:17-25 (same values) ---- */
@@ -441,6 +443,54 @@ int dtk_pipeline_set_chunking(dtk_pipeline *p, uint32_t chunk_bytes, uint32_t wa
 int dtk_pipeline_set_result_fields(dtk_pipeline *p, uint32_t fields);
 int dtk_pipeline_run(dtk_pipeline *p, const dtk_model *m, const uint8_t *text, const uint64_t *doc_off,
                      uint32_t n_docs, uint32_t flags, dtk_slice_fn fn, void *user);
+/* ---- one stream of any length: the reference tokenizes whatever its reader delivers (bufio.Reader, matrix.go:373;
+ *      cmd/datok.go:120-133 feeds a whole file or STDIN as ONE stream, texts separated by U+0004).  dtk_stream_run reads
+ *      the stream through read_fn into page-locked buffers and walks it in slices of slice_bytes (S): slice k is the
+ *      window [k * S, k * S + S + 8192) of the stream, walked as one document from the loop state its predecessor
+ *      carried over, and ends at its cut -- the reference's first window rewind at or behind window byte S, proved exact
+ *      like every lane start of the speculative walk.  Every call of the reference in front of the cut is the slice's;
+ *      the calls from the cut on are the next slice's.  Host memory is depth * (S + 8192) bytes plus result buffers,
+ *      whatever the stream's length.  The last slice ends where the stream does, with the final SentenceEnd / TextEnd.
+ *        slice_fn gets the slices in order on the calling thread.  All positions of `view` (tok_bstart / tok_bend or the
+ *      blocked form, evl_pos or the bitmaps, doc_tail) are relative to the window, whose byte 0 is stream byte `base`;
+ *      a replay starts with the window start (buffer[0] of the reference) at `first`.  The writer's rune offsets and
+ *      sentence list run across cuts (posC, sentB, init of token_writer.go:38-42): they are the host writer's that the
+ *      replay feeds, as in the reference -- tok_rstart / tok_rend / sent of a slice's view are not delivered.
+ *        *status: the OR of the slices' status bits; DTK_ST_EMPTY_TEXT is decided for the stream (a text may span cuts).
+ *      A slice that needs the exact pass ends the run with DTK_E_IRREGULAR. ---- */
+typedef struct dtk_stream dtk_stream;
+typedef struct {
+  uint64_t base;       /* stream offset of window byte 0 */
+  uint32_t first;      /* window-relative: where this slice's calls begin (0 for the first slice, else the previous cut - S) */
+  uint32_t cut;        /* window-relative: where they end; == len on the last slice */
+  uint32_t len;        /* bytes of the window */
+  uint32_t last;       /* 1: the stream's last slice -- view.doc_tail[0] holds the final SentenceEnd / TextEnd */
+  uint32_t status;     /* the slice's DTK_ST_* bits, DTK_ST_EMPTY_TEXT decided with what the stream carried in */
+  const uint8_t *text; /* the window's bytes (page-locked host memory), valid until slice_fn returns */
+  dtk_result_view view;/* host pointers, one document; valid until slice_fn returns */
+} dtk_stream_slice;
+typedef size_t (*dtk_read_fn)(void *user, uint8_t *buf, size_t cap);       /* fills up to cap bytes; 0: end of the stream */
+typedef int (*dtk_stream_slice_fn)(void *user, const dtk_stream_slice *s); /* DTK_OK to go on */
+/* slice_bytes: a multiple of 256, at least 16 384 and below 2^31 (else DTK_E_ARG); depth: 2..16 buffers and batches
+ * (3 and more: the read of slice k + 1 and the delivery of slice k - 1 run beside the walk of slice k). */
+int dtk_stream_create(uint64_t slice_bytes, uint32_t depth, dtk_stream **out);
+void dtk_stream_free(dtk_stream *s);
+/* as dtk_batch_set_chunking; chunk_bytes 0 (one lane per slice), 16..2048 or 0xFFFFFFFF (by slice size) */
+int dtk_stream_set_chunking(dtk_stream *s, uint32_t chunk_bytes, uint32_t warm_bytes);
+/* The DTK_R_* arrays of every slice's view.  DTK_R_CSR, DTK_R_STATUS, DTK_R_TEXTS and DTK_R_EVENT_LIST always come;
+ * the token bytes must be among them as DTK_R_TOK_BYTE or DTK_R_TOK_BYTE_BLK (else DTK_E_ARG).  Default: DTK_R_TOK_BYTE. */
+int dtk_stream_set_result_fields(dtk_stream *s, uint32_t fields);
+/* flags: DTK_NEWLINE_AFTER_EOT is accepted and changes nothing here (it only moves the writer's rune offsets).  Short
+ * reads are retried until a buffer is full; read_fn is not called again after it has returned 0. */
+int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn read_fn, void *read_user, uint32_t flags,
+                   dtk_stream_slice_fn slice_fn, void *slice_user, uint32_t *status);
+/* What the reference writes to w for the stream with a stock NewTokenWriter(w, bits) -- dtk_transduce_replay for a
+ * reader of any length: every slice is replayed into the one writer of the C++ mirror (include/datok.hpp).  *out is
+ * malloc'd (the whole output: a caller that must bound that too writes from slice_fn, as `datok tokenize` does); free
+ * with dtk_free. */
+int dtk_stream_transduce(dtk_stream *s, const dtk_model *m, dtk_read_fn read_fn, void *read_user, uint32_t bits,
+                         char **out, size_t *out_len, uint32_t *status);
+
 /* ---- several GPUs of one node.  Documents are independent (matrix.go:349-381: all walk state is per call), so a corpus
  *      shards by slices with nothing to exchange: dtk_multi keeps one worker thread per listed device, each with its
  *      own replica of the model (loaded from model_path on that device) and its own dtk_pipeline; dtk_multi_run deals

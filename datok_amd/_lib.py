@@ -34,7 +34,7 @@ EXPORTS = [
     "dtk_debug_configure", "dtk_batch_debug_stream", "dtk_blk_start", "dtk_blk_end",
     "dtk_multi_create", "dtk_multi_free", "dtk_multi_type", "dtk_multi_set_result_fields", "dtk_multi_set_chunking", "dtk_multi_run",
     "dtk_stream_create", "dtk_stream_free", "dtk_stream_set_chunking", "dtk_stream_set_result_fields", "dtk_stream_run",
-    "dtk_stream_transduce",
+    "dtk_stream_transduce", "dtk_stream_set_render",
 ]
 
 
@@ -74,7 +74,8 @@ SLICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)
 class StreamSlice(C.Structure):
     """dtk_stream_slice: one slice of dtk_stream_run (positions relative to the window, whose byte 0 is stream byte base)."""
     _fields_ = [("base", C.c_uint64), ("first", C.c_uint32), ("cut", C.c_uint32), ("len", C.c_uint32),
-                ("last", C.c_uint32), ("status", C.c_uint32), ("text", C.c_void_p), ("view", ResultView)]
+                ("last", C.c_uint32), ("status", C.c_uint32), ("text", C.c_void_p), ("view", ResultView),
+                ("out", C.c_void_p), ("out_len", C.c_uint64)]
 
 
 READ_FN = C.CFUNCTYPE(C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -189,6 +190,7 @@ def lib():
     L.dtk_stream_free.restype = None
     L.dtk_stream_set_chunking.argtypes = [vp, u32, u32]
     L.dtk_stream_set_result_fields.argtypes = [vp, u32]
+    L.dtk_stream_set_render.argtypes = [vp, C.c_int, u32]
     L.dtk_stream_run.argtypes = [vp, vp, READ_FN, vp, u32, STREAM_SLICE_FN, vp, C.POINTER(u32)]
     L.dtk_stream_transduce.argtypes = [vp, vp, READ_FN, vp, u32, C.POINTER(vp), C.POINTER(sz), C.POINTER(u32)]
     for f in (L.dtk_blk_start, L.dtk_blk_end):

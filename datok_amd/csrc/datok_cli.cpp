@@ -6,8 +6,10 @@
 //
 // `tokenize` reads its input as ONE stream of any length (cmd/datok.go:120-133), U+0004 ends a text inside it: the
 // stream is read and walked on the GPU in slices of --slice-bytes (default 16 MiB, a multiple of 256 from 16 384 on;
-// dtk_stream_run: the input is never held whole) and every slice is replayed into the one NewTokenWriter on standard
-// output as it comes home.  `convert` is host only; -d: the double array (ToDoubleArray, datok.go:82-238).
+// dtk_stream_run: the input is never held whole).  Without a position flag every slice's bytes are rendered on the
+// device (dtk_stream_set_render) and written to standard output as they come home; with --token-positions or
+// --sentence-positions every slice is replayed into the one NewTokenWriter there.  `convert` is host only; -d: the
+// double array (ToDoubleArray, datok.go:82-238).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -133,6 +135,10 @@ static int cmd_tokenize(int argc, char **argv) {
   rc = dtk_stream_create(slice_bytes, 3, &st);
   uint32_t status = 0;
   bool read_failed = false;
+  const bool render = !tpos && !spos;
+  // (the rendered bytes need no token offsets on the host: the blocked form is the smaller download)
+  if (rc == DTK_OK && render && (rc = dtk_stream_set_render(st, 1, flags)) == DTK_OK)
+    rc = dtk_stream_set_result_fields(st, DTK_R_TOK_BYTE_BLK);
   if (rc == DTK_OK) {
     struct Ctx { FILE *f; datok::TokenWriter *w; bool is_matrix, *read_failed; };
     auto tw = datok::NewTokenWriter(std::cout, (datok::Bits)flags);
@@ -145,7 +151,8 @@ static int cmd_tokenize(int argc, char **argv) {
     };
     auto on_slice = [](void *u, const dtk_stream_slice *sl) -> int {
       Ctx *c = static_cast<Ctx *>(u);
-      datok::detail::replay_list(c->is_matrix, sl->text, sl->len, sl->view, 0, *c->w, sl->first, sl->last != 0);
+      if (sl->out) std::cout.write(reinterpret_cast<const char *>(sl->out), (std::streamsize)sl->out_len);
+      else datok::detail::replay_list(c->is_matrix, sl->text, sl->len, sl->view, 0, *c->w, sl->first, sl->last != 0);
       return DTK_OK;
     };
     rc = dtk_stream_run(st, m, rd, &c, 0, on_slice, &c, &status);

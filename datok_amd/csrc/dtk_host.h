@@ -217,6 +217,15 @@ struct dtk_batch {
   bool has_carry = false;
   DevArray<DtkLaneState> d_init_rec, d_open_fin;  // [1] each
   PinBuf h_init_rec;
+  // The slice's writer bytes in a position-free mode (dtk_stream_set_render, dtk_streamrender.hip): rendered on the
+  // download stream behind every packing of the event list, into sr_out (sr_cap bytes + the length word) and from
+  // there into its page-locked copy.  Both are sized from the totals before anything is enqueued.
+  bool sr_on = false, sr_last = false;
+  uint32_t sr_bits = 0, sr_first = 0, sr_cut = 0;
+  uint64_t sr_cap = 0;             // of the rendering under way
+  DevArray<uint8_t> d_sr_out;
+  DevArray<uint64_t> d_sr_ws;      // tile sums of tokens and entries, the entries' scan
+  PinBuf h_sr_out;
   uint32_t eager_fields = 0;  // the last run's k_to_host was asked for these (0: none); finish() decides whether it counts
   bool results_changed = false;  // finish() had to touch the result arrays after the run (repair, growth, EOT kernel, exact pass)
   Event ev_dl;                 // behind the batch's copies on the (possibly shared) download stream
@@ -234,6 +243,10 @@ int launch_to_host(dtk_batch *b);
 // does) and the record to start from (null: the stream's beginning).  batch_cut: the last run's cut block, behind finish().
 int batch_set_slice(dtk_batch *b, uint32_t open_slice, const DtkLaneState *carry);
 int batch_cut(dtk_batch *b, DtkStreamCut *out);
+// The slice's next download renders NewTokenWriter(w, bits)'s bytes for the calls in [first, cut] (last: the tail word's
+// too); batch_render_out: behind dtk_batch_result_host, the page-locked bytes.
+void batch_set_render(dtk_batch *b, bool on, uint32_t bits, uint32_t first, uint32_t cut, bool last);
+int batch_render_out(dtk_batch *b, const uint8_t **out, uint64_t *out_len);
 
 // The DTK_R_* arrays the last run wrote: DTK_NO_RUNE_OFFSETS / DTK_NO_BYTE_OFFSETS leave theirs alone.
 inline uint32_t run_fields(const dtk_batch *b) {

@@ -428,9 +428,34 @@ struct DtkEvListArgs {
   uint32_t *evl_bit;        // cap, device only: a row's global bit (what k_evl_rows searches)
 };
 
+// A stream slice's writer bytes in the position-free modes (dtk_streamrender.hip, dtk_stream_set_render): the one
+// document's tokens merged with its event list, on the download stream behind k_evl_*.
+struct DtkStreamRenderArgs {
+  uint32_t bits;               // DTK_TOKENS | DTK_SENTENCES
+  uint32_t with_tail;          // the stream's last slice: the tail word's SentenceEnd / TextEnd follow
+  const uint8_t *text;         // the window
+  uint32_t text_len;
+  struct DtkSym sym;           // base non-null only if the run saw invalid UTF-8
+  uint64_t n_tok;
+  const uint32_t *tok_bstart, *tok_bend;
+  const uint32_t *evl_pos;     // the list of document 0 (evl_off[0] == 0)
+  const uint8_t *evl_kind;
+  const uint32_t *evl_count;   // device word: its length
+  uint32_t evl_cap;            // rows the list's arrays hold; a longer list renders nothing (out_len = ~0)
+  const uint32_t *doc_tail;
+  uint32_t tok_tiles, ent_tiles;  // dtk_streamrender_tiles(n_tok) / (evl_cap)
+  uint64_t *tok_base, *ent_base;  // tok_tiles / ent_tiles: tile sums, then their exclusive scans
+  uint64_t *ew;                // evl_cap + 1: exclusive scan of the entries' bytes
+  uint8_t *out;                // cap bytes, 16-byte aligned, filled with '\n' in front of the launch
+  uint64_t cap;                // nothing is written at or behind it
+  uint64_t *out_len;           // device word: the exact length
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+uint32_t dtk_streamrender_tiles(uint64_t n);
+int dtk_launch_streamrender(const struct DtkStreamRenderArgs *args, void *stream);
 uint32_t dtk_evlist_tiles(uint64_t n_bits, uint32_t bit_words);
 int dtk_launch_evlist(const struct DtkEvListArgs *args, void *stream);
 int dtk_launch_to_host(const struct DtkToHostArgs *args, void *stream);

@@ -123,7 +123,53 @@ int pack_event_list(dtk_batch *b, uint64_t rows) {
   b->evl_copied = rows;
   return DTK_OK;
 }
+
+// dtk_stream_set_render: the slice's writer bytes, behind the list's kernels on the download stream and in front of
+// the copies.  The output is sized here, from what the host knows: a surface byte per window byte of the slice (three
+// where the run saw invalid UTF-8), a newline per token, SentenceEnd and TextEnd call, and the tail's two.
+int render_slice(dtk_batch *b) {
+  if (b->n_docs != 1 || b->total > 0xFFFFFFFFull) return DTK_E_STATE;
+  const uint64_t span = b->sr_cut > b->sr_first ? b->sr_cut - b->sr_first : 0;
+  const uint64_t cap = span * (b->n_invalid ? 3u : 1u) + b->totals.n_tokens + b->totals.n_sent + b->totals.n_texts + 2;
+  const uint64_t cap8 = (cap + 7u) & ~7ull;  // (the length word lies behind the bytes)
+  const uint64_t rows = b->evl_copied;
+  const uint32_t tt = dtk_streamrender_tiles(b->totals.n_tokens), et = dtk_streamrender_tiles(rows);
+  const uint64_t words = (uint64_t)tt + et + rows + 1;
+  int rc;
+  if ((rc = b->d_sr_out.fit(cap8 + 8, cap8 + cap8 / 8 + 264)) || (rc = b->d_sr_ws.fit(words, words + words / 8 + 16)) ||
+      (rc = b->h_sr_out.fit((size_t)(cap8 + 8))))
+    return rc;
+  DtkStreamRenderArgs a{};
+  a.bits = b->sr_bits & 3u; a.with_tail = b->sr_last ? 1u : 0u;
+  a.text = b->d_text; a.text_len = (uint32_t)b->total;
+  a.sym = sym_of(b); if (!b->n_invalid) a.sym.base = nullptr;
+  a.n_tok = b->totals.n_tokens; a.tok_bstart = b->d_bstart; a.tok_bend = b->d_bend;
+  a.evl_pos = b->d_evl_pos; a.evl_kind = b->d_evl_kind; a.evl_count = b->d_evl_cnt; a.evl_cap = (uint32_t)rows;
+  a.doc_tail = b->d_doc_tail;
+  a.tok_tiles = tt; a.ent_tiles = et;
+  a.tok_base = b->d_sr_ws; a.ent_base = a.tok_base + tt; a.ew = a.ent_base + et;
+  a.out = b->d_sr_out; a.cap = cap; a.out_len = reinterpret_cast<uint64_t *>(b->d_sr_out.p + cap8);
+  HIP_TRY(hipMemsetAsync(b->d_sr_out, '\n', cap8, b->dl_stream));  // every byte that is no surface byte
+  if (dtk_launch_streamrender(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "render slice");
+  HIP_TRY(hipMemcpyAsync(b->h_sr_out.p, b->d_sr_out, (size_t)(cap8 + 8), hipMemcpyDeviceToHost, b->dl_stream));
+  b->sr_cap = cap;
+  return DTK_OK;
+}
 }  // namespace
+
+void batch_set_render(dtk_batch *b, bool on, uint32_t bits, uint32_t first, uint32_t cut, bool last) {
+  b->sr_on = on; b->sr_bits = bits; b->sr_first = first; b->sr_cut = cut; b->sr_last = last;
+}
+
+int batch_render_out(dtk_batch *b, const uint8_t **out, uint64_t *out_len) {
+  if (!b->sr_on || !b->dl_begun || !b->dl_waited || !b->h_sr_out.p) return DTK_E_STATE;
+  const uint64_t cap8 = (b->sr_cap + 7u) & ~7ull;
+  const uint64_t n = *reinterpret_cast<const uint64_t *>(b->h_sr_out.as<uint8_t>() + cap8);
+  if (n > b->sr_cap) return DTK_E_CAPACITY;  // (more calls than the totals count: no regular slice)
+  *out = b->h_sr_out.as<uint8_t>();
+  *out_len = n;
+  return DTK_OK;
+}
 
 extern "C" int dtk_batch_result_device(dtk_batch *b, dtk_result_view *o) {
   if (!b || !o) return DTK_E_ARG;
@@ -219,6 +265,8 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
     tot[kPerEvent] = g_dbg.evl_cap >= 0 ? (uint64_t)g_dbg.evl_cap : tot[1] + tot[2];
     tot[kPerEvent] = std::max(tot[kPerEvent], b->evl_need);
     if ((rc = pack_event_list(b, tot[kPerEvent])) != DTK_OK) return rc;
+    // (a list packed again -- dtk_batch_result_host saw it outgrow its arrays -- is rendered again behind it)
+    if (b->sr_on && (rc = render_slice(b)) != DTK_OK) return rc;
   }
   const uint32_t blk_want = tot[0] ? want & kBlkFields : 0u;  // (no token: nothing to pack, empty arrays)
   if (blk_want && (rc = pack_blocked(b, blk_want, tot[0])) != DTK_OK) return rc;

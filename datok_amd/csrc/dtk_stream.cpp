@@ -91,30 +91,38 @@ extern "C" int dtk_transduce(const dtk_model *m, const uint8_t *text, size_t n, 
   return DTK_OK;
 }
 
-// One stream of any length through dtk_stream_run and the C++ mirror: every slice is replayed into the one stock
-// NewTokenWriter(w, bits) as it comes home.
+// One stream of any length through dtk_stream_run.  The position-free modes take the slices' bytes as the device
+// rendered them; the position modes replay every slice into the one stock NewTokenWriter(w, bits) of the C++ mirror.
 extern "C" int dtk_stream_transduce(dtk_stream *s, const dtk_model *m, dtk_read_fn read_fn, void *read_user, uint32_t bits,
                                     char **out, size_t *out_len, uint32_t *status) {
   if (!s || !m || !read_fn || !out) return DTK_E_ARG;
   *out = nullptr;
+  const bool replay = (bits & (DTK_TOKEN_POS | DTK_SENTENCE_POS)) != 0;
+  int rc = dtk_stream_set_render(s, replay ? 0 : 1, bits & (uint32_t)(DTK_TOKENS | DTK_SENTENCES));
+  if (rc != DTK_OK) return rc;
   std::ostringstream os;
+  std::string str;
   auto tw = datok::NewTokenWriter(os, (datok::Bits)bits);
-  struct Ctx { datok::TokenWriter *w; bool is_matrix; } c{tw.get(), std::strcmp(dtk_model_type(m), "MATOK") == 0};
+  struct Ctx { datok::TokenWriter *w; bool is_matrix; std::string *bytes; }
+      c{tw.get(), std::strcmp(dtk_model_type(m), "MATOK") == 0, replay ? nullptr : &str};
   auto on_slice = [](void *u, const dtk_stream_slice *sl) -> int {
     Ctx *c = static_cast<Ctx *>(u);
-    datok::detail::replay_list(c->is_matrix, sl->text, sl->len, sl->view, 0, *c->w, sl->first, sl->last != 0);
+    if (c->bytes) c->bytes->append(reinterpret_cast<const char *>(sl->out), (size_t)sl->out_len);
+    else datok::detail::replay_list(c->is_matrix, sl->text, sl->len, sl->view, 0, *c->w, sl->first, sl->last != 0);
     return DTK_OK;
   };
   uint32_t st = 0;
-  const int rc = dtk_stream_run(s, m, read_fn, read_user, bits & DTK_NEWLINE_AFTER_EOT, on_slice, &c, &st);
+  rc = dtk_stream_run(s, m, read_fn, read_user, bits & DTK_NEWLINE_AFTER_EOT, on_slice, &c, &st);
   if (rc != DTK_OK) return rc;
-  tw->Flush();
+  if (replay) {
+    tw->Flush();
+    str = os.str();
+  }
   if (status) {
     // an empty text only breaks the position modes (token_writer.go:108,135,145)
     *status = st;
-    if (!(bits & (DTK_TOKEN_POS | DTK_SENTENCE_POS))) *status &= ~(uint32_t)DTK_ST_EMPTY_TEXT;
+    if (!replay) *status &= ~(uint32_t)DTK_ST_EMPTY_TEXT;
   }
-  const std::string str = os.str();
   char *p = (char *)malloc(str.size() + 1);
   if (!p) return DTK_E_NOMEM;
   memcpy(p, str.data(), str.size());

@@ -22,6 +22,8 @@ struct dtk_stream {
   uint64_t S = 0;
   uint32_t depth = 0;
   uint32_t fields = kForced | DTK_R_TOK_BYTE;
+  bool render = false;        // dtk_stream_set_render: every slice's writer bytes come with it
+  uint32_t render_bits = 0;
   Stream s_up, s_run, s_down;
   std::vector<dtk_batch *> slots;
   std::vector<std::unique_ptr<PinBuf>> buf;  // depth x (S + T)
@@ -80,6 +82,14 @@ extern "C" int dtk_stream_set_result_fields(dtk_stream *s, uint32_t fields) {
     if (rc != DTK_OK) return rc;
   }
   s->fields = fields;
+  return DTK_OK;
+}
+
+extern "C" int dtk_stream_set_render(dtk_stream *s, int on, uint32_t bits) {
+  // (the position modes keep writer state across cuts: the host writer's, through the replay)
+  if (!s || (bits & ~(uint32_t)(DTK_TOKENS | DTK_SENTENCES | DTK_NEWLINE_AFTER_EOT))) return DTK_E_ARG;
+  s->render = on != 0;
+  s->render_bits = bits & (uint32_t)(DTK_TOKENS | DTK_SENTENCES);
   return DTK_OK;
 }
 
@@ -166,6 +176,7 @@ struct Run {
       carry = DtkLaneState{x.c.p, x.c.t, x.c.aux, x.c.flags};
       have_carry = true;
     }
+    batch_set_render(b, s->render, s->render_bits, x.first, x.ended ? len[x.slot] : x.c.cut, x.ended);
     return dtk_batch_download_begin(b);
   }
   // hands the slice over (its successor may be walking meanwhile)
@@ -191,6 +202,7 @@ struct Run {
     const uint64_t nt = sl.view.tok_off[1], nx = sl.view.text_off[1];
     const uint64_t n_teot = nx - ((x.ended && (sl.view.doc_tail[0] & DTK_TAIL_E)) ? 1u : 0u);
     has_tok = n_teot ? nt > sl.view.text_tok_end[n_teot - 1] : (has_tok || nt > 0);
+    if (s->render && (rc = batch_render_out(b, &sl.out, &sl.out_len)) != DTK_OK) return rc;
     return slice_fn ? slice_fn(slice_user, &sl) : DTK_OK;
   }
 };
@@ -242,6 +254,7 @@ extern "C" int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn rea
     if (r.touched[q]) {
       (void)dtk_batch_sync(s->slots[q]);
       (void)batch_set_slice(s->slots[q], 0u, nullptr);
+      batch_set_render(s->slots[q], false, 0u, 0u, 0u, false);
     }
   if (status) *status = r.status;
   return rc;

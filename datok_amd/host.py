@@ -228,12 +228,14 @@ def replay_list(is_matrix, text: bytes, evl_pos, evl_kind, tail, tok_bstart, tok
 class SliceView:
     """One slice of a stream (dtk_stream_slice, datok_gpu.h) in host arrays.  All positions are relative to the
     slice's window `text`, whose byte 0 is stream byte `base`: the slice's calls begin with the reference's window
-    start (buffer[0]) at `first` and end at `cut`; `tail` (doc_tail) counts on the `last` slice only."""
-    __slots__ = ("base", "first", "cut", "text", "last", "status", "tok_bstart", "tok_bend", "evl_pos", "evl_kind", "tail")
+    start (buffer[0]) at `first` and end at `cut`; `tail` (doc_tail) counts on the `last` slice only.  `out`: the bytes
+    a stock writer writes for the slice's calls as the device rendered them (Stream.set_render), else None."""
+    __slots__ = ("base", "first", "cut", "text", "last", "status", "tok_bstart", "tok_bend", "evl_pos", "evl_kind", "tail",
+                 "out")
 
     def __init__(self, **kw):
         for k in self.__slots__:
-            setattr(self, k, kw.get(k, 0))
+            setattr(self, k, kw.get(k, None if k == "out" else 0))
 
 
 def slice_calls(is_matrix, sl: SliceView):
@@ -717,6 +719,13 @@ class Stream:
         offsets, the texts and the status always come."""
         check(lib().dtk_stream_set_result_fields(self._h, int(fields)), "dtk_stream_set_result_fields")
 
+    def set_render(self, bits):
+        """Every slice's SliceView.out: the bytes a stock NewTokenWriter(w, bits) writes for its calls, rendered on the
+        device.  bits: TOKENS, SENTENCES, NEWLINE_AFTER_EOT (no effect); a position flag is E_ARG (those modes keep
+        writer state across cuts: replay_slice).  None turns rendering off."""
+        check(lib().dtk_stream_set_render(self._h, 0 if bits is None else 1, 0 if bits is None else int(bits)),
+              "dtk_stream_set_render")
+
     @staticmethod
     def _reader_fn(reader, err):
         if not hasattr(reader, "read"):
@@ -737,8 +746,9 @@ class Stream:
         return _lib.READ_FN(rd)
 
     def transduce(self, tok, reader, flags=SIMPLE):
-        """dtk_stream_transduce: what the reference writes for the stream with a stock NewTokenWriter(w, flags), every
-        slice replayed into the one writer of the C++ mirror.  Returns (output, status)."""
+        """dtk_stream_transduce: what the reference writes for the stream with a stock NewTokenWriter(w, flags) -- the
+        slices' bytes as the device rendered them, or with a position flag every slice replayed into the one writer of
+        the C++ mirror.  Returns (output, status)."""
         err = []
         out, n, st = C.c_void_p(), C.c_size_t(), C.c_uint32()
         rc = lib().dtk_stream_transduce(self._h, tok._h, self._reader_fn(reader, err), None, int(flags), C.byref(out),
@@ -792,7 +802,8 @@ def _slice_view(s) -> SliceView:
     return SliceView(base=int(s.base), first=int(s.first), cut=int(s.cut), last=int(s.last), status=int(s.status),
                      text=C.string_at(s.text, int(s.len)) if s.len else b"",
                      tok_bstart=bs, tok_bend=be, evl_pos=arr(v.evl_pos, ne, np.uint32)[int(off[0]):],
-                     evl_kind=arr(v.evl_kind, ne, np.uint8)[int(off[0]):], tail=int(arr(v.doc_tail, 1, np.uint32)[0]))
+                     evl_kind=arr(v.evl_kind, ne, np.uint8)[int(off[0]):], tail=int(arr(v.doc_tail, 1, np.uint32)[0]),
+                     out=C.string_at(s.out, int(s.out_len)) if s.out else None)
 
 
 def _slice_callback(on_slice, doc_off, err):

@@ -454,8 +454,11 @@ int dtk_pipeline_run(dtk_pipeline *p, const dtk_model *m, const uint8_t *text, c
  *        slice_fn gets the slices in order on the calling thread.  All positions of `view` (tok_bstart / tok_bend or the
  *      blocked form, evl_pos or the bitmaps, doc_tail) are relative to the window, whose byte 0 is stream byte `base`;
  *      a replay starts with the window start (buffer[0] of the reference) at `first`.  The writer's rune offsets and
- *      sentence list run across cuts (posC, sentB, init of token_writer.go:38-42): they are the host writer's that the
- *      replay feeds, as in the reference -- tok_rstart / tok_rend / sent of a slice's view are not delivered.
+ *      sentence list run across cuts (posC, sentB, init of token_writer.go:38-42) and are read in the position modes
+ *      only: TOKEN_POS and SENTENCE_POS are the host writer's that the replay feeds, as in the reference -- tok_rstart /
+ *      tok_rend / sent of a slice's view are not delivered, and dtk_stream_set_result_fields rejects the rune fields.
+ *      In the four position-free modes (TOKENS, SENTENCES, both, neither; NEWLINE_AFTER_EOT changes nothing there) the
+ *      writer is stateless, and the device renders a slice's bytes (dtk_stream_set_render: `out` / `out_len`).
  *        *status: the OR of the slices' status bits; DTK_ST_EMPTY_TEXT is decided for the stream (a text may span cuts).
  *      A slice that needs the exact pass ends the run with DTK_E_IRREGULAR. ---- */
 typedef struct dtk_stream dtk_stream;
@@ -468,6 +471,8 @@ typedef struct {
   uint32_t status;     /* the slice's DTK_ST_* bits, DTK_ST_EMPTY_TEXT decided with what the stream carried in */
   const uint8_t *text; /* the window's bytes (page-locked host memory), valid until slice_fn returns */
   dtk_result_view view;/* host pointers, one document; valid until slice_fn returns */
+  const uint8_t *out;  /* dtk_stream_set_render: what NewTokenWriter(w, bits) writes for this slice's calls (page-locked */
+  uint64_t out_len;    /* host memory, valid until slice_fn returns); NULL / 0 when rendering is off */
 } dtk_stream_slice;
 typedef size_t (*dtk_read_fn)(void *user, uint8_t *buf, size_t cap);       /* fills up to cap bytes; 0: end of the stream */
 typedef int (*dtk_stream_slice_fn)(void *user, const dtk_stream_slice *s); /* DTK_OK to go on */
@@ -480,12 +485,20 @@ int dtk_stream_set_chunking(dtk_stream *s, uint32_t chunk_bytes, uint32_t warm_b
 /* The DTK_R_* arrays of every slice's view.  DTK_R_CSR, DTK_R_STATUS, DTK_R_TEXTS and DTK_R_EVENT_LIST always come;
  * the token bytes must be among them as DTK_R_TOK_BYTE or DTK_R_TOK_BYTE_BLK (else DTK_E_ARG).  Default: DTK_R_TOK_BYTE. */
 int dtk_stream_set_result_fields(dtk_stream *s, uint32_t fields);
+/* on != 0: every slice also brings the bytes a stock NewTokenWriter(w, bits) writes for its calls, rendered on the device
+ * behind the slice's event list and in front of its copies (about one more byte per input byte on the link); the
+ * slices' bytes one after the other are the stream's.  bits: DTK_TOKENS, DTK_SENTENCES, and DTK_NEWLINE_AFTER_EOT, which is
+ * accepted and changes nothing; a position bit (their writer state runs across cuts) or an unknown bit: DTK_E_ARG.  The
+ * view's arrays are delivered as before.  A token that the reference cannot print (DTK_ST_BAD_OFFSET) prints empty. */
+int dtk_stream_set_render(dtk_stream *s, int on, uint32_t bits);
 /* flags: DTK_NEWLINE_AFTER_EOT is accepted and changes nothing here (it only moves the writer's rune offsets).  Short
  * reads are retried until a buffer is full; read_fn is not called again after it has returned 0. */
 int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn read_fn, void *read_user, uint32_t flags,
                    dtk_stream_slice_fn slice_fn, void *slice_user, uint32_t *status);
-/* What the reference writes to w for the stream with a stock NewTokenWriter(w, bits) -- dtk_transduce_replay for a
- * reader of any length: every slice is replayed into the one writer of the C++ mirror (include/datok.hpp).  *out is
+/* What the reference writes to w for the stream with a stock NewTokenWriter(w, bits), for a reader of any length.
+ * Without a position bit the slices' rendered bytes are appended (dtk_stream_set_render is turned on with `bits`, and
+ * stays so); with TOKEN_POS or SENTENCE_POS rendering is turned off and every slice is replayed into the one writer of
+ * the C++ mirror (include/datok.hpp), as dtk_transduce_replay does for a document.  *out is
  * malloc'd (the whole output: a caller that must bound that too writes from slice_fn, as `datok tokenize` does); free
  * with dtk_free. */
 int dtk_stream_transduce(dtk_stream *s, const dtk_model *m, dtk_read_fn read_fn, void *read_user, uint32_t bits,

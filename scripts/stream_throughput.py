@@ -3,7 +3,8 @@
 
 Leg 1 (stream): a single stream of --gib GiB from a cyclic reader -- once bare running text, once with an EOT every 4 KiB
 -- through dtk_stream_run with R_TOK_BYTE_BLK | R_EVENT_LIST | R_CSR | R_STATUS, with an empty slice callback and with
-the C++ replay of every slice into a TOKENS | SENTENCES writer (dtk_stream_transduce).
+dtk_stream_transduce in mode 3 (the C++ replay of every slice into a TOKENS | SENTENCES writer when profiles/stream.txt
+was taken; the bytes the device renders since dtk_stream_set_render -- scripts/stream_render.py measures both).
 Leg 2 (pipeline): the same bytes as 4 KiB documents through dtk_pipeline_run with the same fields and slice size, on the
 same session.  Legs alternate; medians of --reps runs.  Reports both rates, their ratio, and the stream's token count
 against the oracle's (one period and two periods of the cyclic text: the count of N periods follows).  No threshold.

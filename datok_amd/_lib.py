@@ -35,6 +35,7 @@ EXPORTS = [
     "dtk_multi_create", "dtk_multi_free", "dtk_multi_type", "dtk_multi_set_result_fields", "dtk_multi_set_chunking", "dtk_multi_run",
     "dtk_stream_create", "dtk_stream_free", "dtk_stream_set_chunking", "dtk_stream_set_result_fields", "dtk_stream_run",
     "dtk_stream_transduce", "dtk_stream_set_render",
+    "dtk_stream_set_position_render", "dtk_stream_positions", "dtk_stream_emit",
 ]
 
 
@@ -78,6 +79,19 @@ class StreamSlice(C.Structure):
                 ("out", C.c_void_p), ("out_len", C.c_uint64)]
 
 
+class StreamCarry(C.Structure):
+    """dtk_stream_carry: the position writer's state at a cut."""
+    _fields_ = [("posC", C.c_int64), ("sentB", C.c_uint32), ("init", C.c_uint32), ("pos_nonempty", C.c_uint32),
+                ("sent_nonempty", C.c_uint32)]
+
+
+class StreamPos(C.Structure):
+    """dtk_stream_pos: what belongs to a slice's `out` in a position mode (dtk_stream_positions)."""
+    _fields_ = [("splice_pos", C.c_uint64), ("splice_sent", C.c_uint64), ("open_pos", C.c_void_p), ("open_pos_len", C.c_uint64),
+                ("open_sent", C.c_void_p), ("open_sent_len", C.c_uint64), ("carry_in", StreamCarry), ("carry_out", StreamCarry)]
+
+
+WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 READ_FN = C.CFUNCTYPE(C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t)
 STREAM_SLICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(StreamSlice))
 
@@ -191,6 +205,9 @@ def lib():
     L.dtk_stream_set_chunking.argtypes = [vp, u32, u32]
     L.dtk_stream_set_result_fields.argtypes = [vp, u32]
     L.dtk_stream_set_render.argtypes = [vp, C.c_int, u32]
+    L.dtk_stream_set_position_render.argtypes = [vp, C.c_int, u32]
+    L.dtk_stream_positions.argtypes = [vp, C.POINTER(StreamPos)]
+    L.dtk_stream_emit.argtypes = [vp, WRITE_FN, vp]
     L.dtk_stream_run.argtypes = [vp, vp, READ_FN, vp, u32, STREAM_SLICE_FN, vp, C.POINTER(u32)]
     L.dtk_stream_transduce.argtypes = [vp, vp, READ_FN, vp, u32, C.POINTER(vp), C.POINTER(sz), C.POINTER(u32)]
     for f in (L.dtk_blk_start, L.dtk_blk_end):

@@ -6,10 +6,11 @@
 //
 // `tokenize` reads its input as ONE stream of any length (cmd/datok.go:120-133), U+0004 ends a text inside it: the
 // stream is read and walked on the GPU in slices of --slice-bytes (default 16 MiB, a multiple of 256 from 16 384 on;
-// dtk_stream_run: the input is never held whole).  Without a position flag every slice's bytes are rendered on the
-// device (dtk_stream_set_render) and written to standard output as they come home; with --token-positions or
-// --sentence-positions every slice is replayed into the one NewTokenWriter there.  `convert` is host only; -d: the
-// double array (ToDoubleArray, datok.go:82-238).
+// dtk_stream_run: the input is never held whole).  Every slice's bytes are rendered on the device and written to standard
+// output as they come home: dtk_stream_set_render without a position flag; with --token-positions or
+// --sentence-positions dtk_stream_set_position_render, and dtk_stream_emit puts a text's position line together across
+// slices (it holds the line of the text that is open: memory grows with a text, not with the stream).  `convert` is
+// host only; -d: the double array (ToDoubleArray, datok.go:82-238).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,7 +27,10 @@ static int usage(const char *msg) {
                "  convert --foma=STRING --tokenizer=STRING\n"
                "    Convert a compiled foma FST file to a Matrix or Double Array tokenizer\n\n"
                "  tokenize --tokenizer=STRING [--slice-bytes=N] <input>\n    Tokenize a text (a file, or - for STDIN), read as one\n"
-               "    stream in slices of N bytes (default 16777216; a multiple of 256, at least 16384)\n");
+               "    stream in slices of N bytes (default 16777216; a multiple of 256, at least 16384)\n"
+               "    --[no-]tokens --[no-]sentences -p, --token-positions --sentence-positions --newline-after-eot\n"
+               "    Every mode is rendered on the GPU slice by slice; with positions the line of the text that is\n"
+               "    open is held on the host until its end (U+0004) arrives\n");
   return 1;
 }
 
@@ -135,14 +139,13 @@ static int cmd_tokenize(int argc, char **argv) {
   rc = dtk_stream_create(slice_bytes, 3, &st);
   uint32_t status = 0;
   bool read_failed = false;
-  const bool render = !tpos && !spos;
+  const bool positions = tpos || spos;
   // (the rendered bytes need no token offsets on the host: the blocked form is the smaller download)
-  if (rc == DTK_OK && render && (rc = dtk_stream_set_render(st, 1, flags)) == DTK_OK)
+  if (rc == DTK_OK && (rc = positions ? dtk_stream_set_position_render(st, 1, flags) : dtk_stream_set_render(st, 1, flags)) == DTK_OK)
     rc = dtk_stream_set_result_fields(st, DTK_R_TOK_BYTE_BLK);
   if (rc == DTK_OK) {
-    struct Ctx { FILE *f; datok::TokenWriter *w; bool is_matrix, *read_failed; };
-    auto tw = datok::NewTokenWriter(std::cout, (datok::Bits)flags);
-    Ctx c{f, tw.get(), std::strcmp(dtk_model_type(m), "MATOK") == 0, &read_failed};
+    struct Ctx { FILE *f; dtk_stream *st; bool positions, *read_failed; };
+    Ctx c{f, st, positions, &read_failed};
     auto rd = [](void *u, uint8_t *buf, size_t cap) -> size_t {
       Ctx *c = static_cast<Ctx *>(u);
       const size_t k = std::fread(buf, 1, cap, c->f);
@@ -151,12 +154,14 @@ static int cmd_tokenize(int argc, char **argv) {
     };
     auto on_slice = [](void *u, const dtk_stream_slice *sl) -> int {
       Ctx *c = static_cast<Ctx *>(u);
-      if (sl->out) std::cout.write(reinterpret_cast<const char *>(sl->out), (std::streamsize)sl->out_len);
-      else datok::detail::replay_list(c->is_matrix, sl->text, sl->len, sl->view, 0, *c->w, sl->first, sl->last != 0);
-      return DTK_OK;
+      const dtk_write_fn wr = [](void *, const uint8_t *p, size_t n) -> int {
+        std::cout.write(reinterpret_cast<const char *>(p), (std::streamsize)n);
+        return DTK_OK;
+      };
+      return c->positions ? dtk_stream_emit(c->st, wr, nullptr) : wr(nullptr, sl->out, (size_t)sl->out_len);
     };
-    rc = dtk_stream_run(st, m, rd, &c, 0, on_slice, &c, &status);
-    tw->Flush();
+    rc = dtk_stream_run(st, m, rd, &c, flags & DTK_NEWLINE_AFTER_EOT, on_slice, &c, &status);
+    std::cout.flush();
   }
   dtk_stream_free(st);
   if (f != stdin) std::fclose(f);

@@ -6,6 +6,7 @@
 
 #include <type_traits>
 
+#include "dtk_decimal.h"
 #include "dtk_internal.h"
 
 #define WAVE 64

@@ -39,6 +39,8 @@ struct DtkDebug {
                          // k_pack_blk is launched, so that ordinary text reaches the fallback to the 32-bit arrays
   int evl_cap = -1;      // entries the copies of DTK_R_EVENT_LIST are first sized for, in place of n_sent + n_texts (-1: off),
                          // so that ordinary text reaches the second download of a list that outgrew the bound
+  long long sp_posc0 = 0; // posC in front of a stream's first slice in a position mode (dtk_stream_run reads it once, at its
+                         // start): integers beyond 2^32 and of 11 digits from a stream of a few hundred bytes
 };
 extern DtkDebug g_dbg;
 
@@ -226,6 +228,13 @@ struct dtk_batch {
   DevArray<uint8_t> d_sr_out;
   DevArray<uint64_t> d_sr_ws;      // tile sums of tokens and entries, the entries' scan
   PinBuf h_sr_out;
+  // ... and in a position mode (dtk_stream_set_position_render, dtk_streampos.hip): the same buffers, the trailer block
+  // behind the bytes; the writer's state comes from one of the stream's carry slots and goes into another
+  bool sp_on = false, sp_matrix = false;
+  uint32_t sp_digits = 0;          // no integer of the slice has more bytes (the stream's bound)
+  const DtkPosCarry *sp_carry_in = nullptr;
+  DtkPosCarry *sp_carry_out = nullptr;
+  DevArray<uint64_t> d_sp_ws;
   uint32_t eager_fields = 0;  // the last run's k_to_host was asked for these (0: none); finish() decides whether it counts
   bool results_changed = false;  // finish() had to touch the result arrays after the run (repair, growth, EOT kernel, exact pass)
   Event ev_dl;                 // behind the batch's copies on the (possibly shared) download stream
@@ -247,6 +256,10 @@ int batch_cut(dtk_batch *b, DtkStreamCut *out);
 // too); batch_render_out: behind dtk_batch_result_host, the page-locked bytes.
 void batch_set_render(dtk_batch *b, bool on, uint32_t bits, uint32_t first, uint32_t cut, bool last);
 int batch_render_out(dtk_batch *b, const uint8_t **out, uint64_t *out_len);
+// The same in a position mode: bits holds all five writer bits; on == false returns to batch_set_render's renderer.
+// batch_pos_out: the page-locked bytes and the trailer block behind them (DTK_E_CAPACITY / DTK_E_IRREGULAR as it says).
+void batch_set_pos_render(dtk_batch *b, bool on, bool is_matrix, uint32_t digits, const DtkPosCarry *carry_in, DtkPosCarry *carry_out);
+int batch_pos_out(dtk_batch *b, const uint8_t **out, const DtkPosTrailer **trailer);
 
 // The DTK_R_* arrays the last run wrote: DTK_NO_RUNE_OFFSETS / DTK_NO_BYTE_OFFSETS leave theirs alone.
 inline uint32_t run_fields(const dtk_batch *b) {

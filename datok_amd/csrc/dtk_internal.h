@@ -451,9 +451,78 @@ struct DtkStreamRenderArgs {
   uint64_t *out_len;           // device word: the exact length
 };
 
+// The same in a mode with TOKEN_POS / SENTENCE_POS (dtk_streampos.hip, dtk_stream_set_position_render).  The writer's
+// state in front of and behind a slice: what crosses a cut (token_writer.go:38-42; pos.back() == posC whenever pos is
+// not empty, and the integers already collected are bytes of a line the host holds).
+struct DtkPosCarry {
+  int64_t posC;                            // Go's int
+  uint32_t sentB, init, pos_nonempty, sent_nonempty;
+};
+// what goes home behind the bytes in one block
+struct DtkPosTrailer {
+  uint64_t out_len;                        // ~0: the list did not fit its arrays, nothing was rendered
+  uint64_t open_pos_len, open_sent_len;    // the fragments of the text open at the cut: behind out, in this order
+  uint64_t splice_pos, splice_sent;        // offsets into out, ~0: none
+  struct DtkPosCarry carry_in, carry_out;
+  uint32_t flags;                          // 1: a token with rend == 0 under NEWLINE_AFTER_EOT (the literal rule would fire again)
+  uint32_t pad;
+};
+// the scanning blocks' results, for the kernels behind them
+struct DtkPosHdr {
+  uint64_t tot[3];                         // bytes of all tokens: surfaces, position integers, sentence integers
+  uint64_t ent_tot;                        // bytes of all entries
+  uint64_t head_w;                         // sentence integers of SentenceEnd calls in front of the first token and TextEnd
+  uint32_t head_n, n_te;                   // their number; TextEnd entries of the list
+  uint32_t flags, pad;
+};
+struct DtkStreamPosArgs {
+  uint32_t bits;               // the five writer bits, one of TOKEN_POS / SENTENCE_POS among them
+  uint32_t with_tail;
+  uint32_t is_matrix;          // the window start follows a TextEnd fired by an EOT (matrix.go:601)
+  uint32_t first;              // window byte where the slice's calls begin
+  const uint8_t *text;
+  uint32_t text_len;
+  struct DtkSym sym;           // base non-null only if the run saw invalid UTF-8
+  uint64_t n_tok;
+  const uint32_t *tok_bstart, *tok_bend;
+  const uint32_t *evl_pos;
+  const uint8_t *evl_kind;
+  const uint32_t *evl_count;
+  uint32_t evl_cap;
+  const uint32_t *doc_tail;
+  uint32_t tok_tiles, ent_tiles;
+  const struct DtkPosCarry *carry_in;   // device: the predecessor's carry_out
+  struct DtkPosCarry *carry_out;        // device: another slot
+  // workspace (dtk_streampos_ws gives the sizes)
+  struct DtkPosHdr *hdr;
+  uint64_t *ent_base;          // ent_tiles: tile sums, then their exclusive scans (twice: counts, then bytes)
+  uint64_t *cnt;               // evl_cap + 1: SentenceEnd calls (low word) and TextEnd entries (high word) in front of an entry
+  uint64_t *ew;                // evl_cap + 1: exclusive scan of the entries' bytes
+  uint64_t *ent_pre;           // evl_cap: an entry's bytes in front of a token on its cursor
+  uint32_t *te_idx;            // evl_cap: the entry of the c-th TextEnd
+  uint64_t *seg_pos, *seg_sent;   // evl_cap + 2 each, per text of the slice: where its lines begin in the output
+  uint64_t *seg_pw0;           // ... the position-integer scan at its first token
+  int64_t *seg_sw0;            // ... the sentence-integer scan there (less the head's integers for text 0)
+  int64_t *tile_sum, *tile_in; // tok_tiles: a tile's segmented sum of rune counts; posC in front of the tile
+  uint32_t *tile_flag;         // tok_tiles: the tile has a token that begins a text
+  uint64_t *w_base;            // 3 * tok_tiles: tile sums of the three weights, then their exclusive scans
+  int64_t *rstart, *rend;      // n_tok
+  int32_t *tok_v;              // n_tok: runes a token adds to posC (less one where the newline rule fires)
+  uint32_t *tok_len;           // n_tok: runes of the surface
+  uint32_t *tok_meta;          // n_tok: SentenceEnd calls that read this token's end | begins a text << 30 | sentB << 31
+  uint32_t *tok_seg;           // n_tok: TextEnd entries in front of the token
+  uint32_t *w_in;              // 3 * n_tok: a weight's exclusive scan inside its tile
+  uint8_t *out;                // cap bytes, filled with '\n' in front of the launch
+  uint64_t cap;                // nothing is written at or behind it
+  struct DtkPosTrailer *trailer;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+int dtk_launch_streampos(const struct DtkStreamPosArgs *args, void *stream);
+int dtk_pos_trailer_check(const struct DtkPosTrailer *t, uint64_t cap);  // DTK_OK, DTK_E_CAPACITY or DTK_E_IRREGULAR
+uint64_t dtk_streampos_ws(struct DtkStreamPosArgs *args, uint64_t *ws);  // lays the workspace out (ws null: the size only), in 64-bit words
 uint32_t dtk_streamrender_tiles(uint64_t n);
 int dtk_launch_streamrender(const struct DtkStreamRenderArgs *args, void *stream);
 uint32_t dtk_evlist_tiles(uint64_t n_bits, uint32_t bit_words);

@@ -62,6 +62,10 @@ extern "C" int dtk_debug_configure(const char *key, const char *value) {
       {"ROUND_LIMIT", &g_dbg.round_limit, false}, {"DEBUG_REPAIR", &g_dbg.debug_repair, true},
       {"BLK_SPAN", &g_dbg.blk_span, false}, {"EVL_CAP", &g_dbg.evl_cap, false}};
   if (strncmp(key, "DATOK_", 6) == 0) key += 6;
+  if (strcmp(key, "SP_POSC0") == 0) {  // (a 64-bit value)
+    g_dbg.sp_posc0 = value ? atoll(value) : 0;
+    return DTK_OK;
+  }
   for (const auto &e : tab)
     if (strcmp(key, e.name) == 0) {
       // (a flag is on by being named, as the environment variables were: `DATOK_NO_FUSED=` or `=1` both switch it on)

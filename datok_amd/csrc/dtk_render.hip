@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dtk_decimal.h"
 #include "dtk_internal.h"
 
 namespace {
@@ -19,21 +20,6 @@ namespace {
 constexpr uint32_t RB = 256;          // threads per block
 constexpr uint32_t RI = 4;            // items per thread
 constexpr uint32_t RTILE = RB * RI;   // items per block
-
-// strconv.Itoa: length and digits
-__device__ __forceinline__ uint32_t dec_len(int32_t v) {
-  const uint32_t neg = v < 0 ? 1u : 0u;
-  const uint32_t u = neg ? (uint32_t)(-(int64_t)v) : (uint32_t)v;
-  return 1u + (u >= 10u) + (u >= 100u) + (u >= 1000u) + (u >= 10000u) + (u >= 100000u) + (u >= 1000000u) +
-         (u >= 10000000u) + (u >= 100000000u) + (u >= 1000000000u) + neg;
-}
-
-__device__ __forceinline__ void dec_put(uint8_t *o, int32_t v, uint32_t n) {
-  uint32_t u = v < 0 ? (uint32_t)(-(int64_t)v) : (uint32_t)v;
-  uint32_t i = n;
-  do { o[--i] = (uint8_t)('0' + u % 10u); u /= 10u; } while (u != 0u && i > 0u);
-  if (v < 0) o[0] = '-';
-}
 
 struct Pair { uint64_t a, p; };
 

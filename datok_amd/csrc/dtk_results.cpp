@@ -155,10 +155,77 @@ int render_slice(dtk_batch *b) {
   b->sr_cap = cap;
   return DTK_OK;
 }
+
+// dtk_stream_set_position_render: the same place, dtk_streampos.hip.  The capacity is a bound the host can state before
+// anything is enqueued: the kernels render nothing for a list of more than `rows` entries, so
+// the slice has at most 2 * rows + 1 SentenceEnd calls and rows + 1 TextEnd calls; a token pushes two position
+// integers, and a sentence integer comes from a token behind such a call or from a SentenceEnd call; no integer has
+// more than sp_digits bytes.  The open fragments lie behind the output inside the same bound.
+int render_slice_pos(dtk_batch *b) {
+  if (b->n_docs != 1 || b->total > 0xFFFFFFFFull || !b->sp_carry_in || !b->sp_carry_out) return DTK_E_STATE;
+  const uint64_t span = b->sr_cut > b->sr_first ? b->sr_cut - b->sr_first : 0;
+  const uint64_t rows = b->evl_copied, nt = b->totals.n_tokens;
+  const uint64_t calls = 3 * rows + 2;
+  const uint64_t ints = ((b->sr_bits & DTK_TOKEN_POS) ? 2 * nt : 0) +
+                        ((b->sr_bits & DTK_SENTENCE_POS) ? std::min<uint64_t>(nt, calls + 1) + 2 * rows + 1 : 0);
+  const uint64_t cap = ((b->sr_bits & DTK_TOKENS) ? span * (b->n_invalid ? 3u : 1u) + nt : 0) + calls +
+                       ints * ((uint64_t)b->sp_digits + 1u) + 2 * (rows + 2);
+  const uint64_t cap8 = (cap + 7u) & ~7ull;
+  const uint64_t bytes = cap8 + sizeof(DtkPosTrailer);
+  DtkStreamPosArgs a{};
+  a.bits = b->sr_bits & 31u; a.with_tail = b->sr_last ? 1u : 0u; a.is_matrix = b->sp_matrix ? 1u : 0u; a.first = b->sr_first;
+  a.text = b->d_text; a.text_len = (uint32_t)b->total;
+  a.sym = sym_of(b); if (!b->n_invalid) a.sym.base = nullptr;
+  a.n_tok = nt; a.tok_bstart = b->d_bstart; a.tok_bend = b->d_bend;
+  a.evl_pos = b->d_evl_pos; a.evl_kind = b->d_evl_kind; a.evl_count = b->d_evl_cnt; a.evl_cap = (uint32_t)rows;
+  a.doc_tail = b->d_doc_tail;
+  a.tok_tiles = dtk_streamrender_tiles(nt); a.ent_tiles = dtk_streamrender_tiles(rows);
+  a.carry_in = b->sp_carry_in; a.carry_out = b->sp_carry_out;
+  const uint64_t words = dtk_streampos_ws(&a, nullptr);
+  int rc;
+  if ((rc = b->d_sr_out.fit(bytes, bytes + bytes / 8 + 264)) || (rc = b->d_sp_ws.fit(words, words + words / 8 + 16)) ||
+      (rc = b->h_sr_out.fit((size_t)bytes)))
+    return rc;
+  (void)dtk_streampos_ws(&a, b->d_sp_ws);
+  a.out = b->d_sr_out; a.cap = cap; a.trailer = reinterpret_cast<DtkPosTrailer *>(b->d_sr_out.p + cap8);
+  HIP_TRY(hipMemsetAsync(b->d_sr_out, '\n', cap8, b->dl_stream));  // every byte that is no surface byte and no integer's
+  if (dtk_launch_streampos(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "render slice positions");
+  HIP_TRY(hipMemcpyAsync(b->h_sr_out.p, b->d_sr_out, (size_t)bytes, hipMemcpyDeviceToHost, b->dl_stream));
+  b->sr_cap = cap;
+  return DTK_OK;
+}
 }  // namespace
 
 void batch_set_render(dtk_batch *b, bool on, uint32_t bits, uint32_t first, uint32_t cut, bool last) {
   b->sr_on = on; b->sr_bits = bits; b->sr_first = first; b->sr_cut = cut; b->sr_last = last;
+  b->sp_on = false;
+}
+
+void batch_set_pos_render(dtk_batch *b, bool on, bool is_matrix, uint32_t digits, const DtkPosCarry *carry_in, DtkPosCarry *carry_out) {
+  b->sp_on = on; b->sp_matrix = is_matrix; b->sp_digits = digits; b->sp_carry_in = carry_in; b->sp_carry_out = carry_out;
+}
+
+// What a trailer block that has come home says about its slice: never bytes that differ silently.
+extern "C" int dtk_pos_trailer_check(const DtkPosTrailer *t, uint64_t cap) {
+  if (!t) return DTK_E_ARG;
+  // (more calls than the bound counts -- a list longer than its arrays says so with out_len = ~0 --, or a tile of
+  //  tokens whose integers pass 2^32 bytes: no regular slice)
+  if (t->out_len > cap || t->open_pos_len > cap || t->open_sent_len > cap ||
+      t->out_len + t->open_pos_len + t->open_sent_len > cap || (t->flags & 2u))
+    return DTK_E_CAPACITY;
+  if (t->flags & 1u) return DTK_E_IRREGULAR;  // the newline rule would fire a second time: the exact pass's, from a carried record
+  return DTK_OK;
+}
+
+int batch_pos_out(dtk_batch *b, const uint8_t **out, const DtkPosTrailer **trailer) {
+  if (!b->sr_on || !b->sp_on || !b->dl_begun || !b->dl_waited || !b->h_sr_out.p) return DTK_E_STATE;
+  const uint64_t cap8 = (b->sr_cap + 7u) & ~7ull;
+  const DtkPosTrailer *t = reinterpret_cast<const DtkPosTrailer *>(b->h_sr_out.as<uint8_t>() + cap8);
+  const int rc = dtk_pos_trailer_check(t, b->sr_cap);
+  if (rc != DTK_OK) return rc;
+  *out = b->h_sr_out.as<uint8_t>();
+  *trailer = t;
+  return DTK_OK;
 }
 
 int batch_render_out(dtk_batch *b, const uint8_t **out, uint64_t *out_len) {
@@ -266,7 +333,7 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
     tot[kPerEvent] = std::max(tot[kPerEvent], b->evl_need);
     if ((rc = pack_event_list(b, tot[kPerEvent])) != DTK_OK) return rc;
     // (a list packed again -- dtk_batch_result_host saw it outgrow its arrays -- is rendered again behind it)
-    if (b->sr_on && (rc = render_slice(b)) != DTK_OK) return rc;
+    if (b->sr_on && (rc = b->sp_on ? render_slice_pos(b) : render_slice(b)) != DTK_OK) return rc;
   }
   const uint32_t blk_want = tot[0] ? want & kBlkFields : 0u;  // (no token: nothing to pack, empty arrays)
   if (blk_want && (rc = pack_blocked(b, blk_want, tot[0])) != DTK_OK) return rc;

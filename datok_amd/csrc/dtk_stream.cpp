@@ -91,37 +91,34 @@ extern "C" int dtk_transduce(const dtk_model *m, const uint8_t *text, size_t n, 
   return DTK_OK;
 }
 
-// One stream of any length through dtk_stream_run.  The position-free modes take the slices' bytes as the device
-// rendered them; the position modes replay every slice into the one stock NewTokenWriter(w, bits) of the C++ mirror.
+// One stream of any length through dtk_stream_run: the slices' bytes as the device rendered them, in a position mode
+// with the held prefixes spliced in (dtk_stream_emit).
 extern "C" int dtk_stream_transduce(dtk_stream *s, const dtk_model *m, dtk_read_fn read_fn, void *read_user, uint32_t bits,
                                     char **out, size_t *out_len, uint32_t *status) {
   if (!s || !m || !read_fn || !out) return DTK_E_ARG;
   *out = nullptr;
-  const bool replay = (bits & (DTK_TOKEN_POS | DTK_SENTENCE_POS)) != 0;
-  int rc = dtk_stream_set_render(s, replay ? 0 : 1, bits & (uint32_t)(DTK_TOKENS | DTK_SENTENCES));
+  const bool positions = (bits & (DTK_TOKEN_POS | DTK_SENTENCE_POS)) != 0;
+  int rc = positions ? dtk_stream_set_position_render(s, 1, bits)
+                     : dtk_stream_set_render(s, 1, bits & (uint32_t)(DTK_TOKENS | DTK_SENTENCES));
   if (rc != DTK_OK) return rc;
-  std::ostringstream os;
   std::string str;
-  auto tw = datok::NewTokenWriter(os, (datok::Bits)bits);
-  struct Ctx { datok::TokenWriter *w; bool is_matrix; std::string *bytes; }
-      c{tw.get(), std::strcmp(dtk_model_type(m), "MATOK") == 0, replay ? nullptr : &str};
+  struct Ctx { dtk_stream *s; std::string *bytes; bool positions; } c{s, &str, positions};
   auto on_slice = [](void *u, const dtk_stream_slice *sl) -> int {
     Ctx *c = static_cast<Ctx *>(u);
-    if (c->bytes) c->bytes->append(reinterpret_cast<const char *>(sl->out), (size_t)sl->out_len);
-    else datok::detail::replay_list(c->is_matrix, sl->text, sl->len, sl->view, 0, *c->w, sl->first, sl->last != 0);
-    return DTK_OK;
+    const dtk_write_fn append = [](void *v, const uint8_t *p, size_t n) -> int {
+      static_cast<std::string *>(v)->append(reinterpret_cast<const char *>(p), n);
+      return DTK_OK;
+    };
+    return c->positions ? dtk_stream_emit(c->s, append, c->bytes) : append(c->bytes, sl->out, (size_t)sl->out_len);
   };
   uint32_t st = 0;
   rc = dtk_stream_run(s, m, read_fn, read_user, bits & DTK_NEWLINE_AFTER_EOT, on_slice, &c, &st);
+  if (positions) (void)dtk_stream_set_position_render(s, 0, 0);  // (a later plain run brings no bytes)
   if (rc != DTK_OK) return rc;
-  if (replay) {
-    tw->Flush();
-    str = os.str();
-  }
   if (status) {
     // an empty text only breaks the position modes (token_writer.go:108,135,145)
     *status = st;
-    if (!replay) *status &= ~(uint32_t)DTK_ST_EMPTY_TEXT;
+    if (!positions) *status &= ~(uint32_t)DTK_ST_EMPTY_TEXT;
   }
   char *p = (char *)malloc(str.size() + 1);
   if (!p) return DTK_E_NOMEM;

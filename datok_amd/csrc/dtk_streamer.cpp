@@ -7,6 +7,7 @@
 // so no stale record is ever fed forward.
 #include <cstring>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "dtk_host.h"
@@ -24,6 +25,19 @@ struct dtk_stream {
   uint32_t fields = kForced | DTK_R_TOK_BYTE;
   bool render = false;        // dtk_stream_set_render: every slice's writer bytes come with it
   uint32_t render_bits = 0;
+  // dtk_stream_set_position_render: the same in a mode with TOKEN_POS / SENTENCE_POS.  The writer's state is chained
+  // on the device: slice k reads carry slot k % (depth + 1) and writes the next one -- never the slot it read, and a
+  // slot is written again only by slice k + depth, which takes the batch that slice k has left by then.
+  bool pos_render = false;
+  uint32_t pos_bits = 0;      // all five writer bits
+  DevArray<DtkPosCarry> d_carry;  // depth + 1
+  // The held prefixes (dtk_stream_emit): the integers of the text that is open at the last cut, as the bytes of its
+  // TOKEN_POS / SENTENCE_POS line so far.  They grow with the length of a text, as the reference's pos[] / sent[] do.
+  std::string held_pos, held_sent;
+  // the slice being delivered, inside slice_fn
+  const uint8_t *cur_out = nullptr;
+  const DtkPosTrailer *cur = nullptr;
+  bool cur_emitted = false;
   Stream s_up, s_run, s_down;
   std::vector<dtk_batch *> slots;
   std::vector<std::unique_ptr<PinBuf>> buf;  // depth x (S + T)
@@ -90,6 +104,59 @@ extern "C" int dtk_stream_set_render(dtk_stream *s, int on, uint32_t bits) {
   if (!s || (bits & ~(uint32_t)(DTK_TOKENS | DTK_SENTENCES | DTK_NEWLINE_AFTER_EOT))) return DTK_E_ARG;
   s->render = on != 0;
   s->render_bits = bits & (uint32_t)(DTK_TOKENS | DTK_SENTENCES);
+  if (on) s->pos_render = false;  // (one renderer at a time)
+  return DTK_OK;
+}
+
+extern "C" int dtk_stream_set_position_render(dtk_stream *s, int on, uint32_t bits) {
+  const uint32_t all = DTK_TOKENS | DTK_SENTENCES | DTK_TOKEN_POS | DTK_SENTENCE_POS | DTK_NEWLINE_AFTER_EOT;
+  if (!s || (bits & ~all)) return DTK_E_ARG;
+  if (on && !(bits & (uint32_t)(DTK_TOKEN_POS | DTK_SENTENCE_POS))) return DTK_E_ARG;  // those modes are dtk_stream_set_render's
+  if (on) {
+    const int rc = s->d_carry.fit((uint64_t)s->depth + 1u, (uint64_t)s->depth + 1u);
+    if (rc != DTK_OK) return rc;
+    s->render = false;
+  }
+  s->pos_render = on != 0;
+  s->pos_bits = bits;
+  return DTK_OK;
+}
+
+extern "C" int dtk_stream_positions(dtk_stream *s, dtk_stream_pos *o) {
+  if (!s || !o) return DTK_E_ARG;
+  if (!s->cur) return DTK_E_STATE;
+  const DtkPosTrailer &t = *s->cur;
+  auto carry = [](const DtkPosCarry &c) { return dtk_stream_carry{c.posC, c.sentB, c.init, c.pos_nonempty, c.sent_nonempty}; };
+  o->splice_pos = t.splice_pos; o->splice_sent = t.splice_sent;
+  o->open_pos = s->cur_out + t.out_len; o->open_pos_len = t.open_pos_len;
+  o->open_sent = o->open_pos + t.open_pos_len; o->open_sent_len = t.open_sent_len;
+  o->carry_in = carry(t.carry_in); o->carry_out = carry(t.carry_out);
+  return DTK_OK;
+}
+
+// The one place that splices: out with the held prefixes at the two offsets (the position line comes first), then
+// the open fragments join what is held.
+extern "C" int dtk_stream_emit(dtk_stream *s, dtk_write_fn w, void *user) {
+  if (!s || !w) return DTK_E_ARG;
+  if (!s->cur || s->cur_emitted) return DTK_E_STATE;
+  const DtkPosTrailer &t = *s->cur;
+  s->cur_emitted = true;
+  uint64_t at = 0;
+  int rc;
+  std::string *held[2] = {&s->held_pos, &s->held_sent};
+  const uint64_t splice[2] = {t.splice_pos, t.splice_sent};
+  for (int i = 0; i < 2; i++) {
+    if (splice[i] == UINT64_MAX) continue;
+    if (splice[i] < at || splice[i] > t.out_len) return DTK_E_STATE;
+    if (splice[i] > at && (rc = w(user, s->cur_out + at, (size_t)(splice[i] - at))) != DTK_OK) return rc;
+    at = splice[i];
+    if (!held[i]->empty() && (rc = w(user, reinterpret_cast<const uint8_t *>(held[i]->data()), held[i]->size())) != DTK_OK) return rc;
+    held[i]->clear();
+  }
+  if (t.out_len > at && (rc = w(user, s->cur_out + at, (size_t)(t.out_len - at))) != DTK_OK) return rc;
+  const char *open = reinterpret_cast<const char *>(s->cur_out + t.out_len);
+  s->held_pos.append(open, (size_t)t.open_pos_len);
+  s->held_sent.append(open + t.open_pos_len, (size_t)t.open_sent_len);
   return DTK_OK;
 }
 
@@ -131,6 +198,11 @@ struct Run {
   DtkLaneState carry{};
   bool has_tok = false;          // the current text has had a token
   uint32_t status = 0;
+  // position rendering: the bound of an integer's size.  posC counts runes of windows that begin at or behind the
+  // `first` of the last slice in which a TextEnd fired; `te_from` is that of the last such slice the host has seen
+  // delivered (0: none yet), so posC of a slice being enqueued stays below its cut - te_from, plus what the run began with.
+  bool is_matrix = false;
+  uint64_t te_from = 0, posc0 = 0;
 
   uint8_t *bytes(uint32_t slot) { return s->buf[slot]->as<uint8_t>(); }
 
@@ -158,7 +230,7 @@ struct Run {
   // a slice that has been enqueued
   struct Slice {
     uint32_t slot = 0, first = 0;
-    uint64_t base = 0;
+    uint64_t base = 0, k = 0;
     bool open = false, ended = false, carried = false;
     DtkStreamCut c{};
   };
@@ -176,7 +248,14 @@ struct Run {
       carry = DtkLaneState{x.c.p, x.c.t, x.c.aux, x.c.flags};
       have_carry = true;
     }
-    batch_set_render(b, s->render, s->render_bits, x.first, x.ended ? len[x.slot] : x.c.cut, x.ended);
+    const uint32_t cut = x.ended ? len[x.slot] : x.c.cut;
+    batch_set_render(b, s->render || s->pos_render, s->pos_render ? s->pos_bits : s->render_bits, x.first, cut, x.ended);
+    if (s->pos_render) {
+      uint32_t digits = 2;  // ("-1")
+      for (uint64_t v = x.base + cut - te_from + posc0; v >= 10u; v /= 10u) digits++;
+      const uint64_t slots = (uint64_t)s->depth + 1u;
+      batch_set_pos_render(b, true, is_matrix, digits, s->d_carry + x.k % slots, s->d_carry + (x.k + 1u) % slots);
+    }
     return dtk_batch_download_begin(b);
   }
   // hands the slice over (its successor may be walking meanwhile)
@@ -202,8 +281,16 @@ struct Run {
     const uint64_t nt = sl.view.tok_off[1], nx = sl.view.text_off[1];
     const uint64_t n_teot = nx - ((x.ended && (sl.view.doc_tail[0] & DTK_TAIL_E)) ? 1u : 0u);
     has_tok = n_teot ? nt > sl.view.text_tok_end[n_teot - 1] : (has_tok || nt > 0);
+    if (n_teot || nx) te_from = x.base + x.first;
     if (s->render && (rc = batch_render_out(b, &sl.out, &sl.out_len)) != DTK_OK) return rc;
-    return slice_fn ? slice_fn(slice_user, &sl) : DTK_OK;
+    if (s->pos_render) {
+      if ((rc = batch_pos_out(b, &s->cur_out, &s->cur)) != DTK_OK) { s->cur = nullptr; return rc; }
+      sl.out = s->cur_out; sl.out_len = s->cur->out_len;
+      s->cur_emitted = false;
+    }
+    rc = slice_fn ? slice_fn(slice_user, &sl) : DTK_OK;
+    s->cur = nullptr;
+    return rc;
   }
 };
 }  // namespace
@@ -211,12 +298,22 @@ struct Run {
 extern "C" int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn read_fn, void *read_user, uint32_t flags,
                               dtk_stream_slice_fn slice_fn, void *slice_user, uint32_t *status) {
   if (!s || !m || !read_fn || (flags & ~(uint32_t)31u)) return DTK_E_ARG;
+  if (s->pos_render && ((flags ^ s->pos_bits) & DTK_NEWLINE_AFTER_EOT)) return DTK_E_ARG;  // the rule is part of the rendering
   if (status) *status = 0;
   const uint32_t depth = s->depth;
   Run r;
   r.s = s; r.read_fn = read_fn; r.read_user = read_user; r.slice_fn = slice_fn; r.slice_user = slice_user;
   r.len.assign(depth, 0);
   r.touched.assign(depth, 0);
+  s->held_pos.clear(); s->held_sent.clear();
+  s->cur = nullptr;
+  if (s->pos_render) {
+    // a new writer: {posC 0, sentB, init} (token_writer.go:38-42) in slot 0
+    const DtkPosCarry c0{g_dbg.sp_posc0, 1u, 1u, 0u, 0u};
+    r.posc0 = (uint64_t)(c0.posC < 0 ? -c0.posC : c0.posC);
+    r.is_matrix = std::strcmp(dtk_model_type(m), "MATOK") == 0;
+    HIP_TRY(hipMemcpy(s->d_carry.p, &c0, sizeof(c0), hipMemcpyHostToDevice));
+  }
   // (the writer's rune offsets are the host's: the compaction writes the byte offsets only)
   const uint32_t run_flags = DTK_NO_RUNE_OFFSETS;
   r.fill(0, nullptr);
@@ -226,18 +323,25 @@ extern "C" int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn rea
     const uint32_t slot = (uint32_t)(k % depth), next = (uint32_t)((k + 1) % depth);
     // with two buffers window k + 1 goes where slice k - 1 lies: that one is handed over first
     if (k > 0 && depth == 2 && ((rc = r.take_cut(prev)) != DTK_OK || (rc = r.deliver(prev)) != DTK_OK || prev.ended)) break;
+    // The predecessor's cut: slice k starts from it.  It is taken behind the read of window k + 1, which then runs
+    // beside the predecessor's walk -- except with position rendering, whose download (the capacity bound of the
+    // position lines: some 4 bytes per input byte) is a slice's longest leg: there the cut comes first, and the read
+    // runs beside that download (profiles/stream_positions.txt).
+    const bool cut_first = s->pos_render;
+    auto cut_prev = [&]() -> bool {  // false: the loop ends here
+      if ((rc = r.take_cut(prev)) != DTK_OK) return false;
+      if (prev.ended) { rc = r.deliver(prev); return false; }
+      return true;
+    };
+    if (k > 0 && depth > 2 && cut_first && !cut_prev()) break;
     bool open = false;
     if (r.len[slot] == s->S + kTail && !r.eof) {
       open = r.fill(next, r.bytes(slot) + s->S) > 0;
       if (open && (rc = r.upload(next)) != DTK_OK) break;
     }
-    // the predecessor's cut: slice k starts from it
-    if (k > 0 && depth > 2) {
-      if ((rc = r.take_cut(prev)) != DTK_OK) break;
-      if (prev.ended) { rc = r.deliver(prev); break; }
-    }
+    if (k > 0 && depth > 2 && !cut_first && !cut_prev()) break;
     Run::Slice cur;
-    cur.slot = slot; cur.base = k * s->S; cur.open = open;
+    cur.slot = slot; cur.base = k * s->S; cur.k = k; cur.open = open;
     cur.carried = r.have_carry; cur.first = r.have_carry ? r.carry.p : 0u;
     if ((rc = batch_set_slice(s->slots[slot], open ? (uint32_t)s->S : 0u, r.have_carry ? &r.carry : nullptr)) != DTK_OK ||
         (rc = dtk_batch_run(m, s->slots[slot], run_flags)) != DTK_OK)
@@ -256,6 +360,7 @@ extern "C" int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn rea
       (void)batch_set_slice(s->slots[q], 0u, nullptr);
       batch_set_render(s->slots[q], false, 0u, 0u, 0u, false);
     }
+  s->cur = nullptr;
   if (status) *status = r.status;
   return rc;
 }

@@ -229,13 +229,21 @@ class SliceView:
     """One slice of a stream (dtk_stream_slice, datok_gpu.h) in host arrays.  All positions are relative to the
     slice's window `text`, whose byte 0 is stream byte `base`: the slice's calls begin with the reference's window
     start (buffer[0]) at `first` and end at `cut`; `tail` (doc_tail) counts on the `last` slice only.  `out`: the bytes
-    a stock writer writes for the slice's calls as the device rendered them (Stream.set_render), else None."""
+    a stock writer writes for the slice's calls as the device rendered them (Stream.set_render), else None.
+    In a position mode (Stream.set_position_render) `out` lacks the integers of a text that other slices share:
+    splice_pos / splice_sent (None: no such place) are the offsets where the integers held from earlier slices belong,
+    open_pos / open_sent the integers of the text still open at the cut, carry_in / carry_out the writer's state
+    (posC, sentB, init, pos non-empty, sent non-empty) in front of and behind the slice, and `written` the slice's
+    final bytes (dtk_stream_emit).  (This view is the tests' and scripts' mirror: with position rendering on it runs
+    dtk_stream_emit for every slice and keeps a second copy of the bytes in `written`; a caller that wants the bytes
+    once calls dtk_stream_emit from its own slice callback, as scripts/stream_render.py does.)"""
     __slots__ = ("base", "first", "cut", "text", "last", "status", "tok_bstart", "tok_bend", "evl_pos", "evl_kind", "tail",
-                 "out")
+                 "out", "splice_pos", "splice_sent", "open_pos", "open_sent", "carry_in", "carry_out", "written")
+    _NONE = ("out", "splice_pos", "splice_sent", "open_pos", "open_sent", "carry_in", "carry_out", "written")
 
     def __init__(self, **kw):
         for k in self.__slots__:
-            setattr(self, k, kw.get(k, None if k == "out" else 0))
+            setattr(self, k, kw.get(k, None if k in self._NONE else 0))
 
 
 def slice_calls(is_matrix, sl: SliceView):
@@ -726,6 +734,14 @@ class Stream:
         check(lib().dtk_stream_set_render(self._h, 0 if bits is None else 1, 0 if bits is None else int(bits)),
               "dtk_stream_set_render")
 
+    def set_position_render(self, bits):
+        """The same in a mode with TOKEN_POS or SENTENCE_POS (any of the five writer bits with one of the two): the
+        writer's state is carried from slice to slice on the device, and every SliceView brings out, splice_pos,
+        splice_sent, open_pos, open_sent, carry_in, carry_out and written.  run() must get the same NEWLINE_AFTER_EOT
+        in its flags.  Turns set_render off (and set_render turns this off); None turns it off."""
+        check(lib().dtk_stream_set_position_render(self._h, 0 if bits is None else 1, 0 if bits is None else int(bits)),
+              "dtk_stream_set_position_render")
+
     @staticmethod
     def _reader_fn(reader, err):
         if not hasattr(reader, "read"):
@@ -747,8 +763,8 @@ class Stream:
 
     def transduce(self, tok, reader, flags=SIMPLE):
         """dtk_stream_transduce: what the reference writes for the stream with a stock NewTokenWriter(w, flags) -- the
-        slices' bytes as the device rendered them, or with a position flag every slice replayed into the one writer of
-        the C++ mirror.  Returns (output, status)."""
+        slices' bytes as the device rendered them (with a position flag through dtk_stream_emit; both kinds of
+        rendering are off afterwards).  Returns (output, status)."""
         err = []
         out, n, st = C.c_void_p(), C.c_size_t(), C.c_uint32()
         rc = lib().dtk_stream_transduce(self._h, tok._h, self._reader_fn(reader, err), None, int(flags), C.byref(out),
@@ -770,7 +786,7 @@ class Stream:
             if on_slice is None:
                 return 0
             try:
-                on_slice(_slice_view(p.contents))
+                on_slice(_slice_view(p.contents, self._h))
                 return 0
             except Exception as e:  # noqa: BLE001
                 err.append(e)
@@ -783,7 +799,28 @@ class Stream:
         return int(st.value)
 
 
-def _slice_view(s) -> SliceView:
+def _slice_positions(h) -> dict:
+    """What dtk_stream_positions and dtk_stream_emit say about the slice being delivered ({}: no position rendering)."""
+    sp = _lib.StreamPos()
+    if not h or lib().dtk_stream_positions(h, C.byref(sp)) != _lib.OK:
+        return {}
+    none = 2 ** 64 - 1
+    parts = []
+
+    def wr(_user, p, n):
+        parts.append(C.string_at(p, n))
+        return 0
+    check(lib().dtk_stream_emit(h, _lib.WRITE_FN(wr), None), "dtk_stream_emit")
+
+    def carry(c):
+        return (int(c.posC), bool(c.sentB), bool(c.init), bool(c.pos_nonempty), bool(c.sent_nonempty))
+    return dict(splice_pos=None if sp.splice_pos == none else int(sp.splice_pos),
+                splice_sent=None if sp.splice_sent == none else int(sp.splice_sent),
+                open_pos=C.string_at(sp.open_pos, int(sp.open_pos_len)), open_sent=C.string_at(sp.open_sent, int(sp.open_sent_len)),
+                carry_in=carry(sp.carry_in), carry_out=carry(sp.carry_out), written=b"".join(parts))
+
+
+def _slice_view(s, stream=None) -> SliceView:
     """Host copies of a dtk_stream_slice (its buffers are only valid inside the callback)."""
     v = s.view
 
@@ -803,7 +840,7 @@ def _slice_view(s) -> SliceView:
                      text=C.string_at(s.text, int(s.len)) if s.len else b"",
                      tok_bstart=bs, tok_bend=be, evl_pos=arr(v.evl_pos, ne, np.uint32)[int(off[0]):],
                      evl_kind=arr(v.evl_kind, ne, np.uint8)[int(off[0]):], tail=int(arr(v.doc_tail, 1, np.uint32)[0]),
-                     out=C.string_at(s.out, int(s.out_len)) if s.out else None)
+                     out=C.string_at(s.out, int(s.out_len)) if s.out else None, **_slice_positions(stream))
 
 
 def _slice_callback(on_slice, doc_off, err):

@@ -394,33 +394,38 @@ class GpuTokenizer final : public Tokenizer {
     return rc == DTK_OK &&
            !(last_status_ & (DTK_ST_WINDOW_OVERFLOW | DTK_ST_BAD_MODEL | DTK_ST_STEP_LIMIT | DTK_ST_INTERNAL | DTK_ST_IRREGULAR));
   }
-  // TransduceTokenWriter(r, NewTokenWriter(w, bits)) for a reader of any length where bits holds no position flag
-  // (TOKENS, SENTENCES, NEWLINE_AFTER_EOT): the writer keeps no state then, every slice's bytes are rendered on the
-  // device (dtk_stream_set_render) and written to w as they come home -- no closure is called.  A position flag is
-  // refused (false): those modes go through the TokenWriter overload above.
+  // TransduceTokenWriter(r, NewTokenWriter(w, bits)) for a reader of any length: every slice's bytes are rendered on
+  // the device and written to w as they come home -- no closure is called.  Without a position flag the writer keeps
+  // no state (dtk_stream_set_render); with TOKEN_POS or SENTENCE_POS its state is carried on the device
+  // (dtk_stream_set_position_render) and dtk_stream_emit holds the position line of the text that is open.
   bool TransduceStream(std::istream &r, std::ostream &w, Bits bits, uint64_t slice_bytes = 16u << 20, uint32_t depth = 3) {
     last_status_ = 0;
     dtk_stream *s = nullptr;
     if (dtk_stream_create(slice_bytes, depth, &s) != DTK_OK) return false;
-    int rc = dtk_stream_set_render(s, 1, (uint32_t)bits);
+    const bool positions = (bits & (TOKEN_POS | SENTENCE_POS)) != 0;
+    int rc = positions ? dtk_stream_set_position_render(s, 1, (uint32_t)bits) : dtk_stream_set_render(s, 1, (uint32_t)bits);
     // (the blocked token bytes: nobody reads them here)
     if (rc == DTK_OK) rc = dtk_stream_set_result_fields(s, DTK_R_TOK_BYTE_BLK);
     if (rc == DTK_OK) {
-      struct Ctx { std::istream *r; std::ostream *w; } c{&r, &w};
+      struct Ctx { std::istream *r; std::ostream *w; dtk_stream *s; bool positions; } c{&r, &w, s, positions};
       auto rd = [](void *u, uint8_t *buf, size_t cap) -> size_t {
         Ctx *c = static_cast<Ctx *>(u);
         c->r->read(reinterpret_cast<char *>(buf), (std::streamsize)cap);
         return (size_t)c->r->gcount();
       };
       auto on_slice = [](void *u, const dtk_stream_slice *sl) -> int {
-        static_cast<Ctx *>(u)->w->write(reinterpret_cast<const char *>(sl->out), (std::streamsize)sl->out_len);
-        return DTK_OK;
+        Ctx *c = static_cast<Ctx *>(u);
+        const dtk_write_fn wr = [](void *o, const uint8_t *p, size_t n) -> int {
+          static_cast<std::ostream *>(o)->write(reinterpret_cast<const char *>(p), (std::streamsize)n);
+          return DTK_OK;
+        };
+        return c->positions ? dtk_stream_emit(c->s, wr, c->w) : wr(c->w, sl->out, (size_t)sl->out_len);
       };
-      rc = dtk_stream_run(s, m_, rd, &c, 0, on_slice, &c, &last_status_);
+      rc = dtk_stream_run(s, m_, rd, &c, (uint32_t)bits & DTK_NEWLINE_AFTER_EOT, on_slice, &c, &last_status_);
     }
     dtk_stream_free(s);
     w.flush();
-    last_status_ &= ~(uint32_t)DTK_ST_EMPTY_TEXT;  // (an empty text only breaks the position modes)
+    if (!positions) last_status_ &= ~(uint32_t)DTK_ST_EMPTY_TEXT;  // (an empty text only breaks the position modes)
     return rc == DTK_OK &&
            !(last_status_ & (DTK_ST_WINDOW_OVERFLOW | DTK_ST_BAD_MODEL | DTK_ST_STEP_LIMIT | DTK_ST_INTERNAL | DTK_ST_IRREGULAR));
   }

@@ -455,10 +455,12 @@ int dtk_pipeline_run(dtk_pipeline *p, const dtk_model *m, const uint8_t *text, c
  *      blocked form, evl_pos or the bitmaps, doc_tail) are relative to the window, whose byte 0 is stream byte `base`;
  *      a replay starts with the window start (buffer[0] of the reference) at `first`.  The writer's rune offsets and
  *      sentence list run across cuts (posC, sentB, init of token_writer.go:38-42) and are read in the position modes
- *      only: TOKEN_POS and SENTENCE_POS are the host writer's that the replay feeds, as in the reference -- tok_rstart /
- *      tok_rend / sent of a slice's view are not delivered, and dtk_stream_set_result_fields rejects the rune fields.
- *      In the four position-free modes (TOKENS, SENTENCES, both, neither; NEWLINE_AFTER_EOT changes nothing there) the
- *      writer is stateless, and the device renders a slice's bytes (dtk_stream_set_render: `out` / `out_len`).
+ *      only; tok_rstart / tok_rend / sent of a slice's view are not delivered, and dtk_stream_set_result_fields rejects
+ *      the rune fields.  The device renders a slice's writer bytes in every mode (`out` / `out_len`): in the four
+ *      position-free modes (TOKENS, SENTENCES, both, neither; NEWLINE_AFTER_EOT changes nothing there) the writer is
+ *      stateless (dtk_stream_set_render); with TOKEN_POS or SENTENCE_POS its state is carried from slice to slice on
+ *      the device (dtk_stream_set_position_render, dtk_stream_emit).  A custom TokenWriter's closures are fed by the
+ *      replay (include/datok.hpp, replay_list).
  *        *status: the OR of the slices' status bits; DTK_ST_EMPTY_TEXT is decided for the stream (a text may span cuts).
  *      A slice that needs the exact pass ends the run with DTK_E_IRREGULAR. ---- */
 typedef struct dtk_stream dtk_stream;
@@ -491,14 +493,53 @@ int dtk_stream_set_result_fields(dtk_stream *s, uint32_t fields);
  * accepted and changes nothing; a position bit (their writer state runs across cuts) or an unknown bit: DTK_E_ARG.  The
  * view's arrays are delivered as before.  A token that the reference cannot print (DTK_ST_BAD_OFFSET) prints empty. */
 int dtk_stream_set_render(dtk_stream *s, int on, uint32_t bits);
-/* flags: DTK_NEWLINE_AFTER_EOT is accepted and changes nothing here (it only moves the writer's rune offsets).  Short
+/* The same in the modes with a position bit: on != 0, every slice brings the bytes a stock NewTokenWriter(w, bits)
+ * writes during its calls, rendered on the device from the writer's state behind its predecessor -- posC (64 bits: Go's
+ * int), sentB, init, and whether pos / sent hold an integer -- which stays on the device between slices.
+ * bits: any of the five writer bits with DTK_TOKEN_POS or DTK_SENTENCE_POS among them, else DTK_E_ARG; turning this
+ * on turns dtk_stream_set_render off and the other way round.  dtk_stream_run must then get the same
+ * DTK_NEWLINE_AFTER_EOT in its flags (else DTK_E_ARG).
+ *   `out` / `out_len` of a slice are the writer's bytes in order, with two exceptions, both for a text that began in an
+ * earlier slice or is still open at the cut (a position line is printed at TextEnd and holds a whole text's integers):
+ *   - the position lines of a TextEnd whose text began in an earlier slice hold only the integers pushed in this
+ *     slice, each behind a blank; what earlier slices pushed belongs at splice_pos / splice_sent;
+ *   - the integers pushed in this slice for the text still open at the cut are not in `out`: they are the fragments
+ *     open_pos / open_sent, blank-separated, with a blank in front if the line already has an integer.
+ * dtk_stream_emit puts the two together.  A token whose end offset is 0 under DTK_NEWLINE_AFTER_EOT (the literal rule
+ * of token_writer.go:51 would fire twice in one text) ends the run with DTK_E_IRREGULAR; more calls than the capacity
+ * bound allows for, with DTK_E_CAPACITY.  Texts without a token (DTK_ST_EMPTY_TEXT; the reference panics) print as in
+ * the C++ mirror: the SentenceEnd pushes nothing and an empty list prints no line. */
+int dtk_stream_set_position_render(dtk_stream *s, int on, uint32_t bits);
+typedef struct {
+  int64_t posC;
+  uint32_t sentB, init, pos_nonempty, sent_nonempty;
+} dtk_stream_carry;
+typedef struct {
+  uint64_t splice_pos, splice_sent; /* offsets into out where the held TOKEN_POS / SENTENCE_POS prefix belongs; UINT64_MAX:
+                                       none (at most one of each: only a slice's first text can be a continued one) */
+  const uint8_t *open_pos;          /* the fragments of the text open at the cut (page-locked host memory, valid */
+  uint64_t open_pos_len;            /* until slice_fn returns) */
+  const uint8_t *open_sent;
+  uint64_t open_sent_len;
+  dtk_stream_carry carry_in, carry_out; /* the writer in front of and behind the slice */
+} dtk_stream_pos;
+/* Inside slice_fn, with position rendering on: the slice being delivered (else DTK_E_STATE). */
+int dtk_stream_positions(dtk_stream *s, dtk_stream_pos *o);
+typedef int (*dtk_write_fn)(void *user, const uint8_t *bytes, size_t n); /* DTK_OK to go on */
+/* Inside slice_fn, once per slice: writes the slice's final bytes in order -- `out` with the held prefixes spliced in at
+ * the two offsets -- and then appends the open fragments to the held prefixes.  Those live in the dtk_stream as host
+ * strings, start empty with every run, and grow with the length of a TEXT (not of the stream), as the reference's pos[]
+ * and sent[] do: some 11 bytes per token of the text that is open.  A non-zero return of w ends the call with it. */
+int dtk_stream_emit(dtk_stream *s, dtk_write_fn w, void *user);
+/* flags: DTK_NEWLINE_AFTER_EOT is accepted and changes nothing here (it only moves the writer's rune offsets), except
+ * that with position rendering on it must be the bit dtk_stream_set_position_render got.  Short
  * reads are retried until a buffer is full; read_fn is not called again after it has returned 0. */
 int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn read_fn, void *read_user, uint32_t flags,
                    dtk_stream_slice_fn slice_fn, void *slice_user, uint32_t *status);
 /* What the reference writes to w for the stream with a stock NewTokenWriter(w, bits), for a reader of any length.
  * Without a position bit the slices' rendered bytes are appended (dtk_stream_set_render is turned on with `bits`, and
- * stays so); with TOKEN_POS or SENTENCE_POS rendering is turned off and every slice is replayed into the one writer of
- * the C++ mirror (include/datok.hpp), as dtk_transduce_replay does for a document.  *out is
+ * stays so); with TOKEN_POS or SENTENCE_POS position rendering is turned on for the run, every slice's bytes come from
+ * dtk_stream_emit, and both kinds of rendering are off afterwards.  *out is
  * malloc'd (the whole output: a caller that must bound that too writes from slice_fn, as `datok tokenize` does); free
  * with dtk_free. */
 int dtk_stream_transduce(dtk_stream *s, const dtk_model *m, dtk_read_fn read_fn, void *read_user, uint32_t bits,

@@ -36,6 +36,7 @@ EXPORTS = [
     "dtk_stream_create", "dtk_stream_free", "dtk_stream_set_chunking", "dtk_stream_set_result_fields", "dtk_stream_run",
     "dtk_stream_transduce", "dtk_stream_set_render",
     "dtk_stream_set_position_render", "dtk_stream_positions", "dtk_stream_emit",
+    "dtk_stream_set_offsets", "dtk_stream_offsets", "dtk_blk64_start", "dtk_blk64_end",
 ]
 
 
@@ -89,6 +90,17 @@ class StreamPos(C.Structure):
     """dtk_stream_pos: what belongs to a slice's `out` in a position mode (dtk_stream_positions)."""
     _fields_ = [("splice_pos", C.c_uint64), ("splice_sent", C.c_uint64), ("open_pos", C.c_void_p), ("open_pos_len", C.c_uint64),
                 ("open_sent", C.c_void_p), ("open_sent_len", C.c_uint64), ("carry_in", StreamCarry), ("carry_out", StreamCarry)]
+
+
+SO_PLAIN, SO_BLOCKED = 0, 1   # dtk_stream_set_offsets' forms
+
+
+class StreamOffs(C.Structure):
+    """dtk_stream_offs: a slice's rune offsets and sentence list as arrays (dtk_stream_offsets)."""
+    _fields_ = [("n_tok", C.c_uint64), ("n_sent", C.c_uint64), ("n_text", C.c_uint64),
+                ("tok_rstart", C.c_void_p), ("tok_rend", C.c_void_p), ("tok_rblk", C.c_void_p), ("tok_rblk_head", C.c_void_p),
+                ("sent", C.c_void_p), ("text_tok_end", C.c_void_p), ("text_sent_end", C.c_void_p),
+                ("carry_in", StreamCarry), ("carry_out", StreamCarry)]
 
 
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -208,6 +220,10 @@ def lib():
     L.dtk_stream_set_position_render.argtypes = [vp, C.c_int, u32]
     L.dtk_stream_positions.argtypes = [vp, C.POINTER(StreamPos)]
     L.dtk_stream_emit.argtypes = [vp, WRITE_FN, vp]
+    L.dtk_stream_set_offsets.argtypes = [vp, C.c_int, u32]
+    L.dtk_stream_offsets.argtypes = [vp, C.POINTER(StreamOffs)]
+    for f in (L.dtk_blk64_start, L.dtk_blk64_end):
+        f.argtypes, f.restype = [vp, vp, u64], C.c_int64
     L.dtk_stream_run.argtypes = [vp, vp, READ_FN, vp, u32, STREAM_SLICE_FN, vp, C.POINTER(u32)]
     L.dtk_stream_transduce.argtypes = [vp, vp, READ_FN, vp, u32, C.POINTER(vp), C.POINTER(sz), C.POINTER(u32)]
     for f in (L.dtk_blk_start, L.dtk_blk_end):

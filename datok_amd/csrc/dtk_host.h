@@ -36,10 +36,12 @@ struct DtkDebug {
   int round_limit = -1;  // host repair rounds before the one-lane-per-document fallback (-1: the longest document's lanes)
   int debug_repair = 0;  // print the lane records of documents that stay broken
   int blk_span = -1;     // what a segment of a 64-token block may span in the blocked offsets (-1 or 0: 65 535); read where
-                         // k_pack_blk is launched, so that ordinary text reaches the fallback to the 32-bit arrays
+                         // k_pack_blk is launched, so that ordinary text reaches the fallback to the 32-bit arrays (and where
+                         // a stream's k_so_pack64 is: the fallback to the plain 64-bit arrays)
   int evl_cap = -1;      // entries the copies of DTK_R_EVENT_LIST are first sized for, in place of n_sent + n_texts (-1: off),
-                         // so that ordinary text reaches the second download of a list that outgrew the bound
-  long long sp_posc0 = 0; // posC in front of a stream's first slice in a position mode (dtk_stream_run reads it once, at its
+                         // so that ordinary text reaches the second download of a list that outgrew the bound; a stream's offset
+                         // delivery also sizes its first copies of sent and the text rows with it (the late copy at delivery)
+  long long sp_posc0 = 0; // posC in front of a stream's first slice in a position mode or with offset delivery (dtk_stream_run reads it once, at its
                          // start): integers beyond 2^32 and of 11 digits from a stream of a few hundred bytes
 };
 extern DtkDebug g_dbg;
@@ -235,6 +237,24 @@ struct dtk_batch {
   const DtkPosCarry *sp_carry_in = nullptr;
   DtkPosCarry *sp_carry_out = nullptr;
   DevArray<uint64_t> d_sp_ws;
+  // The slice's rune offsets and sentence list as arrays (dtk_stream_set_offsets, dtk_streamoffs.hip): computed in the
+  // same place from carry slots of their own, beside batch_set_render's bytes or without them.  One device block and
+  // its page-locked copy with the same layout (byte offsets, fixed before anything is enqueued): tok_rstart | tok_rend |
+  // sent | trailer | text_tok_end | text_sent_end | heads | words.  The copies bring the plain or the blocked offsets,
+  // sent and the text rows as far as the compaction's counts reach, and the trailer; what the trailer then asks for
+  // beyond that (blk_fail: the plain offsets; more sent ints or rows) is copied at delivery.
+  bool so_on = false, so_matrix = false, so_nl = false;
+  uint32_t so_form = 0;            // DTK_SO_*
+  const DtkPosCarry *so_carry_in = nullptr;
+  DtkPosCarry *so_carry_out = nullptr;
+  struct SoLayout {
+    uint64_t n = 0, sent_cap = 0, text_cap = 0;  // the capacities: tokens (exact), sent ints, texts
+    uint64_t sent_home = 0, text_home = 0;       // sent ints / text rows the page-locked copy holds
+    uint64_t rstart = 0, rend = 0, sent = 0, trailer = 0, ttok = 0, tsent = 0, heads = 0, words = 0, bytes = 0;
+    bool blocked = false, wide_home = false;     // wide_home: tok_rstart / tok_rend are in the page-locked copy
+  } so;
+  DevArray<uint64_t> d_so_ws, d_so_out;
+  PinBuf h_so_out;
   uint32_t eager_fields = 0;  // the last run's k_to_host was asked for these (0: none); finish() decides whether it counts
   bool results_changed = false;  // finish() had to touch the result arrays after the run (repair, growth, EOT kernel, exact pass)
   Event ev_dl;                 // behind the batch's copies on the (possibly shared) download stream
@@ -260,6 +280,19 @@ int batch_render_out(dtk_batch *b, const uint8_t **out, uint64_t *out_len);
 // batch_pos_out: the page-locked bytes and the trailer block behind them (DTK_E_CAPACITY / DTK_E_IRREGULAR as it says).
 void batch_set_pos_render(dtk_batch *b, bool on, bool is_matrix, uint32_t digits, const DtkPosCarry *carry_in, DtkPosCarry *carry_out);
 int batch_pos_out(dtk_batch *b, const uint8_t **out, const DtkPosTrailer **trailer);
+// The slice's next download also computes its rune offsets and sentence list (form: DTK_SO_*; nl: the run's
+// NEWLINE_AFTER_EOT) from carry_in, and leaves the writer's state in carry_out.  batch_offs_out: behind
+// dtk_batch_result_host, the page-locked arrays (DTK_E_CAPACITY / DTK_E_IRREGULAR as the trailer says); the blocked
+// pointers are null where the plain arrays stand in, and the other way round.
+struct SoView {
+  const DtkOffsTrailer *t;
+  const int64_t *rstart, *rend, *sent;
+  const uint32_t *words;
+  const DtkOffBlock64 *heads;
+  const uint32_t *ttok, *tsent;
+};
+void batch_set_offsets(dtk_batch *b, bool on, uint32_t form, bool is_matrix, bool nl, const DtkPosCarry *carry_in, DtkPosCarry *carry_out);
+int batch_offs_out(dtk_batch *b, SoView *o);
 
 // The DTK_R_* arrays the last run wrote: DTK_NO_RUNE_OFFSETS / DTK_NO_BYTE_OFFSETS leave theirs alone.
 inline uint32_t run_fields(const dtk_batch *b) {

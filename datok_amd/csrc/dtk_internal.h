@@ -517,9 +517,38 @@ struct DtkStreamPosArgs {
   struct DtkPosTrailer *trailer;
 };
 
+// The writer's rune offsets and sentence list of a slice as arrays (dtk_streamoffs.hip, dtk_stream_set_offsets): what a
+// NewTokenWriter with TOKEN_POS | SENTENCE_POS collects in pos[] / sent[] during the slice's calls.  The front of the
+// chain is position rendering's (dtk_streampos_front.h): `front` holds its inputs and the part of the workspace it
+// reads (dtk_streamoffs_ws), with bits = TOKEN_POS | SENTENCE_POS and the run's NEWLINE_AFTER_EOT.
+struct DtkOffBlock64 { int64_t base0, base1; uint32_t brk, reserved; };  // dtk_off_block64 of datok_gpu.h
+struct DtkOffsTrailer {
+  uint64_t n_tok;                          // ~0: the list did not fit its arrays, nothing was computed
+  uint64_t n_sent, n_text;                 // ints pushed to sent[], TextEnd calls: beyond a capacity, the array is cut short
+  struct DtkPosCarry carry_in, carry_out;
+  uint32_t flags;                          // 1: a token with rend == 0 under NEWLINE_AFTER_EOT
+  uint32_t blk_fail;                       // 1: a segment of a block spans more than `span` (k_so_pack64)
+};
+struct DtkStreamOffsArgs {
+  struct DtkStreamPosArgs front;           // (rstart / rend: the plain arrays, n_tok each; out / cap / trailer unused)
+  uint64_t *sent_base;                     // workspace, tok_tiles: a tile's sentence ints, then their exclusive scan
+  uint32_t *sent_in;                       // workspace, n_tok: a token's place among its tile's sentence ints
+  int64_t *sent;                           // sent_cap
+  uint64_t sent_cap, text_cap;             // nothing is written at or behind them
+  uint32_t *text_tok_end, *text_sent_end;  // text_cap each
+  uint32_t blocked;                        // pack tok_rstart / tok_rend into words + heads
+  uint32_t span;                           // largest maximum - minimum a segment of a block may have (65 535)
+  uint32_t *words;                         // n_tok
+  struct DtkOffBlock64 *heads;             // ceil(n_tok / 64), 8-byte aligned
+  struct DtkOffsTrailer *trailer;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+#define DTK_STREAMOFFS_EVENTS 11  // one in front of the chain's ten launches and one behind each
+int dtk_launch_streamoffs(const struct DtkStreamOffsArgs *args, void *stream, void **events);  // events: null, or that many hipEvent_t
+uint64_t dtk_streamoffs_ws(struct DtkStreamOffsArgs *args, uint64_t *ws);  // as dtk_streampos_ws
 int dtk_launch_streampos(const struct DtkStreamPosArgs *args, void *stream);
 int dtk_pos_trailer_check(const struct DtkPosTrailer *t, uint64_t cap);  // DTK_OK, DTK_E_CAPACITY or DTK_E_IRREGULAR
 uint64_t dtk_streampos_ws(struct DtkStreamPosArgs *args, uint64_t *ws);  // lays the workspace out (ws null: the size only), in 64-bit words

@@ -34,6 +34,13 @@ struct dtk_stream {
   // The held prefixes (dtk_stream_emit): the integers of the text that is open at the last cut, as the bytes of its
   // TOKEN_POS / SENTENCE_POS line so far.  They grow with the length of a text, as the reference's pos[] / sent[] do.
   std::string held_pos, held_sent;
+  // dtk_stream_set_offsets: the writer's rune offsets and sentence list as arrays.  The same chain with slots of its
+  // own, beside set_render's bytes or alone; exclusive with position rendering.
+  bool offs = false;
+  uint32_t offs_form = DTK_SO_PLAIN;
+  DevArray<DtkPosCarry> d_ocarry;  // depth + 1
+  bool cur_offs_set = false;       // inside slice_fn: cur_offs is the slice being delivered
+  SoView cur_offs{};
   // the slice being delivered, inside slice_fn
   const uint8_t *cur_out = nullptr;
   const DtkPosTrailer *cur = nullptr;
@@ -89,7 +96,9 @@ extern "C" int dtk_stream_set_chunking(dtk_stream *s, uint32_t chunk_bytes, uint
 
 extern "C" int dtk_stream_set_result_fields(dtk_stream *s, uint32_t fields) {
   if (!s || !(fields & (DTK_R_TOK_BYTE | DTK_R_TOK_BYTE_BLK))) return DTK_E_ARG;
-  if (fields & (DTK_R_TOK_RUNE | DTK_R_TOK_RUNE16 | DTK_R_TOK_RUNE_BLK | DTK_R_SENT | DTK_R_EAGER)) return DTK_E_ARG;  // the host writer's
+  // (the rune fields of a slice's view would be the compaction's: the window as a fresh document.  The stream's rune
+  //  offsets and sentence list come from dtk_stream_set_offsets, computed from the writer's carried state.)
+  if (fields & (DTK_R_TOK_RUNE | DTK_R_TOK_RUNE16 | DTK_R_TOK_RUNE_BLK | DTK_R_SENT | DTK_R_EAGER)) return DTK_E_ARG;
   fields |= kForced;
   for (dtk_batch *b : s->slots) {
     const int rc = dtk_batch_set_result_fields(b, fields);
@@ -112,6 +121,7 @@ extern "C" int dtk_stream_set_position_render(dtk_stream *s, int on, uint32_t bi
   const uint32_t all = DTK_TOKENS | DTK_SENTENCES | DTK_TOKEN_POS | DTK_SENTENCE_POS | DTK_NEWLINE_AFTER_EOT;
   if (!s || (bits & ~all)) return DTK_E_ARG;
   if (on && !(bits & (uint32_t)(DTK_TOKEN_POS | DTK_SENTENCE_POS))) return DTK_E_ARG;  // those modes are dtk_stream_set_render's
+  if (on && s->offs) return DTK_E_ARG;  // (the offsets as digits or as arrays, not both)
   if (on) {
     const int rc = s->d_carry.fit((uint64_t)s->depth + 1u, (uint64_t)s->depth + 1u);
     if (rc != DTK_OK) return rc;
@@ -119,6 +129,32 @@ extern "C" int dtk_stream_set_position_render(dtk_stream *s, int on, uint32_t bi
   }
   s->pos_render = on != 0;
   s->pos_bits = bits;
+  return DTK_OK;
+}
+
+extern "C" int dtk_stream_set_offsets(dtk_stream *s, int on, uint32_t form) {
+  if (!s) return DTK_E_ARG;
+  if (on && ((form != DTK_SO_PLAIN && form != DTK_SO_BLOCKED) || s->pos_render)) return DTK_E_ARG;
+  if (on) {
+    const int rc = s->d_ocarry.fit((uint64_t)s->depth + 1u, (uint64_t)s->depth + 1u);
+    if (rc != DTK_OK) return rc;
+    s->offs_form = form;
+  }
+  s->offs = on != 0;
+  return DTK_OK;
+}
+
+extern "C" int dtk_stream_offsets(dtk_stream *s, dtk_stream_offs *o) {
+  if (!s || !o) return DTK_E_ARG;
+  if (!s->cur_offs_set) return DTK_E_STATE;
+  const SoView &v = s->cur_offs;
+  auto carry = [](const DtkPosCarry &c) { return dtk_stream_carry{c.posC, c.sentB, c.init, c.pos_nonempty, c.sent_nonempty}; };
+  static_assert(sizeof(dtk_off_block64) == sizeof(DtkOffBlock64) && sizeof(dtk_off_block64) == 24, "the kernels' block head is the header's");
+  o->n_tok = v.t->n_tok; o->n_sent = v.t->n_sent; o->n_text = v.t->n_text;
+  o->tok_rstart = v.rstart; o->tok_rend = v.rend;
+  o->tok_rblk = v.words; o->tok_rblk_head = reinterpret_cast<const dtk_off_block64 *>(v.heads);
+  o->sent = v.sent; o->text_tok_end = v.ttok; o->text_sent_end = v.tsent;
+  o->carry_in = carry(v.t->carry_in); o->carry_out = carry(v.t->carry_out);
   return DTK_OK;
 }
 
@@ -202,6 +238,7 @@ struct Run {
   // `first` of the last slice in which a TextEnd fired; `te_from` is that of the last such slice the host has seen
   // delivered (0: none yet), so posC of a slice being enqueued stays below its cut - te_from, plus what the run began with.
   bool is_matrix = false;
+  bool nl = false;               // the run's NEWLINE_AFTER_EOT (offset delivery)
   uint64_t te_from = 0, posc0 = 0;
 
   uint8_t *bytes(uint32_t slot) { return s->buf[slot]->as<uint8_t>(); }
@@ -256,6 +293,9 @@ struct Run {
       const uint64_t slots = (uint64_t)s->depth + 1u;
       batch_set_pos_render(b, true, is_matrix, digits, s->d_carry + x.k % slots, s->d_carry + (x.k + 1u) % slots);
     }
+    const uint64_t oslots = (uint64_t)s->depth + 1u;
+    batch_set_offsets(b, s->offs, s->offs_form, is_matrix, nl, s->offs ? s->d_ocarry + x.k % oslots : nullptr,
+                      s->offs ? s->d_ocarry + (x.k + 1u) % oslots : nullptr);
     return dtk_batch_download_begin(b);
   }
   // hands the slice over (its successor may be walking meanwhile)
@@ -288,8 +328,13 @@ struct Run {
       sl.out = s->cur_out; sl.out_len = s->cur->out_len;
       s->cur_emitted = false;
     }
+    if (s->offs) {
+      if ((rc = batch_offs_out(b, &s->cur_offs)) != DTK_OK) return rc;
+      s->cur_offs_set = true;
+    }
     rc = slice_fn ? slice_fn(slice_user, &sl) : DTK_OK;
     s->cur = nullptr;
+    s->cur_offs_set = false;
     return rc;
   }
 };
@@ -307,11 +352,17 @@ extern "C" int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn rea
   r.touched.assign(depth, 0);
   s->held_pos.clear(); s->held_sent.clear();
   s->cur = nullptr;
+  s->cur_offs_set = false;
+  r.is_matrix = std::strcmp(dtk_model_type(m), "MATOK") == 0;
+  r.nl = (flags & DTK_NEWLINE_AFTER_EOT) != 0;
+  if (s->offs) {  // a new writer in slot 0 of the offsets' chain
+    const DtkPosCarry c0{g_dbg.sp_posc0, 1u, 1u, 0u, 0u};
+    HIP_TRY(hipMemcpy(s->d_ocarry.p, &c0, sizeof(c0), hipMemcpyHostToDevice));
+  }
   if (s->pos_render) {
     // a new writer: {posC 0, sentB, init} (token_writer.go:38-42) in slot 0
     const DtkPosCarry c0{g_dbg.sp_posc0, 1u, 1u, 0u, 0u};
     r.posc0 = (uint64_t)(c0.posC < 0 ? -c0.posC : c0.posC);
-    r.is_matrix = std::strcmp(dtk_model_type(m), "MATOK") == 0;
     HIP_TRY(hipMemcpy(s->d_carry.p, &c0, sizeof(c0), hipMemcpyHostToDevice));
   }
   // (the writer's rune offsets are the host's: the compaction writes the byte offsets only)
@@ -359,8 +410,10 @@ extern "C" int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn rea
       (void)dtk_batch_sync(s->slots[q]);
       (void)batch_set_slice(s->slots[q], 0u, nullptr);
       batch_set_render(s->slots[q], false, 0u, 0u, 0u, false);
+      batch_set_offsets(s->slots[q], false, 0u, false, false, nullptr, nullptr);
     }
   s->cur = nullptr;
+  s->cur_offs_set = false;
   if (status) *status = r.status;
   return rc;
 }

@@ -236,10 +236,19 @@ class SliceView:
     (posC, sentB, init, pos non-empty, sent non-empty) in front of and behind the slice, and `written` the slice's
     final bytes (dtk_stream_emit).  (This view is the tests' and scripts' mirror: with position rendering on it runs
     dtk_stream_emit for every slice and keeps a second copy of the bytes in `written`; a caller that wants the bytes
-    once calls dtk_stream_emit from its own slice callback, as scripts/stream_render.py does.)"""
+    once calls dtk_stream_emit from its own slice callback, as scripts/stream_render.py does.)
+    With Stream.set_offsets the slice brings what a writer with TOKEN_POS | SENTENCE_POS collects during its calls, as
+    arrays (dtk_stream_offsets; None when it is off): r_tok_rstart / r_tok_rend (int64, decoded from whichever form
+    came; r_blocked says whether that was the blocked one, r_rblk / r_rblk_head are its words and heads), r_sent (int64),
+    r_text_tok_end / r_text_sent_end (tokens / sent ints of THIS slice in front of each TextEnd), r_carry_in /
+    r_carry_out (the writer's state as above)."""
     __slots__ = ("base", "first", "cut", "text", "last", "status", "tok_bstart", "tok_bend", "evl_pos", "evl_kind", "tail",
-                 "out", "splice_pos", "splice_sent", "open_pos", "open_sent", "carry_in", "carry_out", "written")
-    _NONE = ("out", "splice_pos", "splice_sent", "open_pos", "open_sent", "carry_in", "carry_out", "written")
+                 "out", "splice_pos", "splice_sent", "open_pos", "open_sent", "carry_in", "carry_out", "written",
+                 "r_tok_rstart", "r_tok_rend", "r_blocked", "r_rblk", "r_rblk_head", "r_sent", "r_text_tok_end",
+                 "r_text_sent_end", "r_carry_in", "r_carry_out")
+    _NONE = ("out", "splice_pos", "splice_sent", "open_pos", "open_sent", "carry_in", "carry_out", "written",
+             "r_tok_rstart", "r_tok_rend", "r_blocked", "r_rblk", "r_rblk_head", "r_sent", "r_text_tok_end",
+             "r_text_sent_end", "r_carry_in", "r_carry_out")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -431,6 +440,20 @@ def unpack_blocked(words, heads, first=0, last=None):
     base = np.where((i & 63) < h[:, 2], h[:, 0], h[:, 1]).astype(np.int32)
     w = words[i]
     return base + (w & np.uint32(0xFFFF)).astype(np.int32), base + (w >> np.uint32(16)).astype(np.int32)
+
+
+HEAD64 = np.dtype([("base0", np.int64), ("base1", np.int64), ("brk", np.uint32), ("reserved", np.uint32)])  # dtk_off_block64
+
+
+def unpack_blocked64(words, heads):
+    """(start, end) as int64 arrays from the blocked form of a stream slice's rune offsets (dtk_off_block64, datok_gpu.h;
+    what dtk_blk64_start / dtk_blk64_end give token by token).  words: uint32[n]; heads: HEAD64[ceil(n / 64)]."""
+    words = np.asarray(words, dtype=np.uint32)
+    heads = np.asarray(heads).view(HEAD64).reshape(-1)
+    i = np.arange(len(words), dtype=np.int64)
+    h = heads[i >> 6]
+    base = np.where((i & 63) < h["brk"], h["base0"], h["base1"]).astype(np.int64)
+    return base + (words & np.uint32(0xFFFF)).astype(np.int64), base + (words >> np.uint32(16)).astype(np.int64)
 
 
 class BatchResult:
@@ -734,6 +757,15 @@ class Stream:
         check(lib().dtk_stream_set_render(self._h, 0 if bits is None else 1, 0 if bits is None else int(bits)),
               "dtk_stream_set_render")
 
+    def set_offsets(self, form):
+        """Every SliceView brings the writer's rune offsets and sentence list as arrays (r_tok_rstart, r_tok_rend,
+        r_sent, r_text_tok_end, r_text_sent_end, r_carry_in, r_carry_out): what a NewTokenWriter with TOKEN_POS |
+        SENTENCE_POS -- and NEWLINE_AFTER_EOT iff run() gets it in its flags -- collects, carried from slice to slice on
+        the device.  form: _lib.SO_PLAIN (int64 pairs) or _lib.SO_BLOCKED (16-bit blocks with 64-bit bases,
+        unpack_blocked64); None turns it off.  Works beside set_render; E_ARG while set_position_render is on."""
+        check(lib().dtk_stream_set_offsets(self._h, 0 if form is None else 1, 0 if form is None else int(form)),
+              "dtk_stream_set_offsets")
+
     def set_position_render(self, bits):
         """The same in a mode with TOKEN_POS or SENTENCE_POS (any of the five writer bits with one of the two): the
         writer's state is carried from slice to slice on the device, and every SliceView brings out, splice_pos,
@@ -820,6 +852,33 @@ def _slice_positions(h) -> dict:
                 carry_in=carry(sp.carry_in), carry_out=carry(sp.carry_out), written=b"".join(parts))
 
 
+def _slice_offsets(h) -> dict:
+    """What dtk_stream_offsets says about the slice being delivered ({}: offset delivery is off)."""
+    so = _lib.StreamOffs()
+    if not h or lib().dtk_stream_offsets(h, C.byref(so)) != _lib.OK:
+        return {}
+
+    def arr(ptr, n, dt):
+        dt = np.dtype(dt)
+        if n == 0 or not ptr:
+            return np.zeros(0, dt)
+        return np.frombuffer((C.c_char * (n * dt.itemsize)).from_address(ptr), dtype=dt).copy()
+
+    def carry(c):
+        return (int(c.posC), bool(c.sentB), bool(c.init), bool(c.pos_nonempty), bool(c.sent_nonempty))
+    nt, ns, nx = int(so.n_tok), int(so.n_sent), int(so.n_text)
+    blocked = not so.tok_rstart and bool(so.tok_rblk)
+    words = heads = None
+    if blocked:
+        words, heads = arr(so.tok_rblk, nt, np.uint32), arr(so.tok_rblk_head, (nt + 63) // 64, HEAD64)
+        rs, re = unpack_blocked64(words, heads)
+    else:
+        rs, re = arr(so.tok_rstart, nt, np.int64), arr(so.tok_rend, nt, np.int64)
+    return dict(r_tok_rstart=rs, r_tok_rend=re, r_blocked=blocked, r_rblk=words, r_rblk_head=heads,
+                r_sent=arr(so.sent, ns, np.int64), r_text_tok_end=arr(so.text_tok_end, nx, np.uint32),
+                r_text_sent_end=arr(so.text_sent_end, nx, np.uint32), r_carry_in=carry(so.carry_in), r_carry_out=carry(so.carry_out))
+
+
 def _slice_view(s, stream=None) -> SliceView:
     """Host copies of a dtk_stream_slice (its buffers are only valid inside the callback)."""
     v = s.view
@@ -840,7 +899,8 @@ def _slice_view(s, stream=None) -> SliceView:
                      text=C.string_at(s.text, int(s.len)) if s.len else b"",
                      tok_bstart=bs, tok_bend=be, evl_pos=arr(v.evl_pos, ne, np.uint32)[int(off[0]):],
                      evl_kind=arr(v.evl_kind, ne, np.uint8)[int(off[0]):], tail=int(arr(v.doc_tail, 1, np.uint32)[0]),
-                     out=C.string_at(s.out, int(s.out_len)) if s.out else None, **_slice_positions(stream))
+                     out=C.string_at(s.out, int(s.out_len)) if s.out else None, **_slice_positions(stream),
+                     **_slice_offsets(stream))
 
 
 def _slice_callback(on_slice, doc_off, err):

@@ -32,6 +32,7 @@
 #include <memory>
 #include <ostream>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "datok_gpu.h"
@@ -426,6 +427,38 @@ class GpuTokenizer final : public Tokenizer {
     dtk_stream_free(s);
     w.flush();
     if (!positions) last_status_ &= ~(uint32_t)DTK_ST_EMPTY_TEXT;  // (an empty text only breaks the position modes)
+    return rc == DTK_OK &&
+           !(last_status_ & (DTK_ST_WINDOW_OVERFLOW | DTK_ST_BAD_MODEL | DTK_ST_STEP_LIMIT | DTK_ST_INTERNAL | DTK_ST_IRREGULAR));
+  }
+  // The rune offsets and sentence list of a reader of any length as data, for a caller that reads offsets and not text
+  // (what a NewTokenWriter with TOKEN_POS | SENTENCE_POS collects, newline_after_eot as its NEWLINE_AFTER_EOT):
+  // cb(const dtk_stream_slice &, const dtk_stream_offs &) gets every slice's arrays in order (dtk_stream_set_offsets;
+  // form: DTK_SO_PLAIN or DTK_SO_BLOCKED, decode with dtk_blk64_start / dtk_blk64_end where tok_rstart is null); they
+  // are valid inside the call.  A non-zero return of cb ends the run.  No closure is called and no text is rendered.
+  template <class Callback>
+  bool TransduceStreamOffsets(std::istream &r, Callback &&cb, bool newline_after_eot = false, uint32_t form = DTK_SO_PLAIN,
+                              uint64_t slice_bytes = 16u << 20, uint32_t depth = 3) {
+    last_status_ = 0;
+    dtk_stream *s = nullptr;
+    if (dtk_stream_create(slice_bytes, depth, &s) != DTK_OK) return false;
+    int rc = dtk_stream_set_offsets(s, 1, form);
+    if (rc == DTK_OK) rc = dtk_stream_set_result_fields(s, DTK_R_TOK_BYTE_BLK);
+    if (rc == DTK_OK) {
+      struct Ctx { std::istream *r; dtk_stream *s; typename std::remove_reference<Callback>::type *cb; } c{&r, s, &cb};
+      auto rd = [](void *u, uint8_t *buf, size_t cap) -> size_t {
+        Ctx *c = static_cast<Ctx *>(u);
+        c->r->read(reinterpret_cast<char *>(buf), (std::streamsize)cap);
+        return (size_t)c->r->gcount();
+      };
+      auto on_slice = [](void *u, const dtk_stream_slice *sl) -> int {
+        Ctx *c = static_cast<Ctx *>(u);
+        dtk_stream_offs o;
+        const int rc = dtk_stream_offsets(c->s, &o);
+        return rc != DTK_OK ? rc : (int)(*c->cb)(*sl, o);
+      };
+      rc = dtk_stream_run(s, m_, rd, &c, newline_after_eot ? (uint32_t)DTK_NEWLINE_AFTER_EOT : 0u, on_slice, &c, &last_status_);
+    }
+    dtk_stream_free(s);
     return rc == DTK_OK &&
            !(last_status_ & (DTK_ST_WINDOW_OVERFLOW | DTK_ST_BAD_MODEL | DTK_ST_STEP_LIMIT | DTK_ST_INTERNAL | DTK_ST_IRREGULAR));
   }

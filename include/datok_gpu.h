@@ -454,9 +454,10 @@ int dtk_pipeline_run(dtk_pipeline *p, const dtk_model *m, const uint8_t *text, c
  *        slice_fn gets the slices in order on the calling thread.  All positions of `view` (tok_bstart / tok_bend or the
  *      blocked form, evl_pos or the bitmaps, doc_tail) are relative to the window, whose byte 0 is stream byte `base`;
  *      a replay starts with the window start (buffer[0] of the reference) at `first`.  The writer's rune offsets and
- *      sentence list run across cuts (posC, sentB, init of token_writer.go:38-42) and are read in the position modes
- *      only; tok_rstart / tok_rend / sent of a slice's view are not delivered, and dtk_stream_set_result_fields rejects
- *      the rune fields.  The device renders a slice's writer bytes in every mode (`out` / `out_len`): in the four
+ *      sentence list run across cuts (posC, sentB, init of token_writer.go:38-42): tok_rstart / tok_rend / sent of a
+ *      slice's view -- the compaction's view of the window as a fresh document -- are not delivered, and
+ *      dtk_stream_set_result_fields rejects the rune fields; the stream's offsets come as arrays of their own, 64-bit
+ *      and computed on the device from the carried state (dtk_stream_set_offsets, dtk_stream_offsets).  The device renders a slice's writer bytes in every mode (`out` / `out_len`): in the four
  *      position-free modes (TOKENS, SENTENCES, both, neither; NEWLINE_AFTER_EOT changes nothing there) the writer is
  *      stateless (dtk_stream_set_render); with TOKEN_POS or SENTENCE_POS its state is carried from slice to slice on
  *      the device (dtk_stream_set_position_render, dtk_stream_emit).  A custom TokenWriter's closures are fed by the
@@ -485,7 +486,9 @@ void dtk_stream_free(dtk_stream *s);
 /* as dtk_batch_set_chunking; chunk_bytes 0 (one lane per slice), 16..2048 or 0xFFFFFFFF (by slice size) */
 int dtk_stream_set_chunking(dtk_stream *s, uint32_t chunk_bytes, uint32_t warm_bytes);
 /* The DTK_R_* arrays of every slice's view.  DTK_R_CSR, DTK_R_STATUS, DTK_R_TEXTS and DTK_R_EVENT_LIST always come;
- * the token bytes must be among them as DTK_R_TOK_BYTE or DTK_R_TOK_BYTE_BLK (else DTK_E_ARG).  Default: DTK_R_TOK_BYTE. */
+ * the token bytes must be among them as DTK_R_TOK_BYTE or DTK_R_TOK_BYTE_BLK (else DTK_E_ARG).  Default: DTK_R_TOK_BYTE.
+ * The rune fields (DTK_R_TOK_RUNE*, DTK_R_SENT) are DTK_E_ARG: a slice's view is the compaction's fresh-document view,
+ * and the way to the stream's rune offsets and sentence list is dtk_stream_set_offsets. */
 int dtk_stream_set_result_fields(dtk_stream *s, uint32_t fields);
 /* on != 0: every slice also brings the bytes a stock NewTokenWriter(w, bits) writes for its calls, rendered on the device
  * behind the slice's event list and in front of its copies (about one more byte per input byte on the link); the
@@ -531,6 +534,52 @@ typedef int (*dtk_write_fn)(void *user, const uint8_t *bytes, size_t n); /* DTK_
  * strings, start empty with every run, and grow with the length of a TEXT (not of the stream), as the reference's pos[]
  * and sent[] do: some 11 bytes per token of the text that is open.  A non-zero return of w ends the call with it. */
 int dtk_stream_emit(dtk_stream *s, dtk_write_fn w, void *user);
+/* ---- a stream's rune offsets and sentence list as arrays: what the batch path hands out as tok_rstart / tok_rend /
+ *      sent / text_tok_end / text_sent_end, for ONE stream of any length, slice by slice.
+ * on != 0: every slice also brings the rune offsets and sentence list that a NewTokenWriter with
+ * TOKEN_POS | SENTENCE_POS (and NEWLINE_AFTER_EOT iff dtk_stream_run's flags carry it) collects during the
+ * slice's calls, computed on the device from the writer's state behind the predecessor, which stays on the device
+ * between slices like position rendering's.  form: DTK_SO_PLAIN (16 B per token) or DTK_SO_BLOCKED (4.375), else
+ * DTK_E_ARG.  May be on beside dtk_stream_set_render (the surfaces as text, the offsets as arrays) or alone; with
+ * dtk_stream_set_position_render it is exclusive: turning either on while the other is on is DTK_E_ARG and changes
+ * nothing.  dtk_stream_transduce turns it off.
+ *   The slices' arrays one behind the other, the slice-relative text_tok_end / text_sent_end rebased by the running
+ * counts of tokens and sent ints, are what one writer collects for the whole stream: the rows of a text that spans cuts
+ * are the rows since the previous TextEnd, across slices.  Offsets are 64-bit: a stream without U+0004 is one text of any
+ * length, and posC is Go's int.  A SentenceEnd in a text without a token pushes nothing (DTK_ST_EMPTY_TEXT; the
+ * reference panics).  A token whose end offset is 0 under DTK_NEWLINE_AFTER_EOT ends the run with DTK_E_IRREGULAR, more
+ * calls than the capacity bound allows for with DTK_E_CAPACITY, as in position rendering.
+ *   The blocked form is dtk_off_block's, word for word, with 64-bit bases: tokens in the slice's order, block j holds
+ * the tokens [64j, 64j + 64) of the slice, the last one is partial;
+ *     brk   = the smallest lane l >= 1 of the block with start[64j + l] < end[64j + l - 1], or 64 if there is none
+ *     base0 = the minimum over every start and end of the lanes < brk
+ *     base1 = the minimum over the lanes >= brk, or 0 if brk == 64
+ *     word[i] = (start[i] - base) | (end[i] - base) << 16   with base = lane < brk ? base0 : base1
+ * A slice in which some segment of some block spans more than 65 535 gets the plain arrays in its place (copied when
+ * the slice is delivered), and the blocked pointers are NULL. ---- */
+enum { DTK_SO_PLAIN = 0, DTK_SO_BLOCKED = 1 };
+int dtk_stream_set_offsets(dtk_stream *s, int on, uint32_t form);
+typedef struct { int64_t base0, base1; uint32_t brk, reserved; } dtk_off_block64; /* 24 bytes */
+DTK_BLK_DECODER int64_t dtk_blk64_start(const uint32_t *words, const dtk_off_block64 *heads, uint64_t i) {
+  const dtk_off_block64 *h = heads + (i >> 6);
+  return ((uint32_t)(i & 63u) < h->brk ? h->base0 : h->base1) + (int64_t)(words[i] & 0xFFFFu);
+}
+DTK_BLK_DECODER int64_t dtk_blk64_end(const uint32_t *words, const dtk_off_block64 *heads, uint64_t i) {
+  const dtk_off_block64 *h = heads + (i >> 6);
+  return ((uint32_t)(i & 63u) < h->brk ? h->base0 : h->base1) + (int64_t)(words[i] >> 16);
+}
+typedef struct {
+  uint64_t n_tok, n_sent, n_text;          /* Token calls, ints pushed to sent[], TextEnd calls of THIS slice */
+  const int64_t *tok_rstart, *tok_rend;    /* n_tok each; NULL when the blocked form was delivered */
+  const uint32_t *tok_rblk;                /* n_tok words; NULL when the plain form was delivered */
+  const dtk_off_block64 *tok_rblk_head;    /* ceil(n_tok / 64) */
+  const int64_t *sent;                     /* n_sent, in push order */
+  const uint32_t *text_tok_end, *text_sent_end; /* n_text each: tokens / sent ints of this slice in front of the g-th TextEnd */
+  dtk_stream_carry carry_in, carry_out;    /* the writer in front of and behind the slice */
+} dtk_stream_offs;
+/* Inside slice_fn, with offset delivery on: the slice being delivered (else DTK_E_STATE).  Page-locked host memory,
+ * valid until slice_fn returns. */
+int dtk_stream_offsets(dtk_stream *s, dtk_stream_offs *o);
 /* flags: DTK_NEWLINE_AFTER_EOT is accepted and changes nothing here (it only moves the writer's rune offsets), except
  * that with position rendering on it must be the bit dtk_stream_set_position_render got.  Short
  * reads are retried until a buffer is full; read_fn is not called again after it has returned 0. */

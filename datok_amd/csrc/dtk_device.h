@@ -1,5 +1,6 @@
-// dtk_device.h -- what the kernel units share: wave helpers, the windows macro of the walk kernels, the per-document
-// repair step (used by the verification's fix kernel and by the one-launch scan).
+// dtk_device.h -- what the kernel units share: wave helpers, the windows macro of the walk kernels, the block scan, the
+// search and the list reads of a stream slice's units, the per-document repair step (used by the verification's fix
+// kernel and by the one-launch scan).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -70,6 +71,67 @@ __device__ __forceinline__ int32_t wave_max(int32_t v) {
   DTK_WAVE_FOLD(x, max);
   return __builtin_amdgcn_readlane(x, WAVE - 1);
 }
+
+// ---- what the kernels of a stream slice's outputs share (dtk_streamrender, dtk_streampos, dtk_streamoffs .hip): blocks
+// of 256 threads over tiles of 256 tokens or list entries
+
+// exclusive prefix sum of a 64-bit value over the block's 256 threads; wave_tot: 256 / WAVE words of LDS
+__device__ __forceinline__ uint64_t block_excl_scan64(uint64_t v, uint64_t *wave_tot, uint64_t &total) {
+  const uint64_t inc = wave_incl_scan64(v);
+  const uint32_t wave = threadIdx.x >> 6;
+  __syncthreads();  // (the previous use of wave_tot has been read)
+  if (lane_id() == WAVE - 1u) wave_tot[wave] = inc;
+  __syncthreads();
+  uint64_t before = 0;
+  total = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 256u / WAVE; k++) {
+    const uint64_t t = wave_tot[k];
+    before += k < wave ? t : 0u;
+    total += t;
+  }
+  return before + inc - v;
+}
+
+// exclusive scan of base[0 .. n) in place by one block of 256 threads; returns the sum
+__device__ __forceinline__ uint64_t scan_row64(uint64_t *base, uint32_t n, uint64_t *wave_tot) {
+  uint64_t carry = 0;
+  for (uint32_t i0 = 0; i0 < n; i0 += 256u) {  // (block-uniform trip count)
+    const uint32_t i = i0 + threadIdx.x;
+    const uint64_t v = i < n ? base[i] : 0u;
+    uint64_t total;
+    const uint64_t x = block_excl_scan64(v, wave_tot, total);
+    if (i < n) base[i] = carry + x;
+    carry += total;
+  }
+  return carry;
+}
+
+// first i in [0, n) with a[i] >= x, else n
+__device__ __forceinline__ uint32_t lower_bound32(const uint32_t *__restrict__ a, uint32_t n, uint32_t x) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] < x) lo = mid + 1u; else hi = mid;
+  }
+  return lo;
+}
+
+// the length of the slice's event list, or 0xFFFFFFFF if it did not fit its arrays (nothing is computed then)
+template <class A>
+__device__ __forceinline__ uint32_t evl_entries(const A &a) {
+  const uint32_t n = *a.evl_count;
+  return n > a.evl_cap ? 0xFFFFFFFFu : n;
+}
+
+// byte i of the text did not decode: it prints as U+FFFD (as is_invalid_byte of dtk_render.hip)
+__device__ __forceinline__ bool sym_invalid_byte(const DtkSym &S, uint64_t i) {
+  const uint32_t e = dtk_sym_entry(S, i);
+  return DTK_SYM_WIDTH(e) == 1u && ((e >> DTK_SYM_CLS_SHIFT) & 3u) >= 2u;
+}
+
+// 64-bit words that hold n 32-bit ones (a workspace is laid out in 64-bit words)
+inline uint64_t words32(uint64_t n) { return (n + 1u) / 2u; }
 
 __device__ __forceinline__ uint32_t doc_of(const uint64_t *__restrict__ doc_off, uint32_t lo, uint32_t hi,
                                            uint64_t g) {

@@ -1,5 +1,5 @@
-// dtk_host.h -- what the host units of libdatok_gpu.so (dtk_model, dtk_foma, dtk_batch, dtk_results .cpp) share: the
-// model and batch objects, the error state, the test hooks, and helpers (hidden, not exported).  No .hip unit includes it.
+// dtk_host.h -- what the host units of libdatok_gpu.so (dtk_model, dtk_foma, dtk_batch, dtk_results, dtk_slice .cpp) share:
+// the model and batch objects, the error state, the test hooks, and helpers (hidden, not exported).  No .hip unit includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -79,6 +79,52 @@ int gunzip(const uint8_t *gz, size_t n, std::vector<uint8_t> &out);
 bool special_ids_ok(const dtk_model *m);
 int layout_matrix(dtk_model *m, const std::vector<uint32_t> &arr, uint64_t n_states, bool da_dense);
 int build_foma(dtk_model *m, const std::vector<uint8_t> &raw);
+
+// ------------------------------------------------------ a stream slice's device outputs
+//
+// What the next download of a batch that is a slot of a stream (dtk_streamer.cpp) computes beside the result arrays, on
+// the download stream behind every packing of the event list (dtk_slice.cpp).  A default-constructed request: nothing.
+struct SliceRequest {
+  uint32_t first = 0, cut = 0;  // the slice's calls: those of the window bytes [first, cut]
+  bool last = false;            // ... and the tail word's (the stream's last slice)
+  // NewTokenWriter(w, bits)'s bytes for these calls: in a position-free mode (dtk_stream_set_render,
+  // dtk_streamrender.hip; bits: TOKENS | SENTENCES) or in a position mode (dtk_stream_set_position_render,
+  // dtk_streampos.hip; all five writer bits)
+  enum Bytes : uint8_t { kNoBytes, kPlainBytes, kPosBytes } bytes = kNoBytes;
+  uint32_t bits = 0;
+  // the writer's rune offsets and sentence list as arrays (dtk_stream_set_offsets, dtk_streamoffs.hip), beside the
+  // position-free bytes or without them
+  bool offs = false;
+  uint32_t form = 0;            // DTK_SO_*
+  bool is_matrix = false;
+  bool nl = false;              // the run's NEWLINE_AFTER_EOT (offsets; a position mode has it in bits)
+  uint32_t digits = 0;          // kPosBytes: no integer of the slice has more bytes (the stream's bound)
+  // kPosBytes or offs: the writer's state comes from one of the stream's carry slots and goes into another
+  const DtkPosCarry *carry_in = nullptr;
+  DtkPosCarry *carry_out = nullptr;
+};
+// The offsets' device block and its page-locked copy have one layout (byte offsets, fixed before anything is enqueued):
+// tok_rstart | tok_rend | sent | trailer | text_tok_end | text_sent_end | heads | words.  The copies bring the plain or
+// the blocked offsets, sent and the text rows as far as the compaction's counts reach, and the trailer; what the
+// trailer then asks for beyond that (blk_fail: the plain offsets; more sent ints or rows) is copied at delivery.
+struct SoLayout {
+  uint64_t n = 0, sent_cap = 0, text_cap = 0;  // the capacities: tokens (exact), sent ints, texts
+  uint64_t sent_home = 0, text_home = 0;       // sent ints / text rows the page-locked copy holds
+  uint64_t rstart = 0, rend = 0, sent = 0, trailer = 0, ttok = 0, tsent = 0, heads = 0, words = 0, bytes = 0;
+  bool blocked = false, wide_home = false;     // wide_home: tok_rstart / tok_rend are in the page-locked copy
+};
+struct SliceOut {
+  SliceRequest req;
+  // the bytes: d_out (cap bytes, then the length word or the trailer block) and its page-locked copy, both sized
+  // before anything is enqueued
+  uint64_t cap = 0;             // of the rendering under way
+  DevArray<uint8_t> d_out;
+  DevArray<uint64_t> d_ws;      // the renderer's workspace (tile sums and scans)
+  PinBuf h_out;
+  SoLayout so;
+  DevArray<uint64_t> d_offs_ws, d_offs_out;
+  PinBuf h_offs_out;
+};
 
 // -------------------------------------------------------------------- batch
 
@@ -221,40 +267,7 @@ struct dtk_batch {
   bool has_carry = false;
   DevArray<DtkLaneState> d_init_rec, d_open_fin;  // [1] each
   PinBuf h_init_rec;
-  // The slice's writer bytes in a position-free mode (dtk_stream_set_render, dtk_streamrender.hip): rendered on the
-  // download stream behind every packing of the event list, into sr_out (sr_cap bytes + the length word) and from
-  // there into its page-locked copy.  Both are sized from the totals before anything is enqueued.
-  bool sr_on = false, sr_last = false;
-  uint32_t sr_bits = 0, sr_first = 0, sr_cut = 0;
-  uint64_t sr_cap = 0;             // of the rendering under way
-  DevArray<uint8_t> d_sr_out;
-  DevArray<uint64_t> d_sr_ws;      // tile sums of tokens and entries, the entries' scan
-  PinBuf h_sr_out;
-  // ... and in a position mode (dtk_stream_set_position_render, dtk_streampos.hip): the same buffers, the trailer block
-  // behind the bytes; the writer's state comes from one of the stream's carry slots and goes into another
-  bool sp_on = false, sp_matrix = false;
-  uint32_t sp_digits = 0;          // no integer of the slice has more bytes (the stream's bound)
-  const DtkPosCarry *sp_carry_in = nullptr;
-  DtkPosCarry *sp_carry_out = nullptr;
-  DevArray<uint64_t> d_sp_ws;
-  // The slice's rune offsets and sentence list as arrays (dtk_stream_set_offsets, dtk_streamoffs.hip): computed in the
-  // same place from carry slots of their own, beside batch_set_render's bytes or without them.  One device block and
-  // its page-locked copy with the same layout (byte offsets, fixed before anything is enqueued): tok_rstart | tok_rend |
-  // sent | trailer | text_tok_end | text_sent_end | heads | words.  The copies bring the plain or the blocked offsets,
-  // sent and the text rows as far as the compaction's counts reach, and the trailer; what the trailer then asks for
-  // beyond that (blk_fail: the plain offsets; more sent ints or rows) is copied at delivery.
-  bool so_on = false, so_matrix = false, so_nl = false;
-  uint32_t so_form = 0;            // DTK_SO_*
-  const DtkPosCarry *so_carry_in = nullptr;
-  DtkPosCarry *so_carry_out = nullptr;
-  struct SoLayout {
-    uint64_t n = 0, sent_cap = 0, text_cap = 0;  // the capacities: tokens (exact), sent ints, texts
-    uint64_t sent_home = 0, text_home = 0;       // sent ints / text rows the page-locked copy holds
-    uint64_t rstart = 0, rend = 0, sent = 0, trailer = 0, ttok = 0, tsent = 0, heads = 0, words = 0, bytes = 0;
-    bool blocked = false, wide_home = false;     // wide_home: tok_rstart / tok_rend are in the page-locked copy
-  } so;
-  DevArray<uint64_t> d_so_ws, d_so_out;
-  PinBuf h_so_out;
+  SliceOut slice;  // what the slice brings home beside the result arrays (dtk_slice.cpp)
   uint32_t eager_fields = 0;  // the last run's k_to_host was asked for these (0: none); finish() decides whether it counts
   bool results_changed = false;  // finish() had to touch the result arrays after the run (repair, growth, EOT kernel, exact pass)
   Event ev_dl;                 // behind the batch's copies on the (possibly shared) download stream
@@ -272,18 +285,12 @@ int launch_to_host(dtk_batch *b);
 // does) and the record to start from (null: the stream's beginning).  batch_cut: the last run's cut block, behind finish().
 int batch_set_slice(dtk_batch *b, uint32_t open_slice, const DtkLaneState *carry);
 int batch_cut(dtk_batch *b, DtkStreamCut *out);
-// The slice's next download renders NewTokenWriter(w, bits)'s bytes for the calls in [first, cut] (last: the tail word's
-// too); batch_render_out: behind dtk_batch_result_host, the page-locked bytes.
-void batch_set_render(dtk_batch *b, bool on, uint32_t bits, uint32_t first, uint32_t cut, bool last);
-int batch_render_out(dtk_batch *b, const uint8_t **out, uint64_t *out_len);
-// The same in a position mode: bits holds all five writer bits; on == false returns to batch_set_render's renderer.
-// batch_pos_out: the page-locked bytes and the trailer block behind them (DTK_E_CAPACITY / DTK_E_IRREGULAR as it says).
-void batch_set_pos_render(dtk_batch *b, bool on, bool is_matrix, uint32_t digits, const DtkPosCarry *carry_in, DtkPosCarry *carry_out);
-int batch_pos_out(dtk_batch *b, const uint8_t **out, const DtkPosTrailer **trailer);
-// The slice's next download also computes its rune offsets and sentence list (form: DTK_SO_*; nl: the run's
-// NEWLINE_AFTER_EOT) from carry_in, and leaves the writer's state in carry_out.  batch_offs_out: behind
-// dtk_batch_result_host, the page-locked arrays (DTK_E_CAPACITY / DTK_E_IRREGULAR as the trailer says); the blocked
-// pointers are null where the plain arrays stand in, and the other way round.
+// dtk_slice.cpp.  batch_set_slice_request: what the slice's next download computes; slice_outputs: enqueues it on the
+// download stream (dtk_batch_download_begin, behind the event list).  Behind dtk_batch_result_host:
+//   batch_render_out  kPlainBytes: the page-locked bytes
+//   batch_pos_out     kPosBytes: the bytes and the trailer block behind them (DTK_E_CAPACITY / DTK_E_IRREGULAR as it says)
+//   batch_offs_out    offs: the page-locked arrays (DTK_E_CAPACITY / DTK_E_IRREGULAR as the trailer says); the blocked
+//                     pointers are null where the plain arrays stand in, and the other way round
 struct SoView {
   const DtkOffsTrailer *t;
   const int64_t *rstart, *rend, *sent;
@@ -291,8 +298,12 @@ struct SoView {
   const DtkOffBlock64 *heads;
   const uint32_t *ttok, *tsent;
 };
-void batch_set_offsets(dtk_batch *b, bool on, uint32_t form, bool is_matrix, bool nl, const DtkPosCarry *carry_in, DtkPosCarry *carry_out);
+inline void batch_set_slice_request(dtk_batch *b, const SliceRequest &q) { b->slice.req = q; }
+int slice_outputs(dtk_batch *b);
+int batch_render_out(dtk_batch *b, const uint8_t **out, uint64_t *out_len);
+int batch_pos_out(dtk_batch *b, const uint8_t **out, const DtkPosTrailer **trailer);
 int batch_offs_out(dtk_batch *b, SoView *o);
+inline uint64_t blocks_of(uint64_t tokens) { return (tokens + 63) / 64; }  // blocks of 64 tokens
 
 // The DTK_R_* arrays the last run wrote: DTK_NO_RUNE_OFFSETS / DTK_NO_BYTE_OFFSETS leave theirs alone.
 inline uint32_t run_fields(const dtk_batch *b) {

@@ -31,7 +31,6 @@ static_assert(DTK_EVL_SEOT == DTK_EVL_K_SEOT && DTK_EVL_TEOT == DTK_EVL_K_TEOT &
 constexpr uint32_t kBlkFields = DTK_R_TOK_RUNE_BLK | DTK_R_TOK_BYTE_BLK;
 constexpr uint32_t kBlkField[2] = {DTK_R_TOK_RUNE_BLK, DTK_R_TOK_BYTE_BLK};
 constexpr uint32_t kBlkWide[2] = {DTK_R_TOK_RUNE, DTK_R_TOK_BYTE};  // what stands in for a pair that does not fit
-uint64_t blocks_of(uint64_t tokens) { return (tokens + 63) / 64; }
 
 // The batch's arrays, in the order their copies are enqueued: the large ones first (k_to_host deals its pieces out to
 // its waves by array; on the download stream the small copies ride behind the large ones).
@@ -123,228 +122,7 @@ int pack_event_list(dtk_batch *b, uint64_t rows) {
   b->evl_copied = rows;
   return DTK_OK;
 }
-
-// dtk_stream_set_render: the slice's writer bytes, behind the list's kernels on the download stream and in front of
-// the copies.  The output is sized here, from what the host knows: a surface byte per window byte of the slice (three
-// where the run saw invalid UTF-8), a newline per token, SentenceEnd and TextEnd call, and the tail's two.
-int render_slice(dtk_batch *b) {
-  if (b->n_docs != 1 || b->total > 0xFFFFFFFFull) return DTK_E_STATE;
-  const uint64_t span = b->sr_cut > b->sr_first ? b->sr_cut - b->sr_first : 0;
-  const uint64_t cap = span * (b->n_invalid ? 3u : 1u) + b->totals.n_tokens + b->totals.n_sent + b->totals.n_texts + 2;
-  const uint64_t cap8 = (cap + 7u) & ~7ull;  // (the length word lies behind the bytes)
-  const uint64_t rows = b->evl_copied;
-  const uint32_t tt = dtk_streamrender_tiles(b->totals.n_tokens), et = dtk_streamrender_tiles(rows);
-  const uint64_t words = (uint64_t)tt + et + rows + 1;
-  int rc;
-  if ((rc = b->d_sr_out.fit(cap8 + 8, cap8 + cap8 / 8 + 264)) || (rc = b->d_sr_ws.fit(words, words + words / 8 + 16)) ||
-      (rc = b->h_sr_out.fit((size_t)(cap8 + 8))))
-    return rc;
-  DtkStreamRenderArgs a{};
-  a.bits = b->sr_bits & 3u; a.with_tail = b->sr_last ? 1u : 0u;
-  a.text = b->d_text; a.text_len = (uint32_t)b->total;
-  a.sym = sym_of(b); if (!b->n_invalid) a.sym.base = nullptr;
-  a.n_tok = b->totals.n_tokens; a.tok_bstart = b->d_bstart; a.tok_bend = b->d_bend;
-  a.evl_pos = b->d_evl_pos; a.evl_kind = b->d_evl_kind; a.evl_count = b->d_evl_cnt; a.evl_cap = (uint32_t)rows;
-  a.doc_tail = b->d_doc_tail;
-  a.tok_tiles = tt; a.ent_tiles = et;
-  a.tok_base = b->d_sr_ws; a.ent_base = a.tok_base + tt; a.ew = a.ent_base + et;
-  a.out = b->d_sr_out; a.cap = cap; a.out_len = reinterpret_cast<uint64_t *>(b->d_sr_out.p + cap8);
-  HIP_TRY(hipMemsetAsync(b->d_sr_out, '\n', cap8, b->dl_stream));  // every byte that is no surface byte
-  if (dtk_launch_streamrender(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "render slice");
-  HIP_TRY(hipMemcpyAsync(b->h_sr_out.p, b->d_sr_out, (size_t)(cap8 + 8), hipMemcpyDeviceToHost, b->dl_stream));
-  b->sr_cap = cap;
-  return DTK_OK;
-}
-
-// dtk_stream_set_position_render: the same place, dtk_streampos.hip.  The capacity is a bound the host can state before
-// anything is enqueued: the kernels render nothing for a list of more than `rows` entries, so
-// the slice has at most 2 * rows + 1 SentenceEnd calls and rows + 1 TextEnd calls; a token pushes two position
-// integers, and a sentence integer comes from a token behind such a call or from a SentenceEnd call; no integer has
-// more than sp_digits bytes.  The open fragments lie behind the output inside the same bound.
-int render_slice_pos(dtk_batch *b) {
-  if (b->n_docs != 1 || b->total > 0xFFFFFFFFull || !b->sp_carry_in || !b->sp_carry_out) return DTK_E_STATE;
-  const uint64_t span = b->sr_cut > b->sr_first ? b->sr_cut - b->sr_first : 0;
-  const uint64_t rows = b->evl_copied, nt = b->totals.n_tokens;
-  const uint64_t calls = 3 * rows + 2;
-  const uint64_t ints = ((b->sr_bits & DTK_TOKEN_POS) ? 2 * nt : 0) +
-                        ((b->sr_bits & DTK_SENTENCE_POS) ? std::min<uint64_t>(nt, calls + 1) + 2 * rows + 1 : 0);
-  const uint64_t cap = ((b->sr_bits & DTK_TOKENS) ? span * (b->n_invalid ? 3u : 1u) + nt : 0) + calls +
-                       ints * ((uint64_t)b->sp_digits + 1u) + 2 * (rows + 2);
-  const uint64_t cap8 = (cap + 7u) & ~7ull;
-  const uint64_t bytes = cap8 + sizeof(DtkPosTrailer);
-  DtkStreamPosArgs a{};
-  a.bits = b->sr_bits & 31u; a.with_tail = b->sr_last ? 1u : 0u; a.is_matrix = b->sp_matrix ? 1u : 0u; a.first = b->sr_first;
-  a.text = b->d_text; a.text_len = (uint32_t)b->total;
-  a.sym = sym_of(b); if (!b->n_invalid) a.sym.base = nullptr;
-  a.n_tok = nt; a.tok_bstart = b->d_bstart; a.tok_bend = b->d_bend;
-  a.evl_pos = b->d_evl_pos; a.evl_kind = b->d_evl_kind; a.evl_count = b->d_evl_cnt; a.evl_cap = (uint32_t)rows;
-  a.doc_tail = b->d_doc_tail;
-  a.tok_tiles = dtk_streamrender_tiles(nt); a.ent_tiles = dtk_streamrender_tiles(rows);
-  a.carry_in = b->sp_carry_in; a.carry_out = b->sp_carry_out;
-  const uint64_t words = dtk_streampos_ws(&a, nullptr);
-  int rc;
-  if ((rc = b->d_sr_out.fit(bytes, bytes + bytes / 8 + 264)) || (rc = b->d_sp_ws.fit(words, words + words / 8 + 16)) ||
-      (rc = b->h_sr_out.fit((size_t)bytes)))
-    return rc;
-  (void)dtk_streampos_ws(&a, b->d_sp_ws);
-  a.out = b->d_sr_out; a.cap = cap; a.trailer = reinterpret_cast<DtkPosTrailer *>(b->d_sr_out.p + cap8);
-  HIP_TRY(hipMemsetAsync(b->d_sr_out, '\n', cap8, b->dl_stream));  // every byte that is no surface byte and no integer's
-  if (dtk_launch_streampos(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "render slice positions");
-  HIP_TRY(hipMemcpyAsync(b->h_sr_out.p, b->d_sr_out, (size_t)bytes, hipMemcpyDeviceToHost, b->dl_stream));
-  b->sr_cap = cap;
-  return DTK_OK;
-}
-
-// dtk_stream_set_offsets: the same place, dtk_streamoffs.hip.  The capacities are bounds the host can state before
-// anything is enqueued, from the tokens and the list's rows: the kernels compute nothing for a
-// list of more than `rows` entries, so the slice has at most 2 * rows + 1 SentenceEnd calls and rows + 1 TextEnd
-// calls; a SentenceEnd call pushes one int, and a token pushes one if such a call (or the carry) lies in front of it.
-int slice_offsets(dtk_batch *b) {
-  if (b->n_docs != 1 || b->total > 0xFFFFFFFFull || !b->so_carry_in || !b->so_carry_out) return DTK_E_STATE;
-  const uint64_t rows = b->evl_copied, nt = b->totals.n_tokens;
-  dtk_batch::SoLayout L;
-  L.n = nt; L.sent_cap = std::min<uint64_t>(nt, 3 * rows + 3) + 2 * rows + 1; L.text_cap = rows + 1;
-  L.blocked = b->so_form == DTK_SO_BLOCKED;
-  // What the copies bring of sent and the text rows: the compaction's counts for the window as a fresh document, which
-  // differ from the stream's by the few calls in front of the slice's first token.  batch_offs_out brings the rest if
-  // the trailer counts more (the debug key EVL_CAP sizes these too, so that ordinary text gets there).
-  L.sent_home = std::min<uint64_t>(L.sent_cap, g_dbg.evl_cap >= 0 ? (uint64_t)g_dbg.evl_cap : b->totals.n_sent + 64);
-  L.text_home = std::min<uint64_t>(L.text_cap, g_dbg.evl_cap >= 0 ? (uint64_t)g_dbg.evl_cap : b->totals.n_texts + 2);
-  uint64_t at = 0;  // (bytes; every piece begins on a multiple of 8)
-  auto take = [&](uint64_t bytes) { const uint64_t o = at; at += (bytes + 7u) & ~7ull; return o; };
-  L.rstart = take(nt * 8); L.rend = take(nt * 8); L.sent = take(L.sent_cap * 8);
-  L.trailer = take(sizeof(DtkOffsTrailer)); L.ttok = take(L.text_cap * 4); L.tsent = take(L.text_cap * 4);
-  L.heads = take(L.blocked ? blocks_of(nt) * sizeof(DtkOffBlock64) : 0); L.words = take(L.blocked ? nt * 4 : 0);
-  L.bytes = at;
-  DtkStreamOffsArgs a{};
-  DtkStreamPosArgs &f = a.front;
-  f.bits = DTK_TOKEN_POS | DTK_SENTENCE_POS | (b->so_nl ? (uint32_t)DTK_NEWLINE_AFTER_EOT : 0u);
-  f.with_tail = b->sr_last ? 1u : 0u; f.is_matrix = b->so_matrix ? 1u : 0u; f.first = b->sr_first;
-  f.text = b->d_text; f.text_len = (uint32_t)b->total;
-  f.sym = sym_of(b); if (!b->n_invalid) f.sym.base = nullptr;
-  f.n_tok = nt; f.tok_bstart = b->d_bstart; f.tok_bend = b->d_bend;
-  f.evl_pos = b->d_evl_pos; f.evl_kind = b->d_evl_kind; f.evl_count = b->d_evl_cnt; f.evl_cap = (uint32_t)rows;
-  f.doc_tail = b->d_doc_tail;
-  f.tok_tiles = dtk_streamrender_tiles(nt); f.ent_tiles = dtk_streamrender_tiles(rows);
-  f.carry_in = b->so_carry_in; f.carry_out = b->so_carry_out;
-  const uint64_t words = dtk_streamoffs_ws(&a, nullptr), out_words = L.bytes / 8;
-  int rc;
-  if ((rc = b->d_so_ws.fit(words, words + words / 8 + 16)) || (rc = b->d_so_out.fit(out_words, out_words + out_words / 8 + 32)) ||
-      (rc = b->h_so_out.fit((size_t)L.bytes)))
-    return rc;
-  (void)dtk_streamoffs_ws(&a, b->d_so_ws);
-  uint8_t *d = reinterpret_cast<uint8_t *>(b->d_so_out.p), *h = b->h_so_out.as<uint8_t>();
-  f.rstart = reinterpret_cast<int64_t *>(d + L.rstart); f.rend = reinterpret_cast<int64_t *>(d + L.rend);
-  a.sent = reinterpret_cast<int64_t *>(d + L.sent); a.sent_cap = L.sent_cap; a.text_cap = L.text_cap;
-  a.trailer = reinterpret_cast<DtkOffsTrailer *>(d + L.trailer);
-  a.text_tok_end = reinterpret_cast<uint32_t *>(d + L.ttok); a.text_sent_end = reinterpret_cast<uint32_t *>(d + L.tsent);
-  a.blocked = L.blocked ? 1u : 0u; a.span = g_dbg.blk_span > 0 ? (uint32_t)g_dbg.blk_span : 65535u;
-  a.heads = reinterpret_cast<DtkOffBlock64 *>(d + L.heads); a.words = reinterpret_cast<uint32_t *>(d + L.words);
-  if (dtk_launch_streamoffs(&a, b->dl_stream, nullptr)) return hip_fail(hipGetLastError(), "slice offsets");
-  // the plain offsets and sent lie back to back; then the trailer with text_tok_end, text_sent_end, the blocked form
-  const uint64_t piece[4][2] = {{L.blocked ? L.sent : 0, L.sent + L.sent_home * 8},
-                                {L.trailer, L.ttok + L.text_home * 4},
-                                {L.tsent, L.tsent + L.text_home * 4},
-                                {L.heads, L.blocked ? L.bytes : L.heads}};
-  for (const auto &q : piece)
-    if (q[1] > q[0]) HIP_TRY(hipMemcpyAsync(h + q[0], d + q[0], (size_t)(q[1] - q[0]), hipMemcpyDeviceToHost, b->dl_stream));
-  L.wide_home = !L.blocked;
-  b->so = L;
-  return DTK_OK;
-}
 }  // namespace
-
-void batch_set_offsets(dtk_batch *b, bool on, uint32_t form, bool is_matrix, bool nl, const DtkPosCarry *carry_in, DtkPosCarry *carry_out) {
-  b->so_on = on; b->so_form = form; b->so_matrix = is_matrix; b->so_nl = nl; b->so_carry_in = carry_in; b->so_carry_out = carry_out;
-}
-
-int batch_offs_out(dtk_batch *b, SoView *o) {
-  if (!b->so_on || !b->dl_begun || !b->dl_waited || !b->h_so_out.p) return DTK_E_STATE;
-  dtk_batch::SoLayout &L = b->so;
-  const uint8_t *h = b->h_so_out.as<uint8_t>();
-  const DtkOffsTrailer *t = reinterpret_cast<const DtkOffsTrailer *>(h + L.trailer);
-  // (a list longer than its arrays says so with n_tok = ~0; more calls than the bound counts: no regular slice)
-  if (t->n_tok != L.n || t->n_sent > L.sent_cap || t->n_text > L.text_cap) return DTK_E_CAPACITY;
-  if (t->flags & 1u) return DTK_E_IRREGULAR;
-  // The slow paths, as a list that is packed again: a segment of a block spans more than 16 bits, so the plain arrays
-  // come over now; the slice has more sent ints or text rows than the copies brought.  The kernels' results stay where
-  // they are on the device, nothing is computed again.
-  const uint8_t *d = reinterpret_cast<const uint8_t *>(b->d_so_out.p);
-  uint8_t *hw = b->h_so_out.as<uint8_t>();
-  bool late = false;
-  auto bring = [&](uint64_t from, uint64_t to) -> int {
-    if (to > from) HIP_TRY(hipMemcpyAsync(hw + from, d + from, (size_t)(to - from), hipMemcpyDeviceToHost, b->dl_stream));
-    late = true;
-    return DTK_OK;
-  };
-  int rc;
-  if (L.blocked && t->blk_fail && !L.wide_home) {
-    if ((rc = bring(0, L.sent)) != DTK_OK) return rc;
-    L.wide_home = true;
-  }
-  if (t->n_sent > L.sent_home) {
-    if ((rc = bring(L.sent + L.sent_home * 8, L.sent + t->n_sent * 8)) != DTK_OK) return rc;
-    L.sent_home = t->n_sent;
-  }
-  if (t->n_text > L.text_home) {
-    if ((rc = bring(L.ttok + L.text_home * 4, L.ttok + t->n_text * 4)) != DTK_OK ||
-        (rc = bring(L.tsent + L.text_home * 4, L.tsent + t->n_text * 4)) != DTK_OK)
-      return rc;
-    L.text_home = t->n_text;
-  }
-  if (late) HIP_TRY(hipStreamSynchronize(b->dl_stream));
-  const bool plain = !L.blocked || t->blk_fail;
-  o->t = t;
-  o->rstart = plain ? reinterpret_cast<const int64_t *>(h + L.rstart) : nullptr;
-  o->rend = plain ? reinterpret_cast<const int64_t *>(h + L.rend) : nullptr;
-  o->words = plain ? nullptr : reinterpret_cast<const uint32_t *>(h + L.words);
-  o->heads = plain ? nullptr : reinterpret_cast<const DtkOffBlock64 *>(h + L.heads);
-  o->sent = reinterpret_cast<const int64_t *>(h + L.sent);
-  o->ttok = reinterpret_cast<const uint32_t *>(h + L.ttok); o->tsent = reinterpret_cast<const uint32_t *>(h + L.tsent);
-  return DTK_OK;
-}
-
-void batch_set_render(dtk_batch *b, bool on, uint32_t bits, uint32_t first, uint32_t cut, bool last) {
-  b->sr_on = on; b->sr_bits = bits; b->sr_first = first; b->sr_cut = cut; b->sr_last = last;
-  b->sp_on = false;
-}
-
-void batch_set_pos_render(dtk_batch *b, bool on, bool is_matrix, uint32_t digits, const DtkPosCarry *carry_in, DtkPosCarry *carry_out) {
-  b->sp_on = on; b->sp_matrix = is_matrix; b->sp_digits = digits; b->sp_carry_in = carry_in; b->sp_carry_out = carry_out;
-}
-
-// What a trailer block that has come home says about its slice: never bytes that differ silently.
-extern "C" int dtk_pos_trailer_check(const DtkPosTrailer *t, uint64_t cap) {
-  if (!t) return DTK_E_ARG;
-  // (more calls than the bound counts -- a list longer than its arrays says so with out_len = ~0 --, or a tile of
-  //  tokens whose integers pass 2^32 bytes: no regular slice)
-  if (t->out_len > cap || t->open_pos_len > cap || t->open_sent_len > cap ||
-      t->out_len + t->open_pos_len + t->open_sent_len > cap || (t->flags & 2u))
-    return DTK_E_CAPACITY;
-  if (t->flags & 1u) return DTK_E_IRREGULAR;  // the newline rule would fire a second time: the exact pass's, from a carried record
-  return DTK_OK;
-}
-
-int batch_pos_out(dtk_batch *b, const uint8_t **out, const DtkPosTrailer **trailer) {
-  if (!b->sr_on || !b->sp_on || !b->dl_begun || !b->dl_waited || !b->h_sr_out.p) return DTK_E_STATE;
-  const uint64_t cap8 = (b->sr_cap + 7u) & ~7ull;
-  const DtkPosTrailer *t = reinterpret_cast<const DtkPosTrailer *>(b->h_sr_out.as<uint8_t>() + cap8);
-  const int rc = dtk_pos_trailer_check(t, b->sr_cap);
-  if (rc != DTK_OK) return rc;
-  *out = b->h_sr_out.as<uint8_t>();
-  *trailer = t;
-  return DTK_OK;
-}
-
-int batch_render_out(dtk_batch *b, const uint8_t **out, uint64_t *out_len) {
-  if (!b->sr_on || !b->dl_begun || !b->dl_waited || !b->h_sr_out.p) return DTK_E_STATE;
-  const uint64_t cap8 = (b->sr_cap + 7u) & ~7ull;
-  const uint64_t n = *reinterpret_cast<const uint64_t *>(b->h_sr_out.as<uint8_t>() + cap8);
-  if (n > b->sr_cap) return DTK_E_CAPACITY;  // (more calls than the totals count: no regular slice)
-  *out = b->h_sr_out.as<uint8_t>();
-  *out_len = n;
-  return DTK_OK;
-}
 
 extern "C" int dtk_batch_result_device(dtk_batch *b, dtk_result_view *o) {
   if (!b || !o) return DTK_E_ARG;
@@ -440,9 +218,9 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
     tot[kPerEvent] = g_dbg.evl_cap >= 0 ? (uint64_t)g_dbg.evl_cap : tot[1] + tot[2];
     tot[kPerEvent] = std::max(tot[kPerEvent], b->evl_need);
     if ((rc = pack_event_list(b, tot[kPerEvent])) != DTK_OK) return rc;
-    // (a list packed again -- dtk_batch_result_host saw it outgrow its arrays -- is rendered again behind it)
-    if (b->sr_on && (rc = b->sp_on ? render_slice_pos(b) : render_slice(b)) != DTK_OK) return rc;
-    if (b->so_on && (rc = slice_offsets(b)) != DTK_OK) return rc;
+    // (what a slice of a stream computes from the list; behind a list packed again -- dtk_batch_result_host saw it
+    //  outgrow its arrays -- it is computed again)
+    if ((rc = slice_outputs(b)) != DTK_OK) return rc;
   }
   const uint32_t blk_want = tot[0] ? want & kBlkFields : 0u;  // (no token: nothing to pack, empty arrays)
   if (blk_want && (rc = pack_blocked(b, blk_want, tot[0])) != DTK_OK) return rc;

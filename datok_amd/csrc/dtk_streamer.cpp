@@ -23,28 +23,29 @@ struct dtk_stream {
   uint64_t S = 0;
   uint32_t depth = 0;
   uint32_t fields = kForced | DTK_R_TOK_BYTE;
-  bool render = false;        // dtk_stream_set_render: every slice's writer bytes come with it
-  uint32_t render_bits = 0;
-  // dtk_stream_set_position_render: the same in a mode with TOKEN_POS / SENTENCE_POS.  The writer's state is chained
-  // on the device: slice k reads carry slot k % (depth + 1) and writes the next one -- never the slot it read, and a
-  // slot is written again only by slice k + depth, which takes the batch that slice k has left by then.
-  bool pos_render = false;
-  uint32_t pos_bits = 0;      // all five writer bits
+  // Every slice's writer bytes come with it: dtk_stream_set_render (kPlainBytes; bits: TOKENS | SENTENCES) or
+  // dtk_stream_set_position_render (kPosBytes; bits: all five writer bits), one renderer at a time.
+  SliceRequest::Bytes bytes = SliceRequest::kNoBytes;
+  uint32_t bits = 0;
+  // dtk_stream_set_offsets: the writer's rune offsets and sentence list as arrays, beside set_render's bytes or alone;
+  // exclusive with position rendering.
+  bool offs = false;
+  uint32_t offs_form = DTK_SO_PLAIN;
+  // Position rendering and offset delivery follow the writer's state, which is chained on the device: slice k reads
+  // carry slot k % (depth + 1) and writes the next one -- never the slot it read, and a slot is written again only by
+  // slice k + depth, which takes the batch that slice k has left by then.
   DevArray<DtkPosCarry> d_carry;  // depth + 1
   // The held prefixes (dtk_stream_emit): the integers of the text that is open at the last cut, as the bytes of its
   // TOKEN_POS / SENTENCE_POS line so far.  They grow with the length of a text, as the reference's pos[] / sent[] do.
   std::string held_pos, held_sent;
-  // dtk_stream_set_offsets: the writer's rune offsets and sentence list as arrays.  The same chain with slots of its
-  // own, beside set_render's bytes or alone; exclusive with position rendering.
-  bool offs = false;
-  uint32_t offs_form = DTK_SO_PLAIN;
-  DevArray<DtkPosCarry> d_ocarry;  // depth + 1
-  bool cur_offs_set = false;       // inside slice_fn: cur_offs is the slice being delivered
-  SoView cur_offs{};
-  // the slice being delivered, inside slice_fn
-  const uint8_t *cur_out = nullptr;
-  const DtkPosTrailer *cur = nullptr;
-  bool cur_emitted = false;
+  // the slice being delivered: valid inside slice_fn only
+  struct Delivery {
+    const uint8_t *out = nullptr;         // position rendering: the bytes, the trailer behind them (null: none),
+    const DtkPosTrailer *pos = nullptr;   // and whether dtk_stream_emit has written them
+    bool emitted = false;
+    bool offs_set = false;                // offset delivery: offs is this slice's
+    SoView offs{};
+  } cur;
   Stream s_up, s_run, s_down;
   std::vector<dtk_batch *> slots;
   std::vector<std::unique_ptr<PinBuf>> buf;  // depth x (S + T)
@@ -64,7 +65,9 @@ extern "C" int dtk_stream_create(uint64_t slice_bytes, uint32_t depth, dtk_strea
   s->S = slice_bytes;
   s->depth = depth;
   int rc;
-  if ((rc = s->s_up.create()) || (rc = s->s_run.create()) || (rc = s->s_down.create())) return rc;
+  if ((rc = s->s_up.create()) || (rc = s->s_run.create()) || (rc = s->s_down.create()) ||
+      (rc = s->d_carry.fit((uint64_t)depth + 1u, (uint64_t)depth + 1u)))
+    return rc;
   for (uint32_t i = 0; i < depth; i++) {
     dtk_batch *b = nullptr;
     if ((rc = dtk_batch_create(slice_bytes + kTail, 1, &b)) != DTK_OK) return rc;
@@ -111,9 +114,12 @@ extern "C" int dtk_stream_set_result_fields(dtk_stream *s, uint32_t fields) {
 extern "C" int dtk_stream_set_render(dtk_stream *s, int on, uint32_t bits) {
   // (the position modes keep writer state across cuts: the host writer's, through the replay)
   if (!s || (bits & ~(uint32_t)(DTK_TOKENS | DTK_SENTENCES | DTK_NEWLINE_AFTER_EOT))) return DTK_E_ARG;
-  s->render = on != 0;
-  s->render_bits = bits & (uint32_t)(DTK_TOKENS | DTK_SENTENCES);
-  if (on) s->pos_render = false;  // (one renderer at a time)
+  if (on) {  // (position rendering, if it was on, is off)
+    s->bytes = SliceRequest::kPlainBytes;
+    s->bits = bits & (uint32_t)(DTK_TOKENS | DTK_SENTENCES);
+  } else if (s->bytes == SliceRequest::kPlainBytes) {
+    s->bytes = SliceRequest::kNoBytes;
+  }
   return DTK_OK;
 }
 
@@ -122,51 +128,48 @@ extern "C" int dtk_stream_set_position_render(dtk_stream *s, int on, uint32_t bi
   if (!s || (bits & ~all)) return DTK_E_ARG;
   if (on && !(bits & (uint32_t)(DTK_TOKEN_POS | DTK_SENTENCE_POS))) return DTK_E_ARG;  // those modes are dtk_stream_set_render's
   if (on && s->offs) return DTK_E_ARG;  // (the offsets as digits or as arrays, not both)
-  if (on) {
-    const int rc = s->d_carry.fit((uint64_t)s->depth + 1u, (uint64_t)s->depth + 1u);
-    if (rc != DTK_OK) return rc;
-    s->render = false;
+  if (on) {  // (plain rendering, if it was on, is off)
+    s->bytes = SliceRequest::kPosBytes;
+    s->bits = bits;
+  } else if (s->bytes == SliceRequest::kPosBytes) {
+    s->bytes = SliceRequest::kNoBytes;
   }
-  s->pos_render = on != 0;
-  s->pos_bits = bits;
   return DTK_OK;
 }
 
 extern "C" int dtk_stream_set_offsets(dtk_stream *s, int on, uint32_t form) {
   if (!s) return DTK_E_ARG;
-  if (on && ((form != DTK_SO_PLAIN && form != DTK_SO_BLOCKED) || s->pos_render)) return DTK_E_ARG;
-  if (on) {
-    const int rc = s->d_ocarry.fit((uint64_t)s->depth + 1u, (uint64_t)s->depth + 1u);
-    if (rc != DTK_OK) return rc;
-    s->offs_form = form;
-  }
+  if (on && ((form != DTK_SO_PLAIN && form != DTK_SO_BLOCKED) || s->bytes == SliceRequest::kPosBytes)) return DTK_E_ARG;
+  if (on) s->offs_form = form;
   s->offs = on != 0;
   return DTK_OK;
 }
 
+static dtk_stream_carry carry_of(const DtkPosCarry &c) {
+  return dtk_stream_carry{c.posC, c.sentB, c.init, c.pos_nonempty, c.sent_nonempty};
+}
+
 extern "C" int dtk_stream_offsets(dtk_stream *s, dtk_stream_offs *o) {
   if (!s || !o) return DTK_E_ARG;
-  if (!s->cur_offs_set) return DTK_E_STATE;
-  const SoView &v = s->cur_offs;
-  auto carry = [](const DtkPosCarry &c) { return dtk_stream_carry{c.posC, c.sentB, c.init, c.pos_nonempty, c.sent_nonempty}; };
+  if (!s->cur.offs_set) return DTK_E_STATE;
+  const SoView &v = s->cur.offs;
   static_assert(sizeof(dtk_off_block64) == sizeof(DtkOffBlock64) && sizeof(dtk_off_block64) == 24, "the kernels' block head is the header's");
   o->n_tok = v.t->n_tok; o->n_sent = v.t->n_sent; o->n_text = v.t->n_text;
   o->tok_rstart = v.rstart; o->tok_rend = v.rend;
   o->tok_rblk = v.words; o->tok_rblk_head = reinterpret_cast<const dtk_off_block64 *>(v.heads);
   o->sent = v.sent; o->text_tok_end = v.ttok; o->text_sent_end = v.tsent;
-  o->carry_in = carry(v.t->carry_in); o->carry_out = carry(v.t->carry_out);
+  o->carry_in = carry_of(v.t->carry_in); o->carry_out = carry_of(v.t->carry_out);
   return DTK_OK;
 }
 
 extern "C" int dtk_stream_positions(dtk_stream *s, dtk_stream_pos *o) {
   if (!s || !o) return DTK_E_ARG;
-  if (!s->cur) return DTK_E_STATE;
-  const DtkPosTrailer &t = *s->cur;
-  auto carry = [](const DtkPosCarry &c) { return dtk_stream_carry{c.posC, c.sentB, c.init, c.pos_nonempty, c.sent_nonempty}; };
+  if (!s->cur.pos) return DTK_E_STATE;
+  const DtkPosTrailer &t = *s->cur.pos;
   o->splice_pos = t.splice_pos; o->splice_sent = t.splice_sent;
-  o->open_pos = s->cur_out + t.out_len; o->open_pos_len = t.open_pos_len;
+  o->open_pos = s->cur.out + t.out_len; o->open_pos_len = t.open_pos_len;
   o->open_sent = o->open_pos + t.open_pos_len; o->open_sent_len = t.open_sent_len;
-  o->carry_in = carry(t.carry_in); o->carry_out = carry(t.carry_out);
+  o->carry_in = carry_of(t.carry_in); o->carry_out = carry_of(t.carry_out);
   return DTK_OK;
 }
 
@@ -174,9 +177,9 @@ extern "C" int dtk_stream_positions(dtk_stream *s, dtk_stream_pos *o) {
 // the open fragments join what is held.
 extern "C" int dtk_stream_emit(dtk_stream *s, dtk_write_fn w, void *user) {
   if (!s || !w) return DTK_E_ARG;
-  if (!s->cur || s->cur_emitted) return DTK_E_STATE;
-  const DtkPosTrailer &t = *s->cur;
-  s->cur_emitted = true;
+  if (!s->cur.pos || s->cur.emitted) return DTK_E_STATE;
+  const DtkPosTrailer &t = *s->cur.pos;
+  s->cur.emitted = true;
   uint64_t at = 0;
   int rc;
   std::string *held[2] = {&s->held_pos, &s->held_sent};
@@ -184,13 +187,13 @@ extern "C" int dtk_stream_emit(dtk_stream *s, dtk_write_fn w, void *user) {
   for (int i = 0; i < 2; i++) {
     if (splice[i] == UINT64_MAX) continue;
     if (splice[i] < at || splice[i] > t.out_len) return DTK_E_STATE;
-    if (splice[i] > at && (rc = w(user, s->cur_out + at, (size_t)(splice[i] - at))) != DTK_OK) return rc;
+    if (splice[i] > at && (rc = w(user, s->cur.out + at, (size_t)(splice[i] - at))) != DTK_OK) return rc;
     at = splice[i];
     if (!held[i]->empty() && (rc = w(user, reinterpret_cast<const uint8_t *>(held[i]->data()), held[i]->size())) != DTK_OK) return rc;
     held[i]->clear();
   }
-  if (t.out_len > at && (rc = w(user, s->cur_out + at, (size_t)(t.out_len - at))) != DTK_OK) return rc;
-  const char *open = reinterpret_cast<const char *>(s->cur_out + t.out_len);
+  if (t.out_len > at && (rc = w(user, s->cur.out + at, (size_t)(t.out_len - at))) != DTK_OK) return rc;
+  const char *open = reinterpret_cast<const char *>(s->cur.out + t.out_len);
   s->held_pos.append(open, (size_t)t.open_pos_len);
   s->held_sent.append(open + t.open_pos_len, (size_t)t.open_sent_len);
   return DTK_OK;
@@ -242,6 +245,7 @@ struct Run {
   uint64_t te_from = 0, posc0 = 0;
 
   uint8_t *bytes(uint32_t slot) { return s->buf[slot]->as<uint8_t>(); }
+  bool pos_render() const { return s->bytes == SliceRequest::kPosBytes; }
 
   // window k into its slot: the tail of window k - 1 (null: the stream's beginning), then fresh bytes.  Returns the
   // fresh bytes read.
@@ -286,16 +290,20 @@ struct Run {
       have_carry = true;
     }
     const uint32_t cut = x.ended ? len[x.slot] : x.c.cut;
-    batch_set_render(b, s->render || s->pos_render, s->pos_render ? s->pos_bits : s->render_bits, x.first, cut, x.ended);
-    if (s->pos_render) {
-      uint32_t digits = 2;  // ("-1")
-      for (uint64_t v = x.base + cut - te_from + posc0; v >= 10u; v /= 10u) digits++;
-      const uint64_t slots = (uint64_t)s->depth + 1u;
-      batch_set_pos_render(b, true, is_matrix, digits, s->d_carry + x.k % slots, s->d_carry + (x.k + 1u) % slots);
+    SliceRequest q;
+    q.first = x.first; q.cut = cut; q.last = x.ended;
+    q.bytes = s->bytes; q.bits = s->bits;
+    q.offs = s->offs; q.form = s->offs_form;
+    q.is_matrix = is_matrix; q.nl = nl;
+    if (pos_render()) {
+      q.digits = 2;  // ("-1")
+      for (uint64_t v = x.base + cut - te_from + posc0; v >= 10u; v /= 10u) q.digits++;
     }
-    const uint64_t oslots = (uint64_t)s->depth + 1u;
-    batch_set_offsets(b, s->offs, s->offs_form, is_matrix, nl, s->offs ? s->d_ocarry + x.k % oslots : nullptr,
-                      s->offs ? s->d_ocarry + (x.k + 1u) % oslots : nullptr);
+    if (pos_render() || s->offs) {
+      const uint64_t slots = (uint64_t)s->depth + 1u, slot = x.k % slots;
+      q.carry_in = s->d_carry + slot; q.carry_out = s->d_carry + (slot + 1u) % slots;
+    }
+    batch_set_slice_request(b, q);
     return dtk_batch_download_begin(b);
   }
   // hands the slice over (its successor may be walking meanwhile)
@@ -322,19 +330,17 @@ struct Run {
     const uint64_t n_teot = nx - ((x.ended && (sl.view.doc_tail[0] & DTK_TAIL_E)) ? 1u : 0u);
     has_tok = n_teot ? nt > sl.view.text_tok_end[n_teot - 1] : (has_tok || nt > 0);
     if (n_teot || nx) te_from = x.base + x.first;
-    if (s->render && (rc = batch_render_out(b, &sl.out, &sl.out_len)) != DTK_OK) return rc;
-    if (s->pos_render) {
-      if ((rc = batch_pos_out(b, &s->cur_out, &s->cur)) != DTK_OK) { s->cur = nullptr; return rc; }
-      sl.out = s->cur_out; sl.out_len = s->cur->out_len;
-      s->cur_emitted = false;
+    if (s->bytes == SliceRequest::kPlainBytes && (rc = batch_render_out(b, &sl.out, &sl.out_len)) != DTK_OK) return rc;
+    if (pos_render()) {
+      if ((rc = batch_pos_out(b, &s->cur.out, &s->cur.pos)) != DTK_OK) return rc;  // (cur is as it was: empty)
+      sl.out = s->cur.out; sl.out_len = s->cur.pos->out_len;
     }
     if (s->offs) {
-      if ((rc = batch_offs_out(b, &s->cur_offs)) != DTK_OK) return rc;
-      s->cur_offs_set = true;
+      if ((rc = batch_offs_out(b, &s->cur.offs)) != DTK_OK) return rc;
+      s->cur.offs_set = true;
     }
     rc = slice_fn ? slice_fn(slice_user, &sl) : DTK_OK;
-    s->cur = nullptr;
-    s->cur_offs_set = false;
+    s->cur = {};
     return rc;
   }
 };
@@ -343,7 +349,7 @@ struct Run {
 extern "C" int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn read_fn, void *read_user, uint32_t flags,
                               dtk_stream_slice_fn slice_fn, void *slice_user, uint32_t *status) {
   if (!s || !m || !read_fn || (flags & ~(uint32_t)31u)) return DTK_E_ARG;
-  if (s->pos_render && ((flags ^ s->pos_bits) & DTK_NEWLINE_AFTER_EOT)) return DTK_E_ARG;  // the rule is part of the rendering
+  if (s->bytes == SliceRequest::kPosBytes && ((flags ^ s->bits) & DTK_NEWLINE_AFTER_EOT)) return DTK_E_ARG;  // the rule is part of the rendering
   if (status) *status = 0;
   const uint32_t depth = s->depth;
   Run r;
@@ -351,18 +357,13 @@ extern "C" int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn rea
   r.len.assign(depth, 0);
   r.touched.assign(depth, 0);
   s->held_pos.clear(); s->held_sent.clear();
-  s->cur = nullptr;
-  s->cur_offs_set = false;
+  s->cur = {};
   r.is_matrix = std::strcmp(dtk_model_type(m), "MATOK") == 0;
   r.nl = (flags & DTK_NEWLINE_AFTER_EOT) != 0;
-  if (s->offs) {  // a new writer in slot 0 of the offsets' chain
+  if (r.pos_render() || s->offs) {
+    // a new writer: {posC 0, sentB, init} (token_writer.go:38-42) in slot 0 of the chain
     const DtkPosCarry c0{g_dbg.sp_posc0, 1u, 1u, 0u, 0u};
-    HIP_TRY(hipMemcpy(s->d_ocarry.p, &c0, sizeof(c0), hipMemcpyHostToDevice));
-  }
-  if (s->pos_render) {
-    // a new writer: {posC 0, sentB, init} (token_writer.go:38-42) in slot 0
-    const DtkPosCarry c0{g_dbg.sp_posc0, 1u, 1u, 0u, 0u};
-    r.posc0 = (uint64_t)(c0.posC < 0 ? -c0.posC : c0.posC);
+    if (r.pos_render()) r.posc0 = (uint64_t)(c0.posC < 0 ? -c0.posC : c0.posC);
     HIP_TRY(hipMemcpy(s->d_carry.p, &c0, sizeof(c0), hipMemcpyHostToDevice));
   }
   // (the writer's rune offsets are the host's: the compaction writes the byte offsets only)
@@ -378,7 +379,7 @@ extern "C" int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn rea
     // beside the predecessor's walk -- except with position rendering, whose download (the capacity bound of the
     // position lines: some 4 bytes per input byte) is a slice's longest leg: there the cut comes first, and the read
     // runs beside that download (profiles/stream_positions.txt).
-    const bool cut_first = s->pos_render;
+    const bool cut_first = r.pos_render();
     auto cut_prev = [&]() -> bool {  // false: the loop ends here
       if ((rc = r.take_cut(prev)) != DTK_OK) return false;
       if (prev.ended) { rc = r.deliver(prev); return false; }
@@ -409,11 +410,8 @@ extern "C" int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn rea
     if (r.touched[q]) {
       (void)dtk_batch_sync(s->slots[q]);
       (void)batch_set_slice(s->slots[q], 0u, nullptr);
-      batch_set_render(s->slots[q], false, 0u, 0u, 0u, false);
-      batch_set_offsets(s->slots[q], false, 0u, false, false, nullptr, nullptr);
+      batch_set_slice_request(s->slots[q], SliceRequest{});
     }
-  s->cur = nullptr;
-  s->cur_offs_set = false;
   if (status) *status = r.status;
   return rc;
 }

@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void k_so_tok_place(OArgs O) {
   __shared__ uint32_t wave_f[SP_WAVES];
   __shared__ uint64_t wave_tot[SP_WAVES];
   const Args &A = O.front;
-  const uint32_t E = sp_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) return;
   const uint32_t N = (uint32_t)A.n_tok;
   const uint32_t k = blockIdx.x * SP_THREADS + threadIdx.x;
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void k_so_tok_place(OArgs O) {
   (void)sp_tok_positions(A, k, wave_s, wave_f, meta);
   const uint64_t n = k < N ? (uint64_t)(meta >> 31) + (meta & 0x3FFFFFFFu) : 0u;
   uint64_t tot;
-  const uint64_t e = sp_block_excl(n, wave_tot, tot);
+  const uint64_t e = block_excl_scan64(n, wave_tot, tot);
   if (k < N) O.sent_in[k] = (uint32_t)e;
   if (threadIdx.x == 0u) O.sent_base[blockIdx.x] = tot;
 }
@@ -61,13 +61,13 @@ __global__ __launch_bounds__(256) void k_so_tok_place(OArgs O) {
 __global__ __launch_bounds__(256) void k_so_scan(OArgs O) {
   __shared__ uint64_t wave_tot[SP_WAVES];
   const Args &A = O.front;
-  const uint32_t E = sp_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) {
     if (threadIdx.x == 0u) O.trailer->n_tok = SP_NONE;
     return;
   }
   const uint32_t N = (uint32_t)A.n_tok;
-  const uint64_t tok_ints = sp_scan_row(O.sent_base, A.tok_tiles, wave_tot);
+  const uint64_t tok_ints = scan_row64(O.sent_base, A.tok_tiles, wave_tot);
   __syncthreads();  // (thread 0 reads the scan of another thread's tile)
   if (threadIdx.x != 0u) return;
   const DtkPosCarry c = *A.carry_in;
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void k_so_scan(OArgs O) {
   A.hdr->tot[2] = tok_ints;
   const uint64_t n_sent = (uint64_t)A.hdr->head_n + tok_ints;
   // the text that is open behind the last TextEnd entry: its first token, its ints
-  const uint32_t tf = n_te ? sp_lower(A.tok_bend, N, A.evl_pos[A.te_idx[n_te - 1u]]) : 0u;
+  const uint32_t tf = n_te ? lower_bound32(A.tok_bend, N, A.evl_pos[A.te_idx[n_te - 1u]]) : 0u;
   const uint64_t open_ints = n_sent - (n_te ? so_sent_at(O, tf) : 0u);
   DtkOffsTrailer T{};
   T.n_tok = N;
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void k_so_scan(OArgs O) {
 // ---------------------------------------------------------------- sent[]
 __global__ __launch_bounds__(256) void k_so_sent(OArgs O) {
   const Args &A = O.front;
-  const uint32_t E = sp_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) return;
   const uint32_t N = (uint32_t)A.n_tok;
   const uint32_t k = blockIdx.x * SP_THREADS + threadIdx.x;
@@ -123,12 +123,12 @@ __global__ __launch_bounds__(256) void k_so_sent(OArgs O) {
 // ---------------------------------------------------------------- the text rows
 __global__ __launch_bounds__(256) void k_so_text(OArgs O) {
   const Args &A = O.front;
-  const uint32_t E = sp_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) return;
   const uint32_t N = (uint32_t)A.n_tok;
   const uint32_t g = blockIdx.x * SP_THREADS + threadIdx.x;
   if (g >= A.hdr->n_te || g >= O.text_cap) return;
-  const uint32_t tl = sp_lower(A.tok_bend, N, A.evl_pos[A.te_idx[g]]);  // (the token on this cursor begins the next text)
+  const uint32_t tl = lower_bound32(A.tok_bend, N, A.evl_pos[A.te_idx[g]]);  // (the token on this cursor begins the next text)
   O.text_tok_end[g] = tl;
   O.text_sent_end[g] = (uint32_t)so_sent_at(O, tl);
 }
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256) void k_so_text(OArgs O) {
 // token per lane; lanes behind the last token take part in nothing.
 __global__ __launch_bounds__(256) void k_so_pack64(OArgs O) {
   const Args &A = O.front;
-  const uint32_t E = sp_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) return;
   const uint64_t N = A.n_tok;
   const uint32_t lane = lane_id();
@@ -164,8 +164,6 @@ __global__ __launch_bounds__(256) void k_so_pack64(OArgs O) {
     if (hi0 - lo0 > (int64_t)O.span || hi1 - lo1 > (int64_t)O.span) O.trailer->blk_fail = 1u;  // (behind k_so_scan's store of the block)
   }
 }
-
-inline uint64_t words32(uint64_t n) { return (n + 1u) / 2u; }
 
 }  // namespace
 

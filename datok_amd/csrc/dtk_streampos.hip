@@ -34,11 +34,6 @@
 
 namespace {
 
-__device__ __forceinline__ bool sp_invalid(const DtkSym &S, uint64_t i) {  // as sr_invalid
-  const uint32_t e = dtk_sym_entry(S, i);
-  return DTK_SYM_WIDTH(e) == 1u && ((e >> DTK_SYM_CLS_SHIFT) & 3u) >= 2u;
-}
-
 // a weight's exclusive scan over the tokens (r: 0 surfaces, 1 position integers, 2 sentence integers), behind scan 2
 __device__ __forceinline__ uint64_t sp_w(const Args &A, uint32_t r, uint32_t k) {
   const uint32_t N = (uint32_t)A.n_tok;
@@ -81,7 +76,7 @@ __global__ __launch_bounds__(256) void k_sp_tok_weights(Args A) {
   __shared__ int64_t wave_s[SP_WAVES];
   __shared__ uint32_t wave_f[SP_WAVES];
   __shared__ uint64_t wave_tot[SP_WAVES];
-  const uint32_t E = sp_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) return;
   const uint32_t N = (uint32_t)A.n_tok;
   const uint32_t k = blockIdx.x * SP_THREADS + threadIdx.x;
@@ -94,7 +89,7 @@ __global__ __launch_bounds__(256) void k_sp_tok_weights(Args A) {
       const uint32_t be = sp_bend(A, k), bs = std::min(A.tok_bstart[k], be);
       w[0] = (uint64_t)(be - bs) + 1u;
       if (INV)
-        for (uint32_t q = bs; q < be; q++) w[0] += sp_invalid(A.sym, q) ? 2u : 0u;
+        for (uint32_t q = bs; q < be; q++) w[0] += sym_invalid_byte(A.sym, q) ? 2u : 0u;
     }
     const uint32_t ds = 1u + dec_len64(rs), de = 1u + dec_len64(re);
     if (A.bits & W_TOKEN_POS) w[1] = ds + de;
@@ -103,7 +98,7 @@ __global__ __launch_bounds__(256) void k_sp_tok_weights(Args A) {
 #pragma unroll
   for (uint32_t r = 0; r < 3u; r++) {
     uint64_t tot;
-    const uint64_t e = sp_block_excl(w[r], wave_tot, tot);
+    const uint64_t e = block_excl_scan64(w[r], wave_tot, tot);
     if (k < N) A.w_in[(uint64_t)r * N + k] = (uint32_t)e;
     if (threadIdx.x == 0u) {
       A.w_base[(uint64_t)r * A.tok_tiles + blockIdx.x] = tot;
@@ -115,7 +110,7 @@ __global__ __launch_bounds__(256) void k_sp_tok_weights(Args A) {
 // ---------------------------------------------------------------- entries: bytes
 __global__ __launch_bounds__(256) void k_sp_ent_weights(Args A) {
   __shared__ uint64_t wave_tot[SP_WAVES];
-  const uint32_t E = sp_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) return;
   const uint32_t N = (uint32_t)A.n_tok;
   const uint32_t j = blockIdx.x * SP_THREADS + threadIdx.x;
@@ -127,8 +122,8 @@ __global__ __launch_bounds__(256) void k_sp_ent_weights(Args A) {
     if (kd & DTK_EVL_K_TEOT) {
       const DtkPosCarry c = *A.carry_in;
       const uint32_t g = (uint32_t)(A.cnt[j] >> 32);
-      const uint32_t tl = sp_lower(A.tok_bend, N, A.evl_pos[j]);  // (the token on this cursor begins the next text)
-      const uint32_t tf = g ? sp_lower(A.tok_bend, N, A.evl_pos[A.te_idx[g - 1u]]) : 0u;
+      const uint32_t tl = lower_bound32(A.tok_bend, N, A.evl_pos[j]);  // (the token on this cursor begins the next text)
+      const uint32_t tf = g ? lower_bound32(A.tok_bend, N, A.evl_pos[A.te_idx[g - 1u]]) : 0u;
       const SpLines L = sp_lines(A, c, g, tf, tl);
       A.seg_pw0[g] = sp_w(A, 1u, tf);
       A.seg_sw0[g] = (int64_t)sp_w(A, 2u, tf) - (g == 0u ? (int64_t)A.hdr->head_w : 0);
@@ -139,13 +134,13 @@ __global__ __launch_bounds__(256) void k_sp_ent_weights(Args A) {
     w = pre + ((kd & DTK_EVL_K_SEPS) ? s : 0u);
   }
   uint64_t total;
-  (void)sp_block_excl(w, wave_tot, total);
+  (void)block_excl_scan64(w, wave_tot, total);
   if (threadIdx.x == 0u) A.ent_base[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(256) void k_sp_ent_offsets(Args A) {
   __shared__ uint64_t wave_tot[SP_WAVES];
-  const uint32_t E = sp_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) return;
   const uint32_t N = (uint32_t)A.n_tok;
   const uint32_t j = blockIdx.x * SP_THREADS + threadIdx.x;
@@ -157,14 +152,14 @@ __global__ __launch_bounds__(256) void k_sp_ent_offsets(Args A) {
     w = A.ent_pre[j] + ((kd & DTK_EVL_K_SEPS) ? s : 0u);
   }
   uint64_t total;
-  const uint64_t x = sp_block_excl(w, wave_tot, total);
+  const uint64_t x = block_excl_scan64(w, wave_tot, total);
   if (j >= E) return;
   const uint64_t at = A.ent_base[blockIdx.x] + x;
   A.ew[j] = at;
   if (kd & DTK_EVL_K_TEOT) {
     const DtkPosCarry c = *A.carry_in;
     const uint32_t g = (uint32_t)(A.cnt[j] >> 32);
-    const uint32_t tl = sp_lower(A.tok_bend, N, A.evl_pos[j]);
+    const uint32_t tl = lower_bound32(A.tok_bend, N, A.evl_pos[j]);
     const uint64_t line = sp_w(A, 0u, tl) + at + ((kd & DTK_EVL_K_SEOT) ? s : 0u);
     const uint64_t pb = A.seg_sent[g];
     A.seg_pos[g] = line;
@@ -179,7 +174,7 @@ __global__ __launch_bounds__(256) void k_sp_ent_offsets(Args A) {
 // ---------------------------------------------------------------- the scanning block
 __global__ __launch_bounds__(256) void k_sp_scan(Args A, uint32_t stage) {
   __shared__ uint64_t wave_tot[SP_WAVES];
-  const uint32_t E = sp_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) {
     if (stage == 2u && threadIdx.x == 0u) A.trailer->out_len = SP_NONE;
     return;
@@ -188,13 +183,13 @@ __global__ __launch_bounds__(256) void k_sp_scan(Args A, uint32_t stage) {
   const uint32_t s = (A.bits & W_SENTENCES) ? 1u : 0u;
   if (stage == 2u) {  // ---- the tokens' weights
     uint64_t tot[3];
-    for (uint32_t r = 0; r < 3u; r++) tot[r] = sp_scan_row(A.w_base + (uint64_t)r * A.tok_tiles, A.tok_tiles, wave_tot);
+    for (uint32_t r = 0; r < 3u; r++) tot[r] = scan_row64(A.w_base + (uint64_t)r * A.tok_tiles, A.tok_tiles, wave_tot);
     if (threadIdx.x == 0u)
       for (uint32_t r = 0; r < 3u; r++) A.hdr->tot[r] = tot[r];
     return;
   }
   // ---- stage 3: the entries' bytes, the lengths, the last text, the carry
-  const uint64_t ent_tot = sp_scan_row(A.ent_base, A.ent_tiles, wave_tot);
+  const uint64_t ent_tot = scan_row64(A.ent_base, A.ent_tiles, wave_tot);
   if (threadIdx.x != 0u) return;
   const DtkPosCarry c = *A.carry_in;
   const uint32_t tail = A.with_tail ? (A.doc_tail[0] & 3u) : 0u;
@@ -202,7 +197,7 @@ __global__ __launch_bounds__(256) void k_sp_scan(Args A, uint32_t stage) {
   A.ew[E] = ent_tot;
   A.hdr->ent_tot = ent_tot;
   const uint32_t g = n_te;
-  const uint32_t tf = g ? sp_lower(A.tok_bend, N, A.evl_pos[A.te_idx[g - 1u]]) : 0u;
+  const uint32_t tf = g ? lower_bound32(A.tok_bend, N, A.evl_pos[A.te_idx[g - 1u]]) : 0u;
   const SpLines L = sp_lines(A, c, g, tf, N);
   A.seg_pw0[g] = sp_w(A, 1u, tf);
   A.seg_sw0[g] = (int64_t)sp_w(A, 2u, tf) - (g == 0u ? (int64_t)A.hdr->head_w : 0);
@@ -235,7 +230,7 @@ __global__ __launch_bounds__(256) void k_sp_scan(Args A, uint32_t stage) {
 // ---------------------------------------------------------------- surfaces and integers
 template <bool INV>
 __global__ __launch_bounds__(256) void k_sp_write(Args A) {
-  const uint32_t E = sp_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) return;
   const uint32_t N = (uint32_t)A.n_tok;
   const uint32_t k = blockIdx.x * SP_THREADS + threadIdx.x;
@@ -252,12 +247,12 @@ __global__ __launch_bounds__(256) void k_sp_write(Args A) {
   const uint32_t ds = 1u + dec_len64(rs), de = 1u + dec_len64(re);
   if (A.bits & W_TOKENS) {
     const uint32_t be = sp_bend(A, k), bs = std::min(A.tok_bstart[k], be);
-    const uint32_t lbk = sp_lower(A.evl_pos, E, be);
+    const uint32_t lbk = lower_bound32(A.evl_pos, E, be);
     uint64_t o = sp_w(A, 0u, k) + A.ew[lbk];
     if (lbk < E && A.evl_pos[lbk] == be) o += A.ent_pre[lbk];
     const uint8_t *__restrict__ text = A.text;
     for (uint32_t q = bs; q < be; q++) {
-      if (INV && sp_invalid(A.sym, q)) {
+      if (INV && sym_invalid_byte(A.sym, q)) {
         if (o + 3u <= A.cap) { out[o] = 0xEF; out[o + 1] = 0xBF; out[o + 2] = 0xBD; }
         o += 3u;
       } else {
@@ -281,8 +276,6 @@ __global__ __launch_bounds__(256) void k_sp_write(Args A) {
     for (uint32_t i = 0; i < n; i++) { sp_put(A, A.seg_sent[g], rel, fresh, re); rel += de; }
   }
 }
-
-inline uint64_t words32(uint64_t n) { return (n + 1u) / 2u; }
 
 }  // namespace
 

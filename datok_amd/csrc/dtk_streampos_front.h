@@ -21,40 +21,7 @@ constexpr uint64_t SP_NONE = ~0ull;
 
 typedef DtkStreamPosArgs Args;
 
-__device__ __forceinline__ uint32_t sp_entries(const Args &A) {
-  const uint32_t n = *A.evl_count;
-  return n > A.evl_cap ? 0xFFFFFFFFu : n;
-}
-
-// first i in [0, n) with a[i] >= x, else n
-__device__ __forceinline__ uint32_t sp_lower(const uint32_t *__restrict__ a, uint32_t n, uint32_t x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < x) lo = mid + 1u; else hi = mid;
-  }
-  return lo;
-}
-
 __device__ __forceinline__ uint32_t sp_bend(const Args &A, uint32_t k) { return std::min(A.tok_bend[k], A.text_len); }
-
-// exclusive prefix sum of a 64-bit value over the block's 256 threads (as sr_block_excl of dtk_streamrender.hip)
-__device__ __forceinline__ uint64_t sp_block_excl(uint64_t v, uint64_t *wave_tot, uint64_t &total) {
-  const uint64_t inc = wave_incl_scan64(v);
-  const uint32_t wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane_id() == WAVE - 1u) wave_tot[wave] = inc;
-  __syncthreads();
-  uint64_t before = 0;
-  total = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < SP_WAVES; k++) {
-    const uint64_t t = wave_tot[k];
-    before += k < wave ? t : 0u;
-    total += t;
-  }
-  return before + inc - v;
-}
 
 // a sum that starts again at every element with f set: (a then b) = (b.f ? b.s : a.s + b.s, a.f | b.f)
 struct Seg { int64_t s; uint32_t f; };
@@ -104,7 +71,7 @@ __device__ __forceinline__ uint32_t sp_sent_calls(const Args &A, uint32_t E, uin
   bool atb = false;
   if (next < N) {
     const uint32_t bn = sp_bend(A, next);
-    b = sp_lower(A.evl_pos, E, bn);
+    b = lower_bound32(A.evl_pos, E, bn);
     atb = b < E && A.evl_pos[b] == bn;
   }
   const uint32_t c0 = (uint32_t)(A.cnt[ap] >> 32);
@@ -121,7 +88,7 @@ __device__ __forceinline__ uint32_t sp_sent_calls(const Args &A, uint32_t E, uin
 // (second == 0: tile sums only; k_sp_front_scan 0 turns them into what lies in front of a tile)
 __global__ __launch_bounds__(256) void k_sp_ent_count(Args A, uint32_t second) {
   __shared__ uint64_t wave_tot[SP_WAVES];
-  const uint32_t E = sp_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) return;
   const uint32_t j = blockIdx.x * SP_THREADS + threadIdx.x;
   uint64_t v = 0;
@@ -130,7 +97,7 @@ __global__ __launch_bounds__(256) void k_sp_ent_count(Args A, uint32_t second) {
     v = (uint64_t)(((kd & DTK_EVL_K_SEOT) ? 1u : 0u) + ((kd & DTK_EVL_K_SEPS) ? 1u : 0u)) | ((kd & DTK_EVL_K_TEOT) ? 1ull << 32 : 0ull);
   }
   uint64_t total;
-  const uint64_t x = sp_block_excl(v, wave_tot, total);
+  const uint64_t x = block_excl_scan64(v, wave_tot, total);
   if (second && j < E) A.cnt[j] = A.ent_base[blockIdx.x] + x;
   if (second && j < E && (v >> 32)) A.te_idx[(uint32_t)((A.ent_base[blockIdx.x] + x) >> 32)] = j;
   if (!second && threadIdx.x == 0u) A.ent_base[blockIdx.x] = total;
@@ -141,7 +108,7 @@ template <bool INV>
 __global__ __launch_bounds__(256) void k_sp_tok_runes(Args A) {
   __shared__ int64_t wave_s[SP_WAVES];
   __shared__ uint32_t wave_f[SP_WAVES];
-  const uint32_t E = sp_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) return;
   const uint32_t N = (uint32_t)A.n_tok;
   const uint32_t k = blockIdx.x * SP_THREADS + threadIdx.x;
@@ -149,13 +116,13 @@ __global__ __launch_bounds__(256) void k_sp_tok_runes(Args A) {
   if (k < N) {
     const DtkPosCarry c = *A.carry_in;
     const uint32_t be = sp_bend(A, k), bs = std::min(A.tok_bstart[k], be);
-    const uint32_t lbk = sp_lower(A.evl_pos, E, be);
+    const uint32_t lbk = lower_bound32(A.evl_pos, E, be);
     const uint32_t kd = (lbk < E && A.evl_pos[lbk] == be) ? A.evl_kind[lbk] : 0u;  // the entry on the token's cursor
     const uint32_t te_k = (uint32_t)(A.cnt[lbk] >> 32) + ((kd & DTK_EVL_K_TEOT) ? 1u : 0u);
     uint32_t te_p = 0, between, bp = A.first;
     if (k) {
       bp = sp_bend(A, k - 1u);
-      const uint32_t lbp = sp_lower(A.evl_pos, E, bp);
+      const uint32_t lbp = lower_bound32(A.evl_pos, E, bp);
       const uint32_t kdp = (lbp < E && A.evl_pos[lbp] == bp) ? A.evl_kind[lbp] : 0u;
       te_p = (uint32_t)(A.cnt[lbp] >> 32) + ((kdp & DTK_EVL_K_TEOT) ? 1u : 0u);
       // (an entry on the predecessor's cursor lies between the two with its SEPS only)
@@ -209,29 +176,15 @@ __device__ __forceinline__ int64_t sp_tok_positions(const Args &A, uint32_t k, i
 }
 
 // ---------------------------------------------------------------- the scanning block
-// exclusive scan of base[0 .. n) in place; returns the sum
-__device__ __forceinline__ uint64_t sp_scan_row(uint64_t *base, uint32_t n, uint64_t *wave_tot) {
-  uint64_t carry = 0;
-  for (uint32_t i0 = 0; i0 < n; i0 += SP_THREADS) {  // (block-uniform trip count)
-    const uint32_t i = i0 + threadIdx.x;
-    const uint64_t v = i < n ? base[i] : 0u;
-    uint64_t total;
-    const uint64_t x = sp_block_excl(v, wave_tot, total);
-    if (i < n) base[i] = carry + x;
-    carry += total;
-  }
-  return carry;
-}
-
 // One block, two stages.  A list longer than its arrays: nothing (the unit's last scanning stage tells the host).
 __global__ __launch_bounds__(256) void k_sp_front_scan(Args A, uint32_t stage) {
   __shared__ uint64_t wave_tot[SP_WAVES];
   __shared__ int64_t wave_s[SP_WAVES];
   __shared__ uint32_t wave_f[SP_WAVES];
-  const uint32_t E = sp_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) return;
   if (stage == 0u) {  // ---- the entries' counts
-    const uint64_t sum = sp_scan_row(A.ent_base, A.ent_tiles, wave_tot);
+    const uint64_t sum = scan_row64(A.ent_base, A.ent_tiles, wave_tot);
     if (threadIdx.x != 0u) return;
     A.cnt[E] = sum;
     DtkPosHdr h{};
@@ -281,7 +234,7 @@ __device__ __forceinline__ DtkPosCarry sp_carry_out(const Args &A, const DtkPosC
     uint32_t after = E + tail;  // calls behind the last token
     if (N) {
       const uint32_t be = sp_bend(A, N - 1u);
-      const uint32_t lbk = sp_lower(A.evl_pos, E, be);
+      const uint32_t lbk = lower_bound32(A.evl_pos, E, be);
       const uint32_t kd = (lbk < E && A.evl_pos[lbk] == be) ? A.evl_kind[lbk] : 0u;
       after = (E - lbk - (kd ? 1u : 0u)) + ((kd & DTK_EVL_K_SEPS) ? 1u : 0u) + tail;
     }

@@ -34,12 +34,6 @@ constexpr uint32_t SR_STAGE = 2048;  // bytes of LDS per wave (a multiple of 16 
 constexpr uint32_t SR_COOP = 64;     // a longer part of a token goes into the stage by the whole wave
 static_assert(SR_STAGE % (16u * WAVE) == 0u, "the fill and the flush take whole rounds of the wave");
 
-// as is_invalid_byte of dtk_render.hip
-__device__ __forceinline__ bool sr_invalid(const DtkSym &S, uint64_t i) {
-  const uint32_t e = dtk_sym_entry(S, i);
-  return DTK_SYM_WIDTH(e) == 1u && ((e >> DTK_SYM_CLS_SHIFT) & 3u) >= 2u;
-}
-
 struct SrTok { uint32_t bs, len; uint64_t w; };
 
 // token k: first byte, surface bytes in the text, bytes in the output (0 behind the last token)
@@ -52,7 +46,7 @@ __device__ __forceinline__ SrTok sr_token(const DtkStreamRenderArgs &A, uint64_t
   t.len = (be > bs && be <= A.text_len) ? be - bs : 0u;  // (start > end: DTK_ST_BAD_OFFSET, out of contract)
   t.w = (uint64_t)t.len + 1u;
   if (INV)
-    for (uint32_t q = 0; q < t.len; q++) t.w += sr_invalid(A.sym, (uint64_t)bs + q) ? 2u : 0u;
+    for (uint32_t q = 0; q < t.len; q++) t.w += sym_invalid_byte(A.sym, (uint64_t)bs + q) ? 2u : 0u;
   return t;
 }
 
@@ -63,34 +57,10 @@ __device__ __forceinline__ void sr_entry(const DtkStreamRenderArgs &A, uint32_t 
   post = (kind & DTK_EVL_K_SEPS) ? s : 0u;
 }
 
-// exclusive prefix sum of a 64-bit value over the block's 256 threads
-__device__ __forceinline__ uint64_t sr_block_excl(uint64_t v, uint64_t *wave_tot, uint64_t &total) {
-  const uint64_t inc = wave_incl_scan64(v);
-  const uint32_t wave = threadIdx.x >> 6;
-  __syncthreads();  // (the previous use of wave_tot has been read)
-  if (lane_id() == WAVE - 1u) wave_tot[wave] = inc;
-  __syncthreads();
-  uint64_t before = 0;
-  total = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < SR_WAVES; k++) {
-    const uint64_t t = wave_tot[k];
-    before += k < wave ? t : 0u;
-    total += t;
-  }
-  return before + inc - v;
-}
-
-// the list's length, or 0xFFFFFFFF if it did not fit its arrays (nothing is rendered then)
-__device__ __forceinline__ uint32_t sr_entries(const DtkStreamRenderArgs &A) {
-  const uint32_t n = *A.evl_count;
-  return n > A.evl_cap ? 0xFFFFFFFFu : n;
-}
-
 template <bool INV>
 __global__ __launch_bounds__(256) void k_sr_sums(DtkStreamRenderArgs A) {
   __shared__ uint64_t wave_tot[SR_WAVES];
-  const uint32_t E = sr_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) return;  // (block-uniform)
   uint64_t w = 0;
   const bool tok = blockIdx.x < A.tok_tiles;
@@ -105,32 +75,19 @@ __global__ __launch_bounds__(256) void k_sr_sums(DtkStreamRenderArgs A) {
     }
   }
   uint64_t total;
-  (void)sr_block_excl(w, wave_tot, total);
+  (void)block_excl_scan64(w, wave_tot, total);
   if (threadIdx.x == 0u) (tok ? A.tok_base[blockIdx.x] : A.ent_base[blockIdx.x - A.tok_tiles]) = total;
 }
 
 __global__ __launch_bounds__(256) void k_sr_scan(DtkStreamRenderArgs A) {
   __shared__ uint64_t wave_tot[SR_WAVES];
-  const uint32_t E = sr_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) {
     if (threadIdx.x == 0u) *A.out_len = ~0ull;
     return;
   }
   uint64_t sum[2];
-  for (uint32_t r = 0; r < 2u; r++) {
-    uint64_t *base = r ? A.ent_base : A.tok_base;
-    const uint32_t n = r ? A.ent_tiles : A.tok_tiles;
-    uint64_t carry = 0;
-    for (uint32_t i0 = 0; i0 < n; i0 += SR_THREADS) {  // (block-uniform trip count)
-      const uint32_t i = i0 + threadIdx.x;
-      const uint64_t v = i < n ? base[i] : 0u;
-      uint64_t total;
-      const uint64_t x = sr_block_excl(v, wave_tot, total);
-      if (i < n) base[i] = carry + x;
-      carry += total;
-    }
-    sum[r] = carry;
-  }
+  for (uint32_t r = 0; r < 2u; r++) sum[r] = scan_row64(r ? A.ent_base : A.tok_base, r ? A.ent_tiles : A.tok_tiles, wave_tot);
   if (threadIdx.x != 0u) return;
   A.ew[E] = sum[1];
   uint64_t tail = 0;
@@ -143,13 +100,13 @@ __global__ __launch_bounds__(256) void k_sr_scan(DtkStreamRenderArgs A) {
 
 __global__ __launch_bounds__(256) void k_sr_entries(DtkStreamRenderArgs A) {
   __shared__ uint64_t wave_tot[SR_WAVES];
-  const uint32_t E = sr_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) return;
   const uint32_t j = blockIdx.x * SR_THREADS + threadIdx.x;
   uint32_t pre = 0, post = 0;
   if (j < E) sr_entry(A, A.evl_kind[j], pre, post);
   uint64_t total;
-  const uint64_t x = sr_block_excl((uint64_t)pre + post, wave_tot, total);
+  const uint64_t x = block_excl_scan64((uint64_t)pre + post, wave_tot, total);
   if (j < E) A.ew[j] = A.ent_base[blockIdx.x] + x;
 }
 
@@ -157,21 +114,17 @@ template <bool INV>
 __global__ __launch_bounds__(256) void k_sr_copy(DtkStreamRenderArgs A) {
   __shared__ uint64_t wave_tot[SR_WAVES];
   __shared__ __attribute__((aligned(16))) uint8_t stage_all[SR_WAVES][SR_STAGE];
-  const uint32_t E = sr_entries(A);
+  const uint32_t E = evl_entries(A);
   if (E == 0xFFFFFFFFu) return;
   const uint64_t k = (uint64_t)blockIdx.x * SR_THREADS + threadIdx.x;
   const SrTok t = sr_token<INV>(A, k);
   uint64_t total;
-  uint64_t off = A.tok_base[blockIdx.x] + sr_block_excl(t.w, wave_tot, total);
+  uint64_t off = A.tok_base[blockIdx.x] + block_excl_scan64(t.w, wave_tot, total);
   const bool valid = k < A.n_tok;
   if (valid) {
     // the entries in front of the token: the first entry at or behind its end
     const uint32_t be = A.tok_bend[k];
-    uint32_t lo = 0, hi = E;
-    while (lo < hi) {
-      const uint32_t mid = lo + ((hi - lo) >> 1);
-      if (A.evl_pos[mid] < be) lo = mid + 1u; else hi = mid;
-    }
+    const uint32_t lo = lower_bound32(A.evl_pos, E, be);
     off += A.ew[lo];
     if (lo < E && A.evl_pos[lo] == be) {
       uint32_t pre, post;
@@ -185,7 +138,7 @@ __global__ __launch_bounds__(256) void k_sr_copy(DtkStreamRenderArgs A) {
     if (!valid) return;
     uint64_t o = off;
     for (uint32_t q = 0; q < t.len; q++) {
-      if (sr_invalid(A.sym, (uint64_t)t.bs + q)) {
+      if (sym_invalid_byte(A.sym, (uint64_t)t.bs + q)) {
         if (o + 3u <= A.cap) { out[o] = 0xEF; out[o + 1] = 0xBF; out[o + 2] = 0xBD; }
         o += 3u;
       } else {

@@ -37,6 +37,7 @@ EXPORTS = [
     "dtk_stream_transduce", "dtk_stream_set_render",
     "dtk_stream_set_position_render", "dtk_stream_positions", "dtk_stream_emit",
     "dtk_stream_set_offsets", "dtk_stream_offsets", "dtk_blk64_start", "dtk_blk64_end",
+    "dtk_batch_sentences_device", "dtk_batch_sentences_host",
 ]
 
 
@@ -68,6 +69,13 @@ class ResultView(C.Structure):
                 ("tok_rblk", C.c_void_p), ("tok_rblk_head", C.c_void_p),
                 ("tok_bblk", C.c_void_p), ("tok_bblk_head", C.c_void_p),
                 ("evl_off", C.c_void_p), ("evl_pos", C.c_void_p), ("evl_kind", C.c_void_p)]
+
+
+class SentenceView(C.Structure):
+    """dtk_sentence_view: a batch's sentences as rows (dtk_batch_sentences_host / _device)."""
+    _fields_ = [("n_sen", C.c_uint64), ("sen_off", C.c_void_p), ("sen_tok_end", C.c_void_p),
+                ("sen_bstart", C.c_void_p), ("sen_bend", C.c_void_p), ("sen_rstart", C.c_void_p), ("sen_rend", C.c_void_p),
+                ("text_sen_end", C.c_void_p)]
 
 
 SLICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)
@@ -178,6 +186,9 @@ def lib():
     L.dtk_batch_result_device.argtypes = [vp, C.POINTER(ResultView)]
     L.dtk_batch_result_host.argtypes = [vp, C.POINTER(ResultView)]
     L.dtk_batch_set_result_fields.argtypes = [vp, u32]
+    L.dtk_batch_sentences_device.argtypes = [vp, C.POINTER(SentenceView)]
+    L.dtk_batch_sentences_host.argtypes = [vp, C.POINTER(SentenceView)]
+    L.dtk_sentences_tile_bits.restype = u32      # (no part of the header: where the kernels' tiles end, for the tests)
     L.dtk_batch_download_begin.argtypes = [vp]
     L.dtk_batch_done.argtypes = [vp]
     L.dtk_batch_set_streams.argtypes = [vp, vp, vp]

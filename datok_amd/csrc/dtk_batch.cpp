@@ -443,6 +443,7 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
   b->dl_begun = false;
   b->blk_pending = b->blk_failed = 0;
   b->evl_pending = false; b->evl_need = 0;
+  b->sen_built = b->sen_home = b->sen_done = false; b->sen_need = 0; b->sen_waited = true;
   if (b->up_pending) {  // the kernels wait for the input's upload on the other stream
     HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_up, 0));
     b->up_pending = false;

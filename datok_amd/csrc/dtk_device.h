@@ -72,6 +72,26 @@ __device__ __forceinline__ int32_t wave_max(int32_t v) {
   return __builtin_amdgcn_readlane(x, WAVE - 1);
 }
 
+// exclusive prefix sum of a 32-bit value over the block's 256 threads (four waves: wave_excl_scan, the wave totals
+// through LDS); wave_tot: 256 / WAVE words of LDS (dtk_evlist.hip, dtk_sentences.hip)
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wave_tot, uint32_t &total) {
+  uint32_t wt;
+  const uint32_t x = wave_excl_scan(v, wt);
+  const uint32_t wave = threadIdx.x >> 6;
+  __syncthreads();  // (the previous use of wave_tot has been read)
+  if (lane_id() == 0u) wave_tot[wave] = wt;
+  __syncthreads();
+  uint32_t before = 0;
+  total = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 256u / WAVE; k++) {
+    const uint32_t t = wave_tot[k];
+    before += k < wave ? t : 0u;
+    total += t;
+  }
+  return before + x;
+}
+
 // ---- what the kernels of a stream slice's outputs share (dtk_streamrender, dtk_streampos, dtk_streamoffs .hip): blocks
 // of 256 threads over tiles of 256 tokens or list entries
 

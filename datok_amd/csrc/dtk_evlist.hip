@@ -64,25 +64,6 @@ __device__ __forceinline__ uint32_t evl_popc(const EvlWords &W) {
   return c;
 }
 
-// exclusive prefix sum over the block's 256 threads (four waves: wave_excl_scan, the wave totals through LDS)
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wave_tot, uint32_t &total) {
-  uint32_t wt;
-  const uint32_t x = wave_excl_scan(v, wt);
-  const uint32_t wave = threadIdx.x >> 6;
-  __syncthreads();  // (the previous use of wave_tot has been read)
-  if (lane_id() == 0u) wave_tot[wave] = wt;
-  __syncthreads();
-  uint32_t before = 0;
-  total = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < EVL_THREADS / WAVE; k++) {
-    const uint32_t t = wave_tot[k];
-    before += k < wave ? t : 0u;
-    total += t;
-  }
-  return before + x;
-}
-
 __device__ __forceinline__ bool evl_wide(const DtkEvListArgs &A) {
   return ((uintptr_t)A.bits & 15u) == 0u && (A.bit_words & 3u) == 0u;
 }

@@ -41,6 +41,8 @@ struct DtkDebug {
   int evl_cap = -1;      // entries the copies of DTK_R_EVENT_LIST are first sized for, in place of n_sent + n_texts (-1: off),
                          // so that ordinary text reaches the second download of a list that outgrew the bound; a stream's offset
                          // delivery also sizes its first copies of sent and the text rows with it (the late copy at delivery)
+  int sen_cap = -1;      // rows the sentence table (DTK_R_SENTENCES) is first sized for, in place of n_sent (-1: off), so that
+                         // ordinary text reaches the second build of a table that outgrew the bound
   long long sp_posc0 = 0; // posC in front of a stream's first slice in a position mode or with offset delivery (dtk_stream_run reads it once, at its
                          // start): integers beyond 2^32 and of 11 digits from a stream of a few hundred bytes
 };
@@ -248,6 +250,21 @@ struct dtk_batch {
   uint64_t evl_copied = 0;         // rows the last enqueued copies of the list hold
   uint64_t evl_need = 0;           // nonzero: this run's list has that many rows, more than the bound (dtk_batch_result_host saw it)
   bool evl_pending = false;        // a list is on its way whose count nobody has looked at yet
+  // DTK_R_SENTENCES / dtk_batch_sentences_*: the sentence table (dtk_sentences.hip), built on the download stream.  One
+  // device block and one page-locked block of the same layout (SenLayout): sen_off | sen_tok_end | sen_bstart | sen_bend |
+  // sen_rstart | sen_rend | text_sen_end | the count word -- one copy brings all of it.  Sized for n_sent rows; the count
+  // word says whether that was enough (sen_need), as with the event list.
+  struct SenLayout { uint64_t rows = 0, texts = 0, tok_end = 0, bstart = 0, bend = 0, rstart = 0, rend = 0, tse = 0, cnt = 0, bytes = 0; } sen;
+  DevArray<uint64_t> d_sen;        // the block (64-bit words)
+  DevArray<uint32_t> d_sen_ws;     // device only: a row's bit | document | first token, and the tiles' two words
+  PinBuf h_sen;
+  Event ev_sen;                    // behind the table's kernels and its last enqueued copy
+  bool sen_built = false;          // the kernels have been enqueued for this run, for sen.rows rows
+  bool sen_home = false;           // ... and the copy of the whole block (else at most the count word's)
+  bool sen_waited = true;          // ev_sen has been waited for: what was enqueued is there
+  bool sen_done = false;           // the count has been looked at and fits (and exact documents are spliced in)
+  uint64_t sen_n = 0;              // rows of the finished table
+  uint64_t sen_need = 0;           // nonzero: this run's table has that many rows, more than the bound
   uint64_t max_doc_bytes = 0;     // of the current input (what decides whether the narrow form exists)
   bool max_doc_valid = false;
   Stream dl_stream;                 // created with the first download, unless the caller lends one (a pipeline's slices share one:
@@ -309,7 +326,7 @@ inline uint64_t blocks_of(uint64_t tokens) { return (tokens + 63) / 64; }  // bl
 inline uint32_t run_fields(const dtk_batch *b) {
   uint32_t f = ~0u;
   if (b->last_flags & DTK_NO_RUNE_OFFSETS) f &= ~(uint32_t)(DTK_R_TOK_RUNE | DTK_R_TOK_RUNE16 | DTK_R_TOK_RUNE_BLK);
-  if (b->last_flags & DTK_NO_BYTE_OFFSETS) f &= ~(uint32_t)(DTK_R_TOK_BYTE | DTK_R_TOK_BYTE_BLK);
+  if (b->last_flags & DTK_NO_BYTE_OFFSETS) f &= ~(uint32_t)(DTK_R_TOK_BYTE | DTK_R_TOK_BYTE_BLK | DTK_R_SENTENCES);
   return f;
 }
 

@@ -428,6 +428,31 @@ struct DtkEvListArgs {
   uint32_t *evl_bit;        // cap, device only: a row's global bit (what k_evl_rows searches)
 };
 
+// DTK_R_SENTENCES (dtk_sentences.hip): the batch's sentences as rows (include/datok_gpu.h, dtk_sentence_view), read off
+// the event bitmaps and gathered from the token rows.  Global bits are below 2^32, as for the event list.
+struct DtkSentencesArgs {
+  const uint32_t *bits;     // event bitmaps of the walk (EVB_KINDS x bit_words words)
+  uint32_t bit_words;
+  uint32_t n_docs;
+  const uint64_t *doc_off;  // n_docs + 1, on the device
+  uint64_t n_bits;          // doc_off[n_docs] + n_docs: bits at or behind it belong to no document
+  uint32_t n_tiles;         // dtk_sentences_tiles(n_bits, bit_words)
+  uint32_t cap;             // rows the arrays below hold; a larger total writes nothing
+  const uint64_t *tok_off, *text_off;         // n_docs + 1 each
+  const uint32_t *tok_bstart, *tok_bend;      // the run's token rows
+  const int32_t *tok_rstart, *tok_rend;       // null: the run wrote no rune offsets, sen_rstart / sen_rend stay unwritten
+  const uint32_t *text_tok_end;               // the run's text rows
+  uint64_t text_cap;                          // rows text_sen_end holds
+  uint32_t *tile_base;      // n_tiles: a tile's summary word, then its first row
+  uint32_t *tile_in;        // n_tiles: f in front of the tile
+  uint32_t *count;          // device word: the total
+  uint32_t *sen_bit, *sen_doc, *sen_first;    // cap each, device only: a row's global bit, document, first token
+  uint64_t *sen_off;        // n_docs + 1
+  uint32_t *sen_tok_end, *sen_bstart, *sen_bend;  // cap each
+  int32_t *sen_rstart, *sen_rend;                 // cap each
+  uint32_t *text_sen_end;   // text_cap
+};
+
 // A stream slice's writer bytes in the position-free modes (dtk_streamrender.hip, dtk_stream_set_render): the one
 // document's tokens merged with its event list, on the download stream behind k_evl_*.
 struct DtkStreamRenderArgs {
@@ -556,6 +581,9 @@ uint32_t dtk_streamrender_tiles(uint64_t n);
 int dtk_launch_streamrender(const struct DtkStreamRenderArgs *args, void *stream);
 uint32_t dtk_evlist_tiles(uint64_t n_bits, uint32_t bit_words);
 int dtk_launch_evlist(const struct DtkEvListArgs *args, void *stream);
+uint32_t dtk_sentences_tile_bits(void);  // cursor positions per tile of dtk_sentences.hip
+uint32_t dtk_sentences_tiles(uint64_t n_bits, uint32_t bit_words);
+int dtk_launch_sentences(const struct DtkSentencesArgs *args, void *stream);
 int dtk_launch_to_host(const struct DtkToHostArgs *args, void *stream);
 int dtk_launch_pack_r16(const int32_t *rs, const int32_t *re, uint32_t *out, uint64_t n, void *stream);
 int dtk_launch_pack_blk(const struct DtkPackBlkArgs *args, void *stream);

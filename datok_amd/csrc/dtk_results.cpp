@@ -4,6 +4,7 @@
 #include <array>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 #define DTK_BLK_DECODER  // (this unit emits dtk_blk_start / dtk_blk_end of datok_gpu.h as exported functions)
 #include "dtk_host.h"
@@ -122,7 +123,205 @@ int pack_event_list(dtk_batch *b, uint64_t rows) {
   b->evl_copied = rows;
   return DTK_OK;
 }
+
+// ---- DTK_R_SENTENCES: the sentence table (dtk_sentences.hip; the definition is in include/datok_gpu.h)
+
+// Where the arrays lie in the device block and in its page-locked copy, for `rows` rows and `texts` text rows.
+dtk_batch::SenLayout sen_layout(uint64_t n_docs, uint64_t rows, uint64_t texts) {
+  dtk_batch::SenLayout L;
+  L.rows = rows; L.texts = texts;
+  uint64_t q = (n_docs + 1) * 8;  // sen_off
+  L.tok_end = q; q += rows * 4;
+  L.bstart = q; q += rows * 4;
+  L.bend = q; q += rows * 4;
+  L.rstart = q; q += rows * 4;
+  L.rend = q; q += rows * 4;
+  L.tse = q; q += texts * 4;
+  L.cnt = q; q += 4;
+  L.bytes = (q + 7) & ~(uint64_t)7;
+  return L;
+}
+
+void sen_view(const dtk_batch *b, const uint8_t *base, dtk_sentence_view *o) {
+  const dtk_batch::SenLayout &L = b->sen;
+  const bool runes = !(b->last_flags & DTK_NO_RUNE_OFFSETS);
+  o->n_sen = b->sen_n;
+  o->sen_off = (const uint64_t *)base;
+  o->sen_tok_end = (const uint32_t *)(base + L.tok_end);
+  o->sen_bstart = (const uint32_t *)(base + L.bstart);
+  o->sen_bend = (const uint32_t *)(base + L.bend);
+  o->sen_rstart = runes ? (const int32_t *)(base + L.rstart) : nullptr;
+  o->sen_rend = runes ? (const int32_t *)(base + L.rend) : nullptr;
+  o->text_sen_end = (const uint32_t *)(base + L.tse);
+}
+
+// Enqueues on the download stream what is still missing of: the table's kernels, and the copy of the whole block
+// (home) or of its count word.  The run is complete (finish()).
+int sen_enqueue(dtk_batch *b, bool home) {
+  if (b->last_flags & DTK_NO_BYTE_OFFSETS) return DTK_E_STATE;  // the table is keyed on tok_bend
+  const uint64_t n_bits = b->total + b->n_docs;
+  // every row is an int the writer's Token closure pushes to sent[]: n_sent bounds the rows of regular documents, and
+  // the count word backs the bound up (sen_finish)
+  uint64_t rows = g_dbg.sen_cap >= 0 ? (uint64_t)g_dbg.sen_cap : b->totals.n_sent;
+  rows = std::max<uint64_t>(std::max(rows, b->sen_need), 1);
+  if (n_bits > 0xFFFFFFFFull || rows > 0xFFFFFFFFull) return DTK_E_CAPACITY;
+  if (!dtk_batch_download_stream(b)) return hip_fail(hipGetLastError(), "download stream");
+  int rc;
+  if (b->sen_done && (b->sen_home || !home)) return DTK_OK;  // nothing is missing
+  if (!b->sen_built || (!b->sen_done && rows > b->sen.rows)) {
+    const dtk_batch::SenLayout L = sen_layout(b->n_docs, rows, b->totals.n_texts);
+    const uint32_t tiles = dtk_sentences_tiles(n_bits, b->bit_words);
+    const uint64_t ws = 3 * rows + 2 * (uint64_t)tiles;
+    if ((rc = b->d_sen.fit(L.bytes / 8, L.bytes / 8 + L.bytes / 64)) || (rc = b->d_sen_ws.fit(ws, ws + ws / 8)) ||
+        (rc = b->h_sen.fit((size_t)L.bytes)))
+      return rc;
+    b->sen = L;
+    uint8_t *base = (uint8_t *)b->d_sen.p;
+    DtkSentencesArgs a{};
+    a.bits = b->d_bits; a.bit_words = b->bit_words; a.n_docs = b->n_docs; a.doc_off = b->d_off; a.n_bits = n_bits;
+    a.n_tiles = tiles; a.cap = (uint32_t)rows;
+    a.tok_off = b->d_tok_off; a.text_off = b->d_text_off; a.tok_bstart = b->d_bstart; a.tok_bend = b->d_bend;
+    if (!(b->last_flags & DTK_NO_RUNE_OFFSETS)) { a.tok_rstart = b->d_rstart; a.tok_rend = b->d_rend; }
+    a.text_tok_end = b->d_ttok;
+    a.text_cap = L.texts;
+    a.sen_bit = b->d_sen_ws; a.sen_doc = a.sen_bit + rows; a.sen_first = a.sen_doc + rows;
+    a.tile_base = a.sen_first + rows; a.tile_in = a.tile_base + tiles;
+    a.count = (uint32_t *)(base + L.cnt);
+    a.sen_off = (uint64_t *)base;
+    a.sen_tok_end = (uint32_t *)(base + L.tok_end); a.sen_bstart = (uint32_t *)(base + L.bstart);
+    a.sen_bend = (uint32_t *)(base + L.bend); a.sen_rstart = (int32_t *)(base + L.rstart);
+    a.sen_rend = (int32_t *)(base + L.rend); a.text_sen_end = (uint32_t *)(base + L.tse);
+    if (dtk_launch_sentences(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "sentence table");
+    b->sen_built = true;
+    b->sen_home = b->sen_done = false;
+  } else if (b->sen_home) {
+    return DTK_OK;  // on its way
+  }
+  uint8_t *h = b->h_sen.as<uint8_t>();
+  if (home) HIP_TRY(hipMemcpyAsync(h, b->d_sen.p, (size_t)b->sen.bytes, hipMemcpyDeviceToHost, b->dl_stream));
+  else HIP_TRY(hipMemcpyAsync(h + b->sen.cnt, (const uint8_t *)b->d_sen.p + b->sen.cnt, 4, hipMemcpyDeviceToHost, b->dl_stream));
+  b->sen_home = home;
+  if ((rc = b->ev_sen.ensure(hipEventDisableTiming)) != DTK_OK) return rc;
+  HIP_TRY(hipEventRecord(b->ev_sen, b->dl_stream));
+  b->sen_waited = false;
+  return DTK_OK;
+}
+
+// The rows of documents the exact pass walked come from their calls: the table is taken apart on the host, their
+// rows are put in place of what their bitmaps gave, and the whole goes back to the device.  Exact, and slow.
+int sen_splice_exact(dtk_batch *b) {
+  const uint32_t nd = b->n_docs, ne = (uint32_t)b->h_exact_ids.size();
+  const bool runes = !(b->last_flags & DTK_NO_RUNE_OFFSETS);
+  std::vector<uint64_t> csr(3 * ((size_t)nd + 1));
+  HIP_TRY(hipMemcpy(csr.data(), b->d_csr, csr.size() * 8, hipMemcpyDeviceToHost));
+  const uint64_t *tok_off = csr.data(), *text_off = csr.data() + 2 * ((size_t)nd + 1);
+  const dtk_batch::SenLayout old = b->sen;
+  const uint8_t *h = b->h_sen.as<uint8_t>();
+  const uint64_t *o_off = (const uint64_t *)h;
+  struct Row { uint32_t tok_end, bstart, bend; int32_t rstart, rend; };
+  std::vector<Row> rows;
+  std::vector<uint64_t> off((size_t)nd + 1, 0);
+  std::vector<uint32_t> tse((const uint32_t *)(h + old.tse), (const uint32_t *)(h + old.tse) + old.texts);
+  rows.reserve((size_t)b->sen_n);
+  auto field = [&](uint64_t at, uint64_t i) { return ((const uint32_t *)(h + at))[i]; };
+  uint32_t e = 0;
+  std::vector<uint32_t> firsts, bs, be, ttok;
+  std::vector<int32_t> rs, re;
+  for (uint32_t d = 0; d < nd; d++) {
+    off[d] = rows.size();
+    if (e < ne && b->h_exact_ids[e] == d) {
+      firsts.clear();
+      uint32_t k = 0;
+      bool open = false;
+      for (uint64_t c = b->h_exact_off[e]; c < b->h_exact_off[e + 1]; c++) {
+        if (b->h_calls[c].kind == 0) { if (!open) firsts.push_back(k); open = true; k++; }
+        else open = false;
+      }
+      e++;
+      const uint64_t t0 = tok_off[d], nt = tok_off[d + 1] - t0;
+      if (k != nt) return DTK_E_STATE;  // (the exact pass wrote one token row per Token call)
+      bs.resize(nt); be.resize(nt); rs.assign(nt, 0); re.assign(nt, 0);
+      if (nt) {
+        HIP_TRY(hipMemcpy(bs.data(), b->d_bstart + t0, nt * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(be.data(), b->d_bend + t0, nt * 4, hipMemcpyDeviceToHost));
+        if (runes) {
+          HIP_TRY(hipMemcpy(rs.data(), b->d_rstart + t0, nt * 4, hipMemcpyDeviceToHost));
+          HIP_TRY(hipMemcpy(re.data(), b->d_rend + t0, nt * 4, hipMemcpyDeviceToHost));
+        }
+      }
+      for (size_t i = 0; i < firsts.size(); i++) {
+        const uint32_t f = firsts[i], end = i + 1 < firsts.size() ? firsts[i + 1] : (uint32_t)nt;
+        rows.push_back(Row{end, bs[f], be[end - 1], rs[f], re[end - 1]});
+      }
+      const uint64_t x0 = text_off[d], nx = text_off[d + 1] - x0;
+      ttok.resize(nx);
+      if (nx) HIP_TRY(hipMemcpy(ttok.data(), b->d_ttok + x0, nx * 4, hipMemcpyDeviceToHost));
+      for (uint64_t g = 0; g < nx && x0 + g < tse.size(); g++)
+        tse[x0 + g] = (uint32_t)(std::lower_bound(firsts.begin(), firsts.end(), ttok[g]) - firsts.begin());
+    } else {
+      for (uint64_t i = o_off[d]; i < o_off[d + 1]; i++)
+        rows.push_back(Row{field(old.tok_end, i), field(old.bstart, i), field(old.bend, i), (int32_t)field(old.rstart, i),
+                           (int32_t)field(old.rend, i)});
+    }
+  }
+  off[nd] = rows.size();
+  const uint64_t n = rows.size();
+  const dtk_batch::SenLayout L = sen_layout(nd, std::max<uint64_t>(n, 1), old.texts);
+  std::vector<uint64_t> blk(L.bytes / 8, 0);
+  uint8_t *q = (uint8_t *)blk.data();
+  memcpy(q, off.data(), off.size() * 8);
+  for (uint64_t i = 0; i < n; i++) {
+    ((uint32_t *)(q + L.tok_end))[i] = rows[i].tok_end; ((uint32_t *)(q + L.bstart))[i] = rows[i].bstart;
+    ((uint32_t *)(q + L.bend))[i] = rows[i].bend; ((int32_t *)(q + L.rstart))[i] = rows[i].rstart;
+    ((int32_t *)(q + L.rend))[i] = rows[i].rend;
+  }
+  if (!tse.empty()) memcpy(q + L.tse, tse.data(), tse.size() * 4);
+  *(uint32_t *)(q + L.cnt) = (uint32_t)n;
+  int rc;
+  if ((rc = b->d_sen.fit(L.bytes / 8, L.bytes / 8)) || (rc = b->h_sen.fit((size_t)L.bytes))) return rc;
+  memcpy(b->h_sen.p, q, (size_t)L.bytes);
+  HIP_TRY(hipMemcpy(b->d_sen.p, q, (size_t)L.bytes, hipMemcpyHostToDevice));
+  b->sen = L;
+  b->sen_n = n;
+  return DTK_OK;
+}
+
+// The table, complete: on the device, and (home) in the page-locked block.
+int sen_finish(dtk_batch *b, bool home) {
+  int rc = finish(b);
+  if (rc != DTK_OK) return rc;
+  if (!b->h_exact_ids.empty()) home = true;  // (the splice works on the host copy)
+  for (;;) {
+    if ((rc = sen_enqueue(b, home)) != DTK_OK) return rc;
+    if (!b->sen_waited) { HIP_TRY(hipEventSynchronize(b->ev_sen)); b->sen_waited = true; }
+    if (b->sen_done) return DTK_OK;  // (the count was looked at before: this call only brought the block home)
+    const uint64_t n = *(const uint32_t *)(b->h_sen.as<uint8_t>() + b->sen.cnt);
+    if (n <= b->sen.rows) { b->sen_n = n; break; }
+    // more rows than the bound (not expected of regular documents): the kernels wrote nothing; again, for n rows
+    b->sen_need = n;
+    b->sen_built = false;
+  }
+  if (!b->h_exact_ids.empty() && (rc = sen_splice_exact(b)) != DTK_OK) return rc;
+  b->sen_done = true;
+  return DTK_OK;
+}
 }  // namespace
+
+extern "C" int dtk_batch_sentences_device(dtk_batch *b, dtk_sentence_view *o) {
+  if (!b || !o) return DTK_E_ARG;
+  const int rc = sen_finish(b, false);
+  if (rc != DTK_OK) return rc;
+  sen_view(b, (const uint8_t *)b->d_sen.p, o);
+  return DTK_OK;
+}
+
+extern "C" int dtk_batch_sentences_host(dtk_batch *b, dtk_sentence_view *o) {
+  if (!b || !o) return DTK_E_ARG;
+  const int rc = sen_finish(b, true);
+  if (rc != DTK_OK) return rc;
+  sen_view(b, b->h_sen.as<uint8_t>(), o);
+  return DTK_OK;
+}
 
 extern "C" int dtk_batch_result_device(dtk_batch *b, dtk_result_view *o) {
   if (!b || !o) return DTK_E_ARG;
@@ -139,7 +338,7 @@ extern "C" int dtk_batch_result_device(dtk_batch *b, dtk_result_view *o) {
 }
 
 extern "C" int dtk_batch_set_result_fields(dtk_batch *b, uint32_t fields) {
-  if (!b || (fields & ~(uint32_t)(DTK_R_ALL | DTK_R_TOK_RUNE16 | DTK_R_EAGER | kBlkFields | DTK_R_EVENT_LIST))) return DTK_E_ARG;
+  if (!b || (fields & ~(uint32_t)(DTK_R_ALL | DTK_R_TOK_RUNE16 | DTK_R_EAGER | kBlkFields | DTK_R_EVENT_LIST | DTK_R_SENTENCES))) return DTK_E_ARG;
   b->fields = fields;
   return DTK_OK;
 }
@@ -190,7 +389,7 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
   if (!b) return DTK_E_ARG;
   int rc = finish(b);
   if (rc != DTK_OK) return rc;
-  uint32_t sel = b->fields & (DTK_R_ALL | DTK_R_TOK_RUNE16 | kBlkFields | DTK_R_EVENT_LIST);
+  uint32_t sel = b->fields & (DTK_R_ALL | DTK_R_TOK_RUNE16 | kBlkFields | DTK_R_EVENT_LIST | DTK_R_SENTENCES);
   if (sel & DTK_R_TOK_RUNE16) {
     // the narrow form holds every offset of a document of at most 32 767 bytes; a batch with a longer one gets the
     // 32-bit arrays in its place
@@ -222,6 +421,8 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
     //  outgrow its arrays -- it is computed again)
     if ((rc = slice_outputs(b)) != DTK_OK) return rc;
   }
+  // the sentence table: its kernels and its one copy, in front of the arrays' copies (dtk_batch_sentences_host waits)
+  if ((want & DTK_R_SENTENCES) && (rc = sen_enqueue(b, true)) != DTK_OK) return rc;
   const uint32_t blk_want = tot[0] ? want & kBlkFields : 0u;  // (no token: nothing to pack, empty arrays)
   if (blk_want && (rc = pack_blocked(b, blk_want, tot[0])) != DTK_OK) return rc;
   for (const HostArray &r : host_arrays(b)) {

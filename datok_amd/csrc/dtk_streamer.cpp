@@ -101,7 +101,8 @@ extern "C" int dtk_stream_set_result_fields(dtk_stream *s, uint32_t fields) {
   if (!s || !(fields & (DTK_R_TOK_BYTE | DTK_R_TOK_BYTE_BLK))) return DTK_E_ARG;
   // (the rune fields of a slice's view would be the compaction's: the window as a fresh document.  The stream's rune
   //  offsets and sentence list come from dtk_stream_set_offsets, computed from the writer's carried state.)
-  if (fields & (DTK_R_TOK_RUNE | DTK_R_TOK_RUNE16 | DTK_R_TOK_RUNE_BLK | DTK_R_SENT | DTK_R_EAGER)) return DTK_E_ARG;
+  // (nor the sentence table: a sentence can span a cut)
+  if (fields & (DTK_R_TOK_RUNE | DTK_R_TOK_RUNE16 | DTK_R_TOK_RUNE_BLK | DTK_R_SENT | DTK_R_EAGER | DTK_R_SENTENCES)) return DTK_E_ARG;
   fields |= kForced;
   for (dtk_batch *b : s->slots) {
     const int rc = dtk_batch_set_result_fields(b, fields);

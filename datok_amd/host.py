@@ -6,7 +6,7 @@ import sys
 import numpy as np
 
 from . import _lib
-from ._lib import ModelInfo, RenderView, ResultView, Totals, check, lib
+from ._lib import ModelInfo, RenderView, ResultView, SentenceView, Totals, check, lib
 
 # token_writer.go:17-25
 TOKENS, SENTENCES, TOKEN_POS, SENTENCE_POS, NEWLINE_AFTER_EOT = 1, 2, 4, 8, 16
@@ -487,6 +487,22 @@ class BatchResult:
                     text_sent_end=self.text_sent_end[t0:t1], status=int(self.status[d]))
 
 
+class SentenceTable:
+    """dtk_sentence_view (datok_gpu.h): a batch's sentences as rows, under the C names.  A sentence is a maximal
+    non-empty run of Token calls with no SentenceEnd / TextEnd between them; row i of document d holds the document's
+    tokens [sen_tok_end[i - 1], sen_tok_end[i]) (0 at the document's first row), the bytes [sen_bstart[i], sen_bend[i])
+    of the document and the runes [sen_rstart[i], sen_rend[i]) of the text.  Host table: numpy arrays (sen_rstart /
+    sen_rend are None after a run with NO_RUNE_OFFSETS); device table: the raw device pointers as ints (or None)."""
+    __slots__ = ("n_sen", "sen_off", "sen_tok_end", "sen_bstart", "sen_bend", "sen_rstart", "sen_rend", "text_sen_end")
+
+    def doc(self, d):
+        """The rows of document d of a host table."""
+        a, b = int(self.sen_off[d]), int(self.sen_off[d + 1])
+        return dict(sen_tok_end=self.sen_tok_end[a:b], sen_bstart=self.sen_bstart[a:b], sen_bend=self.sen_bend[a:b],
+                    sen_rstart=None if self.sen_rstart is None else self.sen_rstart[a:b],
+                    sen_rend=None if self.sen_rend is None else self.sen_rend[a:b])
+
+
 class Batch:
     """dtk_batch: device buffers + one HIP stream for many documents per launch."""
 
@@ -608,6 +624,38 @@ class Batch:
                            # a block that does not fit gets the 32-bit arrays in their place
     R_EVENT_LIST = 2048    # what a closure replay needs of the event bitmaps as a list (BatchResult.evl_off / evl_pos /
                            # evl_kind, replay_list) + doc_tail: about one 5-byte entry per sentence
+
+    R_SENTENCES = 8192     # the sentence table (sentences()) comes home with the download; without the bit it is built
+                           # and copied when sentences() asks
+
+    def sentences(self, device=False, copy=True) -> SentenceTable:
+        """The last run's sentences as rows (dtk_batch_sentences_host; device=True: dtk_batch_sentences_device, the
+        table stays in HBM and the fields are raw device pointers).  copy=False: views of the batch's page-locked
+        block, valid until its next run.  E_STATE before a run and after a run with NO_BYTE_OFFSETS."""
+        v = SentenceView()
+        fn = lib().dtk_batch_sentences_device if device else lib().dtk_batch_sentences_host
+        check(fn(self._h, C.byref(v)), "dtk_batch_sentences_device" if device else "dtk_batch_sentences_host")
+        t = SentenceTable()
+        t.n_sen = int(v.n_sen)
+        names = [n for n, _ in SentenceView._fields_[1:]]
+        if device:
+            for n in names:
+                setattr(t, n, getattr(v, n) or None)
+            return t
+        n_texts = self.totals()["n_texts"]
+        shape = dict(sen_off=(self.n_docs + 1, np.uint64), sen_tok_end=(t.n_sen, np.uint32), sen_bstart=(t.n_sen, np.uint32),
+                     sen_bend=(t.n_sen, np.uint32), sen_rstart=(t.n_sen, np.int32), sen_rend=(t.n_sen, np.int32),
+                     text_sen_end=(n_texts, np.uint32))
+        for n in names:
+            ptr, (cnt, dt) = getattr(v, n), shape[n]
+            if not ptr:
+                setattr(t, n, None)
+            elif cnt == 0:
+                setattr(t, n, np.zeros(0, dt))
+            else:
+                a = np.frombuffer((C.c_char * (cnt * np.dtype(dt).itemsize)).from_address(ptr), dtype=dt)
+                setattr(t, n, a.copy() if copy else a)
+        return t
 
     def set_result_fields(self, fields=R_ALL):
         """Which arrays result() brings to the host (the others come back empty)."""

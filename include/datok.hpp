@@ -504,4 +504,33 @@ inline bool ModelInfo(const void *gz_bytes, size_t n, dtk_model_info *out) {
   return rc == DTK_OK;
 }
 
+// ---- a batch's sentences as rows (dtk_sentence_view, datok_gpu.h): a sentence is a maximal non-empty run of Token
+// calls with no SentenceEnd / TextEnd between them.
+// The last run's table in page-locked host memory (device: device pointers), valid until the batch's next run; false +
+// log line on failure (before a run, or after a run with DTK_NO_BYTE_OFFSETS).
+inline bool Sentences(dtk_batch *b, dtk_sentence_view *out, bool device = false) {
+  const int rc = device ? dtk_batch_sentences_device(b, out) : dtk_batch_sentences_host(b, out);
+  if (rc != DTK_OK) std::fprintf(stderr, "datok: sentences: %s\n", dtk_strerror(rc));
+  return rc == DTK_OK;
+}
+
+// One sentence of a document: its tokens [tok_first, tok_end) (document-relative, as text_tok_end counts), its bytes
+// [bstart, bend) of the document and its runes [rstart, rend) of the text (0 when the run had DTK_NO_RUNE_OFFSETS).
+struct SentenceRow {
+  uint32_t tok_first, tok_end, bstart, bend;
+  int32_t rstart, rend;
+};
+// The rows of document d of a host view.
+inline std::vector<SentenceRow> sentence_rows(const dtk_sentence_view &v, uint32_t d) {
+  std::vector<SentenceRow> rows;
+  rows.reserve((size_t)(v.sen_off[d + 1] - v.sen_off[d]));
+  uint32_t first = 0;
+  for (uint64_t i = v.sen_off[d]; i < v.sen_off[d + 1]; i++) {
+    rows.push_back(SentenceRow{first, v.sen_tok_end[i], v.sen_bstart[i], v.sen_bend[i], v.sen_rstart ? v.sen_rstart[i] : 0,
+                               v.sen_rend ? v.sen_rend[i] : 0});
+    first = v.sen_tok_end[i];
+  }
+  return rows;
+}
+
 }  // namespace datok

@@ -382,7 +382,12 @@ enum {
    * DTK_R_EVENTS.  A closure replay then needs DTK_R_EVENT_LIST | DTK_R_TOK_BYTE (or DTK_R_TOK_BYTE_BLK) | DTK_R_CSR |
    * DTK_R_STATUS.  The copies are enqueued for n_sent + n_texts entries, which bounds the count for regular documents;
    * dtk_batch_result_host looks at the true count behind the download and copies again if that was too few. */
-  DTK_R_EVENT_LIST = 2048
+  DTK_R_EVENT_LIST = 2048,
+  /* the sentence table (dtk_sentence_view below, read with dtk_batch_sentences_host): built from the event bitmaps and
+   * the token rows on the download stream in front of its copies and brought home with the other fields, about 20 B
+   * per sentence.  Like DTK_R_EVENT_LIST not part of DTK_R_ALL nor of the eager copy.  A run with DTK_NO_BYTE_OFFSETS
+   * has no table (it is keyed on tok_bend): the bit is then ignored.  (4096 stays an unknown bit.) */
+  DTK_R_SENTENCES = 8192
 };
 /* bits of evl_kind; at one cursor the calls fire in the order SEOT, TEOT, the Token ending there, SEPS */
 enum { DTK_EVL_SEOT = 1, DTK_EVL_TEOT = 2, DTK_EVL_SEPS = 4 };
@@ -394,6 +399,44 @@ int dtk_batch_download_begin(dtk_batch *b);
 int dtk_batch_set_download_stream(dtk_batch *b, void *hip_stream);
 void *dtk_batch_download_stream(dtk_batch *b);
 int dtk_batch_result_host(dtk_batch *b, dtk_result_view *out);
+
+/* ---- a batch's sentences as rows: which tokens form a sentence, and its byte and rune span.
+ *      The definition is a pure function of the reference's calls for one document (one TransduceTokenWriter call),
+ *      scanned in order: a SENTENCE is a maximal non-empty run of Token calls with no SentenceEnd or TextEnd between
+ *      them.  An open run is closed by a SentenceEnd, by a TextEnd, or by the end of the calls; a boundary with no
+ *      token since the previous one makes no row.  Every token of a document belongs to exactly one sentence: row i
+ *      of document d is the token range [sen_tok_end[i - 1], sen_tok_end[i]) of the document, with 0 in place of
+ *      sen_tok_end[i - 1] at the document's first row.  This is the writer's own notion: a document has as many rows
+ *      as the writer's Token closure pushes ints to sent[] (token_writer.go:75-79; sentB is true at the start and
+ *      behind either kind of boundary), so rows(d) <= sent_off[d + 1] - sent_off[d] and dtk_totals.n_sent bounds n_sen.
+ *        From the event bitmaps (every document not in exact_doc): f = 1 at the document's bit 0; then per cursor
+ *      p = 0..len in ascending order, in the order the calls fire there: SEOT or TEOT set: f = 1; END set: that token
+ *      is a sentence's first iff f, then f = 0; SEPS set: f = 1.  The tail word's calls come last and open nothing.
+ *      The k-th END bit of a document is its k-th token: the first token of a row is the first k of the document's
+ *      rows with tok_bend[k] >= cursor.  Documents in exact_doc get their rows from `calls` by the definition above;
+ *      documents with a status bit get the rows this rule gives on what was delivered for them (a span whose token
+ *      row does not exist reads as 0).
+ *        dtk_batch_sentences_device: device pointers owned by the batch; the table is built on the batch's download
+ *      stream and the call returns when it is complete.  dtk_batch_sentences_host: page-locked host memory; with
+ *      DTK_R_SENTENCES among the result fields dtk_batch_download_begin has built and copied the table and the call
+ *      only waits, without the bit it builds and copies on demand.  Both views are valid until the batch's next run
+ *      or free.  Before a run, and after a run with DTK_NO_BYTE_OFFSETS: DTK_E_STATE (also, never expected, when a
+ *      document in exact_doc has another number of Token calls than token rows).  (With documents in exact_doc
+ *      the table is finished on the host and written back: a slow path that only crafted models reach.) ---- */
+typedef struct {
+  uint64_t n_sen;                  /* rows in the batch */
+  const uint64_t *sen_off;         /* n_docs + 1: rows of document d are [sen_off[d], sen_off[d+1]) */
+  const uint32_t *sen_tok_end;     /* document-relative: tokens of the document up to and including row i's last
+                                      (the convention of text_tok_end) */
+  const uint32_t *sen_bstart, *sen_bend;  /* tok_bstart of the row's first token, tok_bend of its last */
+  const int32_t  *sen_rstart, *sen_rend;  /* tok_rstart of the first, tok_rend of the last (text-relative, so they
+                                             follow DTK_NEWLINE_AFTER_EOT as the token rows do); NULL when the run
+                                             had DTK_NO_RUNE_OFFSETS */
+  const uint32_t *text_sen_end;    /* one per TextEnd, indexed like text_tok_end (text_off): rows of the document
+                                      closed in front of that TextEnd (a TextEnd closes the open sentence first) */
+} dtk_sentence_view;
+int dtk_batch_sentences_device(dtk_batch *b, dtk_sentence_view *out);
+int dtk_batch_sentences_host(dtk_batch *b, dtk_sentence_view *out);
 
 /* bit of position 0 of document d in the bitmaps of dtk_result_view.ev_bits */
 #define DTK_EVENT_BIT(doc_off_d, d) (((uint64_t)(doc_off_d)) + (uint64_t)(d))
@@ -488,7 +531,8 @@ int dtk_stream_set_chunking(dtk_stream *s, uint32_t chunk_bytes, uint32_t warm_b
 /* The DTK_R_* arrays of every slice's view.  DTK_R_CSR, DTK_R_STATUS, DTK_R_TEXTS and DTK_R_EVENT_LIST always come;
  * the token bytes must be among them as DTK_R_TOK_BYTE or DTK_R_TOK_BYTE_BLK (else DTK_E_ARG).  Default: DTK_R_TOK_BYTE.
  * The rune fields (DTK_R_TOK_RUNE*, DTK_R_SENT) are DTK_E_ARG: a slice's view is the compaction's fresh-document view,
- * and the way to the stream's rune offsets and sentence list is dtk_stream_set_offsets. */
+ * and the way to the stream's rune offsets and sentence list is dtk_stream_set_offsets.  DTK_R_SENTENCES is DTK_E_ARG
+ * too: a sentence can span a cut. */
 int dtk_stream_set_result_fields(dtk_stream *s, uint32_t fields);
 /* on != 0: every slice also brings the bytes a stock NewTokenWriter(w, bits) writes for its calls, rendered on the device
  * behind the slice's event list and in front of its copies (about one more byte per input byte on the link); the

@@ -38,6 +38,7 @@ EXPORTS = [
     "dtk_stream_set_position_render", "dtk_stream_positions", "dtk_stream_emit",
     "dtk_stream_set_offsets", "dtk_stream_offsets", "dtk_blk64_start", "dtk_blk64_end",
     "dtk_batch_sentences_device", "dtk_batch_sentences_host",
+    "dtk_stream_set_sentences", "dtk_stream_sentences",
 ]
 
 
@@ -109,6 +110,19 @@ class StreamOffs(C.Structure):
                 ("tok_rstart", C.c_void_p), ("tok_rend", C.c_void_p), ("tok_rblk", C.c_void_p), ("tok_rblk_head", C.c_void_p),
                 ("sent", C.c_void_p), ("text_tok_end", C.c_void_p), ("text_sent_end", C.c_void_p),
                 ("carry_in", StreamCarry), ("carry_out", StreamCarry)]
+
+
+class StreamSenCarry(C.Structure):
+    """dtk_stream_sen_carry: the sentence that is open at a cut."""
+    _fields_ = [("open", C.c_uint32), ("reserved", C.c_uint32), ("bstart", C.c_uint64), ("bend", C.c_uint64),
+                ("rstart", C.c_int64), ("rend", C.c_int64)]
+
+
+class StreamSens(C.Structure):
+    """dtk_stream_sens: the sentences a slice's calls close, as rows (dtk_stream_sentences)."""
+    _fields_ = [("n_sen", C.c_uint64), ("n_text", C.c_uint64), ("sen_tok_end", C.c_void_p),
+                ("sen_bstart", C.c_void_p), ("sen_bend", C.c_void_p), ("sen_rstart", C.c_void_p), ("sen_rend", C.c_void_p),
+                ("text_sen_end", C.c_void_p), ("carry_in", StreamSenCarry), ("carry_out", StreamSenCarry)]
 
 
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -233,6 +247,8 @@ def lib():
     L.dtk_stream_emit.argtypes = [vp, WRITE_FN, vp]
     L.dtk_stream_set_offsets.argtypes = [vp, C.c_int, u32]
     L.dtk_stream_offsets.argtypes = [vp, C.POINTER(StreamOffs)]
+    L.dtk_stream_set_sentences.argtypes = [vp, C.c_int]
+    L.dtk_stream_sentences.argtypes = [vp, C.POINTER(StreamSens)]
     for f in (L.dtk_blk64_start, L.dtk_blk64_end):
         f.argtypes, f.restype = [vp, vp, u64], C.c_int64
     L.dtk_stream_run.argtypes = [vp, vp, READ_FN, vp, u32, STREAM_SLICE_FN, vp, C.POINTER(u32)]

@@ -98,10 +98,16 @@ struct SliceRequest {
   // position-free bytes or without them
   bool offs = false;
   uint32_t form = 0;            // DTK_SO_*
+  // the sentences as rows (dtk_stream_set_sentences, dtk_streamsens.hip), behind the offsets chain, which then runs
+  // whether offs is set or not (without it: in the plain form, and nothing of its arrays comes home)
+  bool sens = false;
+  uint64_t base = 0;            // sens: stream offset of window byte 0
+  const DtkSenCarry *sen_carry_in = nullptr;  // sens: the open row comes from one of the stream's slots and goes into another
+  DtkSenCarry *sen_carry_out = nullptr;
   bool is_matrix = false;
   bool nl = false;              // the run's NEWLINE_AFTER_EOT (offsets; a position mode has it in bits)
   uint32_t digits = 0;          // kPosBytes: no integer of the slice has more bytes (the stream's bound)
-  // kPosBytes or offs: the writer's state comes from one of the stream's carry slots and goes into another
+  // kPosBytes, offs or sens: the writer's state comes from one of the stream's carry slots and goes into another
   const DtkPosCarry *carry_in = nullptr;
   DtkPosCarry *carry_out = nullptr;
 };
@@ -115,6 +121,14 @@ struct SoLayout {
   uint64_t rstart = 0, rend = 0, sent = 0, trailer = 0, ttok = 0, tsent = 0, heads = 0, words = 0, bytes = 0;
   bool blocked = false, wide_home = false;     // wide_home: tok_rstart / tok_rend are in the page-locked copy
 };
+// The sentence rows' device block and its page-locked copy, in the same way: trailer | text_sen_end | sen_tok_end |
+// sen_bstart | sen_bend | sen_rstart | sen_rend.  The copies bring the trailer, the text rows and the five arrays as far
+// as the compaction's counts reach; what the trailer counts beyond that is copied at delivery.
+struct SsLayout {
+  uint64_t n = 0, sen_cap = 0, text_cap = 0;   // the capacities: tokens (exact), rows, texts
+  uint64_t sen_home = 0, text_home = 0;        // rows / text rows the page-locked copy holds
+  uint64_t trailer = 0, tse = 0, tok_end = 0, bstart = 0, bend = 0, rstart = 0, rend = 0, bytes = 0;
+};
 struct SliceOut {
   SliceRequest req;
   // the bytes: d_out (cap bytes, then the length word or the trailer block) and its page-locked copy, both sized
@@ -126,6 +140,9 @@ struct SliceOut {
   SoLayout so;
   DevArray<uint64_t> d_offs_ws, d_offs_out;
   PinBuf h_offs_out;
+  SsLayout ss;
+  DevArray<uint64_t> d_sens_ws, d_sens_out;
+  PinBuf h_sens_out;
 };
 
 // -------------------------------------------------------------------- batch
@@ -308,6 +325,13 @@ int batch_cut(dtk_batch *b, DtkStreamCut *out);
 //   batch_pos_out     kPosBytes: the bytes and the trailer block behind them (DTK_E_CAPACITY / DTK_E_IRREGULAR as it says)
 //   batch_offs_out    offs: the page-locked arrays (DTK_E_CAPACITY / DTK_E_IRREGULAR as the trailer says); the blocked
 //                     pointers are null where the plain arrays stand in, and the other way round
+//   batch_sens_out    sens: the page-locked rows (DTK_E_CAPACITY / DTK_E_IRREGULAR as its own trailer says)
+struct SsView {
+  const DtkSensTrailer *t;
+  const uint32_t *tok_end, *tse;
+  const uint64_t *bstart, *bend;
+  const int64_t *rstart, *rend;
+};
 struct SoView {
   const DtkOffsTrailer *t;
   const int64_t *rstart, *rend, *sent;
@@ -320,6 +344,7 @@ int slice_outputs(dtk_batch *b);
 int batch_render_out(dtk_batch *b, const uint8_t **out, uint64_t *out_len);
 int batch_pos_out(dtk_batch *b, const uint8_t **out, const DtkPosTrailer **trailer);
 int batch_offs_out(dtk_batch *b, SoView *o);
+int batch_sens_out(dtk_batch *b, SsView *o);
 inline uint64_t blocks_of(uint64_t tokens) { return (tokens + 63) / 64; }  // blocks of 64 tokens
 
 // The DTK_R_* arrays the last run wrote: DTK_NO_RUNE_OFFSETS / DTK_NO_BYTE_OFFSETS leave theirs alone.

@@ -568,9 +568,42 @@ struct DtkStreamOffsArgs {
   struct DtkOffsTrailer *trailer;
 };
 
+// The sentences of a slice as rows (dtk_streamsens.hip, dtk_stream_set_sentences), behind the offsets chain of the same
+// slice: `front` is that chain's, with its workspace as the chain left it (tok_meta, rstart / rend, hdr, te_idx, the
+// writer's carry_out).  What crosses a cut is the row that is open there.
+struct DtkSenCarry {                       // dtk_stream_sen_carry of datok_gpu.h
+  uint32_t open, reserved;
+  uint64_t bstart, bend;                   // stream byte offsets: start of its first token, end of its last so far
+  int64_t rstart, rend;                    // the writer's rune offsets of the same two
+};
+struct DtkSensTrailer {
+  uint64_t n_tok;                          // ~0: the list did not fit its arrays, nothing was computed
+  uint64_t n_sen, n_text;                  // rows closed by this slice's calls, TextEnd calls: beyond a capacity, the array is cut short
+  uint64_t firsts;                         // tokens of the slice that begin a sentence (the kernels' own)
+  struct DtkSenCarry carry_in, carry_out;
+  uint32_t flags, pad;                     // 1: a token with rend == 0 under NEWLINE_AFTER_EOT
+};
+struct DtkStreamSensArgs {
+  struct DtkStreamPosArgs front;
+  uint64_t base;                           // stream offset of window byte 0
+  const struct DtkSenCarry *carry_in;      // device: the predecessor's carry_out
+  struct DtkSenCarry *carry_out;           // device: another slot
+  uint64_t *first_base;                    // workspace, tok_tiles: a tile's sentence-first tokens, then their exclusive scan
+  uint64_t *first_mask;                    // workspace, ceil(n_tok / 64): which tokens of a wave's 64 begin a sentence
+  uint64_t sen_cap, text_cap;              // nothing is written at or behind them
+  uint32_t *sen_tok_end;                   // sen_cap each
+  uint64_t *sen_bstart, *sen_bend;
+  int64_t *sen_rstart, *sen_rend;
+  uint32_t *text_sen_end;                  // text_cap
+  struct DtkSensTrailer *trailer;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+#define DTK_STREAMSENS_EVENTS 5   // one in front of the unit's four launches and one behind each
+int dtk_launch_streamsens(const struct DtkStreamSensArgs *args, void *stream, void **events);  // events: null, or that many hipEvent_t
+uint64_t dtk_streamsens_ws(struct DtkStreamSensArgs *args, uint64_t *ws);  // as dtk_streampos_ws, the unit's own two arrays
 #define DTK_STREAMOFFS_EVENTS 11  // one in front of the chain's ten launches and one behind each
 int dtk_launch_streamoffs(const struct DtkStreamOffsArgs *args, void *stream, void **events);  // events: null, or that many hipEvent_t
 uint64_t dtk_streamoffs_ws(struct DtkStreamOffsArgs *args, uint64_t *ws);  // as dtk_streampos_ws

@@ -1,6 +1,6 @@
 // dtk_slice.cpp -- what a slice of a stream brings home beside its batch's result arrays (SliceRequest, dtk_host.h): the
-// writer's bytes in a position-free mode or in a position mode, and the writer's rune offsets and sentence list as
-// arrays.  All of it is computed on the download stream behind the list's kernels and in front of the copies
+// writer's bytes in a position-free mode or in a position mode, the writer's rune offsets and sentence list as
+// arrays, and the sentences as rows.  All of it is computed on the download stream behind the list's kernels and in front of the copies
 // (slice_outputs, called by dtk_batch_download_begin behind every packing of the event list), into buffers that are
 // sized from what the host knows before anything is enqueued, and handed out behind dtk_batch_result_host.
 #include <algorithm>
@@ -90,15 +90,16 @@ int render_slice_pos(dtk_batch *b) {
 // offs.  The capacities are bounds the host can state before anything is enqueued, from the
 // tokens and the list's rows: the kernels compute nothing for a list of more than `rows` entries, so the slice has at
 // most 2 * rows + 1 SentenceEnd calls and rows + 1 TextEnd calls; a SentenceEnd call pushes one int, and a token pushes
-// one if such a call (or the carry) lies in front of it.
-int slice_offsets(dtk_batch *b) {
+// one if such a call (or the carry) lies in front of it.  Without offs (the sentence rows alone want the chain's device
+// results) the form is the plain one and nothing is copied home.  *chain: the chain's arguments as they were launched.
+int slice_offsets(dtk_batch *b, DtkStreamOffsArgs *chain) {
   SliceOut &o = b->slice;
   const SliceRequest &q = o.req;
   if (!q.carry_in || !q.carry_out) return DTK_E_STATE;
   const uint64_t rows = b->evl_copied, nt = b->totals.n_tokens;
   SoLayout L;
   L.n = nt; L.sent_cap = std::min<uint64_t>(nt, 3 * rows + 3) + 2 * rows + 1; L.text_cap = rows + 1;
-  L.blocked = q.form == DTK_SO_BLOCKED;
+  L.blocked = q.offs && q.form == DTK_SO_BLOCKED;
   // What the copies bring of sent and the text rows: the compaction's counts for the window as a fresh document, which
   // differ from the stream's by the few calls in front of the slice's first token.  batch_offs_out brings the rest if
   // the trailer counts more (the debug key EVL_CAP sizes these too, so that ordinary text gets there).
@@ -117,7 +118,7 @@ int slice_offsets(dtk_batch *b) {
   const uint64_t words = dtk_streamoffs_ws(&a, nullptr), out_words = L.bytes / 8;
   int rc;
   if ((rc = o.d_offs_ws.fit(words, words + words / 8 + 16)) || (rc = o.d_offs_out.fit(out_words, out_words + out_words / 8 + 32)) ||
-      (rc = o.h_offs_out.fit((size_t)L.bytes)))
+      (q.offs && (rc = o.h_offs_out.fit((size_t)L.bytes))))
     return rc;
   (void)dtk_streamoffs_ws(&a, o.d_offs_ws);
   uint8_t *d = reinterpret_cast<uint8_t *>(o.d_offs_out.p), *h = o.h_offs_out.as<uint8_t>();
@@ -128,6 +129,9 @@ int slice_offsets(dtk_batch *b) {
   a.blocked = L.blocked ? 1u : 0u; a.span = g_dbg.blk_span > 0 ? (uint32_t)g_dbg.blk_span : 65535u;
   a.heads = reinterpret_cast<DtkOffBlock64 *>(d + L.heads); a.words = reinterpret_cast<uint32_t *>(d + L.words);
   if (dtk_launch_streamoffs(&a, b->dl_stream, nullptr)) return hip_fail(hipGetLastError(), "slice offsets");
+  *chain = a;
+  o.so = L;
+  if (!q.offs) return DTK_OK;
   // the plain offsets and sent lie back to back; then the trailer with text_tok_end, text_sent_end, the blocked form
   const uint64_t piece[4][2] = {{L.blocked ? L.sent : 0, L.sent + L.sent_home * 8},
                                 {L.trailer, L.ttok + L.text_home * 4},
@@ -135,8 +139,56 @@ int slice_offsets(dtk_batch *b) {
                                 {L.heads, L.blocked ? L.bytes : L.heads}};
   for (const auto &p : piece)
     if (p[1] > p[0]) HIP_TRY(hipMemcpyAsync(h + p[0], d + p[0], (size_t)(p[1] - p[0]), hipMemcpyDeviceToHost, b->dl_stream));
-  L.wide_home = !L.blocked;
-  o.so = L;
+  o.so.wide_home = !L.blocked;
+  return DTK_OK;
+}
+
+// sens, behind the offsets chain `chain` of the same slice.  A sentence-first token needs a call or the carry in front
+// of it, and the carried row is one more: min(n_tok, 3 * rows + 3) + 1 rows, and a text row per TextEnd as above.
+int slice_sentences(dtk_batch *b, const DtkStreamOffsArgs &chain) {
+  SliceOut &o = b->slice;
+  const SliceRequest &q = o.req;
+  if (!q.sen_carry_in || !q.sen_carry_out) return DTK_E_STATE;
+  const uint64_t rows = b->evl_copied, nt = b->totals.n_tokens;
+  SsLayout L;
+  L.n = nt; L.sen_cap = std::min<uint64_t>(nt, 3 * rows + 3) + 1; L.text_cap = rows + 1;
+  // What the copies bring of the rows, from the compaction's counts for the window as a fresh document: there every row
+  // pushes one sent int with its first token, and a second one unless a TextEnd or the window's end closes it, so
+  // 2 * rows <= n_sent + n_texts + 1 (half of n_sent + 64 rows' bytes on running text; the carried row and the calls in
+  // front of the first token are inside the 64).  batch_sens_out brings the rest if the trailer counts more.
+  L.sen_home = std::min<uint64_t>(L.sen_cap, g_dbg.evl_cap >= 0 ? (uint64_t)g_dbg.evl_cap
+                                                                : (b->totals.n_sent + b->totals.n_texts + 1) / 2 + 64);
+  L.text_home = std::min<uint64_t>(L.text_cap, g_dbg.evl_cap >= 0 ? (uint64_t)g_dbg.evl_cap : b->totals.n_texts + 2);
+  uint64_t at = 0;
+  auto take = [&](uint64_t bytes) { const uint64_t p = at; at += (bytes + 7u) & ~7ull; return p; };
+  L.trailer = take(sizeof(DtkSensTrailer)); L.tse = take(L.text_cap * 4);
+  L.tok_end = take(L.sen_cap * 4); L.bstart = take(L.sen_cap * 8); L.bend = take(L.sen_cap * 8);
+  L.rstart = take(L.sen_cap * 8); L.rend = take(L.sen_cap * 8);
+  L.bytes = at;
+  DtkStreamSensArgs a{};
+  a.front = chain.front;
+  a.base = q.base; a.carry_in = q.sen_carry_in; a.carry_out = q.sen_carry_out;
+  const uint64_t words = dtk_streamsens_ws(&a, nullptr), out_words = L.bytes / 8;
+  int rc;
+  if ((rc = o.d_sens_ws.fit(words + 1u, words + words / 8 + 16)) || (rc = o.d_sens_out.fit(out_words, out_words + out_words / 8 + 32)) ||
+      (rc = o.h_sens_out.fit((size_t)L.bytes)))
+    return rc;
+  (void)dtk_streamsens_ws(&a, o.d_sens_ws);
+  uint8_t *d = reinterpret_cast<uint8_t *>(o.d_sens_out.p), *h = o.h_sens_out.as<uint8_t>();
+  a.sen_cap = L.sen_cap; a.text_cap = L.text_cap;
+  a.trailer = reinterpret_cast<DtkSensTrailer *>(d + L.trailer);
+  a.text_sen_end = reinterpret_cast<uint32_t *>(d + L.tse);
+  a.sen_tok_end = reinterpret_cast<uint32_t *>(d + L.tok_end);
+  a.sen_bstart = reinterpret_cast<uint64_t *>(d + L.bstart); a.sen_bend = reinterpret_cast<uint64_t *>(d + L.bend);
+  a.sen_rstart = reinterpret_cast<int64_t *>(d + L.rstart); a.sen_rend = reinterpret_cast<int64_t *>(d + L.rend);
+  if (dtk_launch_streamsens(&a, b->dl_stream, nullptr)) return hip_fail(hipGetLastError(), "slice sentences");
+  // the trailer with text_sen_end behind it, then the five arrays
+  const uint64_t piece[6][2] = {{L.trailer, L.tse + L.text_home * 4},       {L.tok_end, L.tok_end + L.sen_home * 4},
+                                {L.bstart, L.bstart + L.sen_home * 8},      {L.bend, L.bend + L.sen_home * 8},
+                                {L.rstart, L.rstart + L.sen_home * 8},      {L.rend, L.rend + L.sen_home * 8}};
+  for (const auto &p : piece)
+    if (p[1] > p[0]) HIP_TRY(hipMemcpyAsync(h + p[0], d + p[0], (size_t)(p[1] - p[0]), hipMemcpyDeviceToHost, b->dl_stream));
+  o.ss = L;
   return DTK_OK;
 }
 
@@ -146,11 +198,13 @@ bool slice_home(const dtk_batch *b) { return b->dl_begun && b->dl_waited; }
 
 int slice_outputs(dtk_batch *b) {
   const SliceRequest &q = b->slice.req;
-  if (q.bytes == SliceRequest::kNoBytes && !q.offs) return DTK_OK;
+  if (q.bytes == SliceRequest::kNoBytes && !q.offs && !q.sens) return DTK_OK;
   if (b->n_docs != 1 || b->total > 0xFFFFFFFFull) return DTK_E_STATE;
   int rc = DTK_OK;
   if (q.bytes != SliceRequest::kNoBytes) rc = q.bytes == SliceRequest::kPosBytes ? render_slice_pos(b) : render_slice(b);
-  if (rc == DTK_OK && q.offs) rc = slice_offsets(b);
+  DtkStreamOffsArgs chain{};  // (once per slice, whoever wants it)
+  if (rc == DTK_OK && (q.offs || q.sens)) rc = slice_offsets(b, &chain);
+  if (rc == DTK_OK && q.sens) rc = slice_sentences(b, chain);
   return rc;
 }
 
@@ -233,5 +287,42 @@ int batch_offs_out(dtk_batch *b, SoView *v) {
   v->heads = plain ? nullptr : reinterpret_cast<const DtkOffBlock64 *>(h + L.heads);
   v->sent = reinterpret_cast<const int64_t *>(h + L.sent);
   v->ttok = reinterpret_cast<const uint32_t *>(h + L.ttok); v->tsent = reinterpret_cast<const uint32_t *>(h + L.tsent);
+  return DTK_OK;
+}
+
+int batch_sens_out(dtk_batch *b, SsView *v) {
+  SliceOut &o = b->slice;
+  if (!o.req.sens || !slice_home(b) || !o.h_sens_out.p) return DTK_E_STATE;
+  SsLayout &L = o.ss;
+  uint8_t *h = o.h_sens_out.as<uint8_t>();
+  const DtkSensTrailer *t = reinterpret_cast<const DtkSensTrailer *>(h + L.trailer);
+  // (a list longer than its arrays says so with n_tok = ~0; more rows than the bound counts: no regular slice)
+  if (t->n_tok != L.n || t->n_sen > L.sen_cap || t->n_text > L.text_cap || t->firsts > L.n) return DTK_E_CAPACITY;
+  if (t->flags & 1u) return DTK_E_IRREGULAR;
+  // the slice closed more rows or texts than the copies brought: the rest comes now, nothing is computed again
+  const uint8_t *d = reinterpret_cast<const uint8_t *>(o.d_sens_out.p);
+  bool late = false;
+  auto bring = [&](uint64_t at, uint64_t from, uint64_t to, uint64_t size) -> int {
+    HIP_TRY(hipMemcpyAsync(h + at + from * size, d + at + from * size, (size_t)((to - from) * size), hipMemcpyDeviceToHost, b->dl_stream));
+    late = true;
+    return DTK_OK;
+  };
+  int rc;
+  if (t->n_sen > L.sen_home) {
+    if ((rc = bring(L.tok_end, L.sen_home, t->n_sen, 4)) != DTK_OK || (rc = bring(L.bstart, L.sen_home, t->n_sen, 8)) != DTK_OK ||
+        (rc = bring(L.bend, L.sen_home, t->n_sen, 8)) != DTK_OK || (rc = bring(L.rstart, L.sen_home, t->n_sen, 8)) != DTK_OK ||
+        (rc = bring(L.rend, L.sen_home, t->n_sen, 8)) != DTK_OK)
+      return rc;
+    L.sen_home = t->n_sen;
+  }
+  if (t->n_text > L.text_home) {
+    if ((rc = bring(L.tse, L.text_home, t->n_text, 4)) != DTK_OK) return rc;
+    L.text_home = t->n_text;
+  }
+  if (late) HIP_TRY(hipStreamSynchronize(b->dl_stream));
+  v->t = t;
+  v->tok_end = reinterpret_cast<const uint32_t *>(h + L.tok_end); v->tse = reinterpret_cast<const uint32_t *>(h + L.tse);
+  v->bstart = reinterpret_cast<const uint64_t *>(h + L.bstart); v->bend = reinterpret_cast<const uint64_t *>(h + L.bend);
+  v->rstart = reinterpret_cast<const int64_t *>(h + L.rstart); v->rend = reinterpret_cast<const int64_t *>(h + L.rend);
   return DTK_OK;
 }

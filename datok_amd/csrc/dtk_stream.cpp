@@ -98,7 +98,8 @@ extern "C" int dtk_stream_transduce(dtk_stream *s, const dtk_model *m, dtk_read_
   if (!s || !m || !read_fn || !out) return DTK_E_ARG;
   *out = nullptr;
   const bool positions = (bits & (DTK_TOKEN_POS | DTK_SENTENCE_POS)) != 0;
-  (void)dtk_stream_set_offsets(s, 0, 0);  // (bytes are asked for: offset delivery is off for this run and stays off)
+  (void)dtk_stream_set_offsets(s, 0, 0);  // (bytes are asked for: offset delivery is off for this run and stays off,
+  (void)dtk_stream_set_sentences(s, 0);   //  and so are the sentence rows)
   int rc = positions ? dtk_stream_set_position_render(s, 1, bits)
                      : dtk_stream_set_render(s, 1, bits & (uint32_t)(DTK_TOKENS | DTK_SENTENCES));
   if (rc != DTK_OK) return rc;

@@ -31,6 +31,11 @@ struct dtk_stream {
   // exclusive with position rendering.
   bool offs = false;
   uint32_t offs_form = DTK_SO_PLAIN;
+  // dtk_stream_set_sentences: the sentences as rows, beside set_render's bytes, beside the offsets or alone; exclusive
+  // with position rendering like the offsets.  The row that is open at a cut is chained like the writer's state, in
+  // slots of its own with the same rule.
+  bool sens = false;
+  DevArray<DtkSenCarry> d_sen_carry;  // depth + 1
   // Position rendering and offset delivery follow the writer's state, which is chained on the device: slice k reads
   // carry slot k % (depth + 1) and writes the next one -- never the slot it read, and a slot is written again only by
   // slice k + depth, which takes the batch that slice k has left by then.
@@ -45,6 +50,8 @@ struct dtk_stream {
     bool emitted = false;
     bool offs_set = false;                // offset delivery: offs is this slice's
     SoView offs{};
+    bool sens_set = false;                // the sentence rows: sens is this slice's
+    SsView sens{};
   } cur;
   Stream s_up, s_run, s_down;
   std::vector<dtk_batch *> slots;
@@ -66,7 +73,8 @@ extern "C" int dtk_stream_create(uint64_t slice_bytes, uint32_t depth, dtk_strea
   s->depth = depth;
   int rc;
   if ((rc = s->s_up.create()) || (rc = s->s_run.create()) || (rc = s->s_down.create()) ||
-      (rc = s->d_carry.fit((uint64_t)depth + 1u, (uint64_t)depth + 1u)))
+      (rc = s->d_carry.fit((uint64_t)depth + 1u, (uint64_t)depth + 1u)) ||
+      (rc = s->d_sen_carry.fit((uint64_t)depth + 1u, (uint64_t)depth + 1u)))
     return rc;
   for (uint32_t i = 0; i < depth; i++) {
     dtk_batch *b = nullptr;
@@ -101,7 +109,8 @@ extern "C" int dtk_stream_set_result_fields(dtk_stream *s, uint32_t fields) {
   if (!s || !(fields & (DTK_R_TOK_BYTE | DTK_R_TOK_BYTE_BLK))) return DTK_E_ARG;
   // (the rune fields of a slice's view would be the compaction's: the window as a fresh document.  The stream's rune
   //  offsets and sentence list come from dtk_stream_set_offsets, computed from the writer's carried state.)
-  // (nor the sentence table: a sentence can span a cut)
+  // (nor the batch's sentence table, which ends with the window: a stream's rows come from dtk_stream_set_sentences,
+  //  with the open row carried across the cuts)
   if (fields & (DTK_R_TOK_RUNE | DTK_R_TOK_RUNE16 | DTK_R_TOK_RUNE_BLK | DTK_R_SENT | DTK_R_EAGER | DTK_R_SENTENCES)) return DTK_E_ARG;
   fields |= kForced;
   for (dtk_batch *b : s->slots) {
@@ -128,7 +137,7 @@ extern "C" int dtk_stream_set_position_render(dtk_stream *s, int on, uint32_t bi
   const uint32_t all = DTK_TOKENS | DTK_SENTENCES | DTK_TOKEN_POS | DTK_SENTENCE_POS | DTK_NEWLINE_AFTER_EOT;
   if (!s || (bits & ~all)) return DTK_E_ARG;
   if (on && !(bits & (uint32_t)(DTK_TOKEN_POS | DTK_SENTENCE_POS))) return DTK_E_ARG;  // those modes are dtk_stream_set_render's
-  if (on && s->offs) return DTK_E_ARG;  // (the offsets as digits or as arrays, not both)
+  if (on && (s->offs || s->sens)) return DTK_E_ARG;  // (the offsets as digits or as arrays, not both; the rows read the arrays' chain)
   if (on) {  // (plain rendering, if it was on, is off)
     s->bytes = SliceRequest::kPosBytes;
     s->bits = bits;
@@ -146,6 +155,13 @@ extern "C" int dtk_stream_set_offsets(dtk_stream *s, int on, uint32_t form) {
   return DTK_OK;
 }
 
+extern "C" int dtk_stream_set_sentences(dtk_stream *s, int on) {
+  if (!s) return DTK_E_ARG;
+  if (on && s->bytes == SliceRequest::kPosBytes) return DTK_E_ARG;
+  s->sens = on != 0;
+  return DTK_OK;
+}
+
 static dtk_stream_carry carry_of(const DtkPosCarry &c) {
   return dtk_stream_carry{c.posC, c.sentB, c.init, c.pos_nonempty, c.sent_nonempty};
 }
@@ -160,6 +176,23 @@ extern "C" int dtk_stream_offsets(dtk_stream *s, dtk_stream_offs *o) {
   o->tok_rblk = v.words; o->tok_rblk_head = reinterpret_cast<const dtk_off_block64 *>(v.heads);
   o->sent = v.sent; o->text_tok_end = v.ttok; o->text_sent_end = v.tsent;
   o->carry_in = carry_of(v.t->carry_in); o->carry_out = carry_of(v.t->carry_out);
+  return DTK_OK;
+}
+
+static dtk_stream_sen_carry sen_carry_of(const DtkSenCarry &c) {
+  return dtk_stream_sen_carry{c.open, 0u, c.bstart, c.bend, c.rstart, c.rend};
+}
+
+extern "C" int dtk_stream_sentences(dtk_stream *s, dtk_stream_sens *o) {
+  if (!s || !o) return DTK_E_ARG;
+  if (!s->cur.sens_set) return DTK_E_STATE;
+  const SsView &v = s->cur.sens;
+  static_assert(sizeof(dtk_stream_sen_carry) == sizeof(DtkSenCarry) && sizeof(dtk_stream_sen_carry) == 40, "the kernels' carry is the header's");
+  o->n_sen = v.t->n_sen; o->n_text = v.t->n_text;
+  o->sen_tok_end = v.tok_end;
+  o->sen_bstart = v.bstart; o->sen_bend = v.bend; o->sen_rstart = v.rstart; o->sen_rend = v.rend;
+  o->text_sen_end = v.tse;
+  o->carry_in = sen_carry_of(v.t->carry_in); o->carry_out = sen_carry_of(v.t->carry_out);
   return DTK_OK;
 }
 
@@ -247,6 +280,7 @@ struct Run {
 
   uint8_t *bytes(uint32_t slot) { return s->buf[slot]->as<uint8_t>(); }
   bool pos_render() const { return s->bytes == SliceRequest::kPosBytes; }
+  bool writer_chain() const { return pos_render() || s->offs || s->sens; }  // the writer's state is chained on the device
 
   // window k into its slot: the tail of window k - 1 (null: the stream's beginning), then fresh bytes.  Returns the
   // fresh bytes read.
@@ -300,9 +334,11 @@ struct Run {
       q.digits = 2;  // ("-1")
       for (uint64_t v = x.base + cut - te_from + posc0; v >= 10u; v /= 10u) q.digits++;
     }
-    if (pos_render() || s->offs) {
+    q.sens = s->sens; q.base = x.base;
+    if (writer_chain()) {
       const uint64_t slots = (uint64_t)s->depth + 1u, slot = x.k % slots;
       q.carry_in = s->d_carry + slot; q.carry_out = s->d_carry + (slot + 1u) % slots;
+      if (s->sens) { q.sen_carry_in = s->d_sen_carry + slot; q.sen_carry_out = s->d_sen_carry + (slot + 1u) % slots; }
     }
     batch_set_slice_request(b, q);
     return dtk_batch_download_begin(b);
@@ -340,6 +376,10 @@ struct Run {
       if ((rc = batch_offs_out(b, &s->cur.offs)) != DTK_OK) return rc;
       s->cur.offs_set = true;
     }
+    if (s->sens) {
+      if ((rc = batch_sens_out(b, &s->cur.sens)) != DTK_OK) return rc;
+      s->cur.sens_set = true;
+    }
     rc = slice_fn ? slice_fn(slice_user, &sl) : DTK_OK;
     s->cur = {};
     return rc;
@@ -361,11 +401,13 @@ extern "C" int dtk_stream_run(dtk_stream *s, const dtk_model *m, dtk_read_fn rea
   s->cur = {};
   r.is_matrix = std::strcmp(dtk_model_type(m), "MATOK") == 0;
   r.nl = (flags & DTK_NEWLINE_AFTER_EOT) != 0;
-  if (r.pos_render() || s->offs) {
+  if (r.writer_chain()) {
     // a new writer: {posC 0, sentB, init} (token_writer.go:38-42) in slot 0 of the chain
     const DtkPosCarry c0{g_dbg.sp_posc0, 1u, 1u, 0u, 0u};
     if (r.pos_render()) r.posc0 = (uint64_t)(c0.posC < 0 ? -c0.posC : c0.posC);
     HIP_TRY(hipMemcpy(s->d_carry.p, &c0, sizeof(c0), hipMemcpyHostToDevice));
+    const DtkSenCarry s0{};  // no row is open
+    if (s->sens) HIP_TRY(hipMemcpy(s->d_sen_carry.p, &s0, sizeof(s0), hipMemcpyHostToDevice));
   }
   // (the writer's rune offsets are the host's: the compaction writes the byte offsets only)
   const uint32_t run_flags = DTK_NO_RUNE_OFFSETS;

@@ -241,14 +241,20 @@ class SliceView:
     arrays (dtk_stream_offsets; None when it is off): r_tok_rstart / r_tok_rend (int64, decoded from whichever form
     came; r_blocked says whether that was the blocked one, r_rblk / r_rblk_head are its words and heads), r_sent (int64),
     r_text_tok_end / r_text_sent_end (tokens / sent ints of THIS slice in front of each TextEnd), r_carry_in /
-    r_carry_out (the writer's state as above)."""
+    r_carry_out (the writer's state as above).
+    With Stream.set_sentences the slice brings the sentences its calls close, as rows (dtk_stream_sentences; None when
+    it is off): s_tok_end (uint32: tokens of THIS slice up to and including the row's last), s_bstart / s_bend (uint64,
+    stream byte offsets), s_rstart / s_rend (int64, the writer's rune offsets), s_text_sen_end (rows of THIS slice closed
+    in front of each TextEnd), s_carry_in / s_carry_out (the row open at the cut: (open, bstart, bend, rstart, rend))."""
     __slots__ = ("base", "first", "cut", "text", "last", "status", "tok_bstart", "tok_bend", "evl_pos", "evl_kind", "tail",
                  "out", "splice_pos", "splice_sent", "open_pos", "open_sent", "carry_in", "carry_out", "written",
                  "r_tok_rstart", "r_tok_rend", "r_blocked", "r_rblk", "r_rblk_head", "r_sent", "r_text_tok_end",
-                 "r_text_sent_end", "r_carry_in", "r_carry_out")
+                 "r_text_sent_end", "r_carry_in", "r_carry_out",
+                 "s_tok_end", "s_bstart", "s_bend", "s_rstart", "s_rend", "s_text_sen_end", "s_carry_in", "s_carry_out")
     _NONE = ("out", "splice_pos", "splice_sent", "open_pos", "open_sent", "carry_in", "carry_out", "written",
              "r_tok_rstart", "r_tok_rend", "r_blocked", "r_rblk", "r_rblk_head", "r_sent", "r_text_tok_end",
-             "r_text_sent_end", "r_carry_in", "r_carry_out")
+             "r_text_sent_end", "r_carry_in", "r_carry_out",
+             "s_tok_end", "s_bstart", "s_bend", "s_rstart", "s_rend", "s_text_sen_end", "s_carry_in", "s_carry_out")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -814,6 +820,13 @@ class Stream:
         check(lib().dtk_stream_set_offsets(self._h, 0 if form is None else 1, 0 if form is None else int(form)),
               "dtk_stream_set_offsets")
 
+    def set_sentences(self, on):
+        """Every SliceView brings the sentences its calls close as rows (s_tok_end, s_bstart, s_bend, s_rstart, s_rend,
+        s_text_sen_end, s_carry_in, s_carry_out): the batch's sentence table for the stream as one document, the open
+        row carried from slice to slice on the device.  Works alone (then the r_* fields stay None), beside set_offsets
+        and beside set_render; E_ARG while set_position_render is on."""
+        check(lib().dtk_stream_set_sentences(self._h, 1 if on else 0), "dtk_stream_set_sentences")
+
     def set_position_render(self, bits):
         """The same in a mode with TOKEN_POS or SENTENCE_POS (any of the five writer bits with one of the two): the
         writer's state is carried from slice to slice on the device, and every SliceView brings out, splice_pos,
@@ -927,6 +940,27 @@ def _slice_offsets(h) -> dict:
                 r_text_sent_end=arr(so.text_sent_end, nx, np.uint32), r_carry_in=carry(so.carry_in), r_carry_out=carry(so.carry_out))
 
 
+def _slice_sentences(h) -> dict:
+    """What dtk_stream_sentences says about the slice being delivered ({}: the sentence rows are off)."""
+    ss = _lib.StreamSens()
+    if not h or lib().dtk_stream_sentences(h, C.byref(ss)) != _lib.OK:
+        return {}
+
+    def arr(ptr, n, dt):
+        dt = np.dtype(dt)
+        if n == 0 or not ptr:
+            return np.zeros(0, dt)
+        return np.frombuffer((C.c_char * (n * dt.itemsize)).from_address(ptr), dtype=dt).copy()
+
+    def carry(c):
+        return (bool(c.open), int(c.bstart), int(c.bend), int(c.rstart), int(c.rend))
+    n, nx = int(ss.n_sen), int(ss.n_text)
+    return dict(s_tok_end=arr(ss.sen_tok_end, n, np.uint32), s_bstart=arr(ss.sen_bstart, n, np.uint64),
+                s_bend=arr(ss.sen_bend, n, np.uint64), s_rstart=arr(ss.sen_rstart, n, np.int64),
+                s_rend=arr(ss.sen_rend, n, np.int64), s_text_sen_end=arr(ss.text_sen_end, nx, np.uint32),
+                s_carry_in=carry(ss.carry_in), s_carry_out=carry(ss.carry_out))
+
+
 def _slice_view(s, stream=None) -> SliceView:
     """Host copies of a dtk_stream_slice (its buffers are only valid inside the callback)."""
     v = s.view
@@ -948,7 +982,7 @@ def _slice_view(s, stream=None) -> SliceView:
                      tok_bstart=bs, tok_bend=be, evl_pos=arr(v.evl_pos, ne, np.uint32)[int(off[0]):],
                      evl_kind=arr(v.evl_kind, ne, np.uint8)[int(off[0]):], tail=int(arr(v.doc_tail, 1, np.uint32)[0]),
                      out=C.string_at(s.out, int(s.out_len)) if s.out else None, **_slice_positions(stream),
-                     **_slice_offsets(stream))
+                     **_slice_offsets(stream), **_slice_sentences(stream))
 
 
 def _slice_callback(on_slice, doc_off, err):

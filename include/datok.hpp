@@ -462,6 +462,40 @@ class GpuTokenizer final : public Tokenizer {
     return rc == DTK_OK &&
            !(last_status_ & (DTK_ST_WINDOW_OVERFLOW | DTK_ST_BAD_MODEL | DTK_ST_STEP_LIMIT | DTK_ST_INTERNAL | DTK_ST_IRREGULAR));
   }
+  // The sentences of a reader of any length as rows, for a caller that wants sentence spans and no token offsets:
+  // cb(const dtk_stream_slice &, const dtk_stream_sens &) gets the rows every slice's calls close, in order
+  // (dtk_stream_set_sentences: the slices' rows one behind the other are the stream's table; the row open at a cut is
+  // carried on the device); they are valid inside the call.  newline_after_eot moves the rune spans as it moves the
+  // writer's offsets.  A non-zero return of cb ends the run.  No closure is called, no text is rendered and no token
+  // offsets come home.
+  template <class Callback>
+  bool TransduceStreamSentences(std::istream &r, Callback &&cb, bool newline_after_eot = false,
+                                uint64_t slice_bytes = 16u << 20, uint32_t depth = 3) {
+    last_status_ = 0;
+    dtk_stream *s = nullptr;
+    if (dtk_stream_create(slice_bytes, depth, &s) != DTK_OK) return false;
+    int rc = dtk_stream_set_sentences(s, 1);
+    if (rc == DTK_OK) rc = dtk_stream_set_result_fields(s, DTK_R_TOK_BYTE_BLK);
+    if (rc == DTK_OK) {
+      struct Ctx { std::istream *r; dtk_stream *s; typename std::remove_reference<Callback>::type *cb; } c{&r, s, &cb};
+      auto rd = [](void *u, uint8_t *buf, size_t cap) -> size_t {
+        Ctx *c = static_cast<Ctx *>(u);
+        c->r->read(reinterpret_cast<char *>(buf), (std::streamsize)cap);
+        return (size_t)c->r->gcount();
+      };
+      auto on_slice = [](void *u, const dtk_stream_slice *sl) -> int {
+        Ctx *c = static_cast<Ctx *>(u);
+        dtk_stream_sens o;
+        const int rc = dtk_stream_sentences(c->s, &o);
+        return rc != DTK_OK ? rc : (int)(*c->cb)(*sl, o);
+      };
+      rc = dtk_stream_run(s, m_, rd, &c, newline_after_eot ? (uint32_t)DTK_NEWLINE_AFTER_EOT : 0u, on_slice, &c, &last_status_);
+    }
+    dtk_stream_free(s);
+    last_status_ &= ~(uint32_t)DTK_ST_EMPTY_TEXT;  // (an empty text only breaks the position modes: it makes no row)
+    return rc == DTK_OK &&
+           !(last_status_ & (DTK_ST_WINDOW_OVERFLOW | DTK_ST_BAD_MODEL | DTK_ST_STEP_LIMIT | DTK_ST_INTERNAL | DTK_ST_IRREGULAR));
+  }
   // ... on a dtk_stream the caller keeps (and has configured); returns dtk_stream_run's code
   int RunStream(dtk_stream *s, std::istream &r, TokenWriter &w) {
     struct Ctx { std::istream *r; TokenWriter *w; bool is_matrix; } c{&r, &w, Type() == "MATOK"};

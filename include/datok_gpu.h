@@ -500,7 +500,8 @@ int dtk_pipeline_run(dtk_pipeline *p, const dtk_model *m, const uint8_t *text, c
  *      sentence list run across cuts (posC, sentB, init of token_writer.go:38-42): tok_rstart / tok_rend / sent of a
  *      slice's view -- the compaction's view of the window as a fresh document -- are not delivered, and
  *      dtk_stream_set_result_fields rejects the rune fields; the stream's offsets come as arrays of their own, 64-bit
- *      and computed on the device from the carried state (dtk_stream_set_offsets, dtk_stream_offsets).  The device renders a slice's writer bytes in every mode (`out` / `out_len`): in the four
+ *      and computed on the device from the carried state (dtk_stream_set_offsets, dtk_stream_offsets), and its sentences
+ *      as rows with the open row carried across the cuts (dtk_stream_set_sentences, dtk_stream_sentences).  The device renders a slice's writer bytes in every mode (`out` / `out_len`): in the four
  *      position-free modes (TOKENS, SENTENCES, both, neither; NEWLINE_AFTER_EOT changes nothing there) the writer is
  *      stateless (dtk_stream_set_render); with TOKEN_POS or SENTENCE_POS its state is carried from slice to slice on
  *      the device (dtk_stream_set_position_render, dtk_stream_emit).  A custom TokenWriter's closures are fed by the
@@ -532,7 +533,7 @@ int dtk_stream_set_chunking(dtk_stream *s, uint32_t chunk_bytes, uint32_t warm_b
  * the token bytes must be among them as DTK_R_TOK_BYTE or DTK_R_TOK_BYTE_BLK (else DTK_E_ARG).  Default: DTK_R_TOK_BYTE.
  * The rune fields (DTK_R_TOK_RUNE*, DTK_R_SENT) are DTK_E_ARG: a slice's view is the compaction's fresh-document view,
  * and the way to the stream's rune offsets and sentence list is dtk_stream_set_offsets.  DTK_R_SENTENCES is DTK_E_ARG
- * too: a sentence can span a cut. */
+ * too: a sentence can span a cut, and the stream's rows come from dtk_stream_set_sentences, which carries the open one. */
 int dtk_stream_set_result_fields(dtk_stream *s, uint32_t fields);
 /* on != 0: every slice also brings the bytes a stock NewTokenWriter(w, bits) writes for its calls, rendered on the device
  * behind the slice's event list and in front of its copies (about one more byte per input byte on the link); the
@@ -624,6 +625,43 @@ typedef struct {
 /* Inside slice_fn, with offset delivery on: the slice being delivered (else DTK_E_STATE).  Page-locked host memory,
  * valid until slice_fn returns. */
 int dtk_stream_offsets(dtk_stream *s, dtk_stream_offs *o);
+/* ---- a stream's sentences as rows: what the batch path hands out with DTK_R_SENTENCES (dtk_sentence_view), for ONE
+ *      stream of any length, slice by slice.
+ * The definition is the batch's, with the stream as one document: scan the reference's calls for the whole stream in
+ * order; a sentence is a maximal non-empty run of Token calls with no SentenceEnd or TextEnd between them; a SentenceEnd,
+ * a TextEnd or the end of the calls closes an open run; a boundary with no token since the previous one makes no row;
+ * every token belongs to exactly one row.
+ *   A row is delivered by the slice whose calls close it -- by a SentenceEnd or TextEnd call of that slice, on the last
+ * slice also by the end of the calls behind the tail word's.  So every row arrives exactly once, complete and in order,
+ * and the slices' rows one behind the other are the stream's table; a row whose tokens all lie in earlier slices still
+ * arrives, with no token of the delivering slice (sen_tok_end 0).  What crosses a cut is the open row
+ * (dtk_stream_sen_carry), chained on the device between slices like the writer's state; it starts as all-zero with
+ * every run.
+ *   on != 0: every slice also brings its rows, computed on the device behind the offsets chain of the slice (the rune
+ * spans are the writer's offsets, as dtk_stream_offs delivers them, and DTK_NEWLINE_AFTER_EOT in dtk_stream_run's flags
+ * moves them alike).  May be on alone -- then only the rows come home, some 36 B per sentence, and dtk_stream_offsets
+ * answers DTK_E_STATE --, beside dtk_stream_set_offsets and beside dtk_stream_set_render; with
+ * dtk_stream_set_position_render it is exclusive: turning either on while the other is on is DTK_E_ARG and changes
+ * nothing.  dtk_stream_transduce turns it off.  DTK_E_IRREGULAR and DTK_E_CAPACITY end the run where offset delivery
+ * gives them. ---- */
+int dtk_stream_set_sentences(dtk_stream *s, int on);
+typedef struct {
+  uint32_t open, reserved;     /* a sentence is open at the cut (== !sentB of the writer's carry) */
+  uint64_t bstart, bend;       /* stream byte offsets: start of its first token, end of its last so far */
+  int64_t  rstart, rend;       /* the writer's rune offsets of the same two (text-relative, 64-bit like dtk_stream_offs) */
+} dtk_stream_sen_carry;
+typedef struct {
+  uint64_t n_sen, n_text;                 /* rows closed by THIS slice's calls; TextEnd calls of this slice */
+  const uint32_t *sen_tok_end;            /* tokens of THIS slice up to and including row i's last; 0 for a carried row that
+                                             gets no token here; rebased by the running token count it is the stream's */
+  const uint64_t *sen_bstart, *sen_bend;  /* stream byte offsets (slice base + window offset), first token's start / last token's end */
+  const int64_t  *sen_rstart, *sen_rend;  /* tok_rstart of the first, tok_rend of the last, as dtk_stream_offs delivers them */
+  const uint32_t *text_sen_end;           /* n_text: rows of THIS slice closed in front of the g-th TextEnd (a TextEnd closes the open row first) */
+  dtk_stream_sen_carry carry_in, carry_out;
+} dtk_stream_sens;
+/* Inside slice_fn, with the sentence rows on: the slice being delivered (else DTK_E_STATE).  Page-locked host memory,
+ * valid until slice_fn returns. */
+int dtk_stream_sentences(dtk_stream *s, dtk_stream_sens *o);
 /* flags: DTK_NEWLINE_AFTER_EOT is accepted and changes nothing here (it only moves the writer's rune offsets), except
  * that with position rendering on it must be the bit dtk_stream_set_position_render got.  Short
  * reads are retried until a buffer is full; read_fn is not called again after it has returned 0. */

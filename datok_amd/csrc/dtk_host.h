@@ -10,6 +10,7 @@
 #include "../../include/datok_gpu.h"
 #include "dtk_internal.h"
 #include "dtk_own.h"  // the error state (hip_fail, HIP_TRY) and the owning types
+#include "dtk_mirror.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -111,38 +112,33 @@ struct SliceRequest {
   const DtkPosCarry *carry_in = nullptr;
   DtkPosCarry *carry_out = nullptr;
 };
-// The offsets' device block and its page-locked copy have one layout (byte offsets, fixed before anything is enqueued):
-// tok_rstart | tok_rend | sent | trailer | text_tok_end | text_sent_end | heads | words.  The copies bring the plain or
-// the blocked offsets, sent and the text rows as far as the compaction's counts reach, and the trailer; what the
-// trailer then asks for beyond that (blk_fail: the plain offsets; more sent ints or rows) is copied at delivery.
-struct SoLayout {
-  uint64_t n = 0, sent_cap = 0, text_cap = 0;  // the capacities: tokens (exact), sent ints, texts
-  uint64_t sent_home = 0, text_home = 0;       // sent ints / text rows the page-locked copy holds
-  uint64_t rstart = 0, rend = 0, sent = 0, trailer = 0, ttok = 0, tsent = 0, heads = 0, words = 0, bytes = 0;
-  bool blocked = false, wide_home = false;     // wide_home: tok_rstart / tok_rend are in the page-locked copy
-};
-// The sentence rows' device block and its page-locked copy, in the same way: trailer | text_sen_end | sen_tok_end |
-// sen_bstart | sen_bend | sen_rstart | sen_rend.  The copies bring the trailer, the text rows and the five arrays as far
-// as the compaction's counts reach; what the trailer counts beyond that is copied at delivery.
-struct SsLayout {
-  uint64_t n = 0, sen_cap = 0, text_cap = 0;   // the capacities: tokens (exact), rows, texts
-  uint64_t sen_home = 0, text_home = 0;        // rows / text rows the page-locked copy holds
-  uint64_t trailer = 0, tse = 0, tok_end = 0, bstart = 0, bend = 0, rstart = 0, rend = 0, bytes = 0;
-};
+// What comes home lies in blocks of dtk_mirror.h, described anew for every slice (dtk_slice.cpp): each piece below is
+// both a device array the kernels write and its page-locked copy.  The first copies bring a piece as far as the
+// compaction's counts reach, and the trailer; what the trailer then asks for beyond that (blk_fail: the plain offsets;
+// more sent ints or rows) is copied at delivery -- the pieces' home counts say what is there.
 struct SliceOut {
   SliceRequest req;
-  // the bytes: d_out (cap bytes, then the length word or the trailer block) and its page-locked copy, both sized
-  // before anything is enqueued
-  uint64_t cap = 0;             // of the rendering under way
-  DevArray<uint8_t> d_out;
-  DevArray<uint64_t> d_ws;      // the renderer's workspace (tile sums and scans)
-  PinBuf h_out;
-  SoLayout so;
-  DevArray<uint64_t> d_offs_ws, d_offs_out;
-  PinBuf h_offs_out;
-  SsLayout ss;
-  DevArray<uint64_t> d_sens_ws, d_sens_out;
-  PinBuf h_sens_out;
+  DevArray<uint64_t> d_ws, d_offs_ws, d_sens_ws;  // the units' workspaces (tile sums and scans)
+  struct Bytes : MirrorBlock {  // the rendering under way: the bytes, then the length word (kPlainBytes) or the trailer (kPosBytes)
+    Piece<uint8_t> out;
+    Piece<uint64_t> len;
+    Piece<DtkPosTrailer> trailer;
+  } bytes;
+  struct Offs : MirrorBlock {
+    Piece<int64_t> rstart, rend, sent;  // tokens (exact), tokens, sent ints
+    Piece<DtkOffsTrailer> trailer;
+    Piece<uint32_t> ttok, tsent;        // texts
+    Piece<DtkOffBlock64> heads;         // the blocked form, else empty
+    Piece<uint32_t> words;
+    bool blocked = false;
+  } offs;
+  struct Sens : MirrorBlock {
+    Piece<DtkSensTrailer> trailer;
+    Piece<uint32_t> tse, tok_end;       // texts, rows
+    Piece<uint64_t> bstart, bend;       // rows
+    Piece<int64_t> rstart, rend;
+    uint64_t n = 0;                     // the slice's tokens
+  } sens;
 };
 
 // -------------------------------------------------------------------- batch
@@ -267,16 +263,18 @@ struct dtk_batch {
   uint64_t evl_copied = 0;         // rows the last enqueued copies of the list hold
   uint64_t evl_need = 0;           // nonzero: this run's list has that many rows, more than the bound (dtk_batch_result_host saw it)
   bool evl_pending = false;        // a list is on its way whose count nobody has looked at yet
-  // DTK_R_SENTENCES / dtk_batch_sentences_*: the sentence table (dtk_sentences.hip), built on the download stream.  One
-  // device block and one page-locked block of the same layout (SenLayout): sen_off | sen_tok_end | sen_bstart | sen_bend |
-  // sen_rstart | sen_rend | text_sen_end | the count word -- one copy brings all of it.  Sized for n_sent rows; the count
-  // word says whether that was enough (sen_need), as with the event list.
-  struct SenLayout { uint64_t rows = 0, texts = 0, tok_end = 0, bstart = 0, bend = 0, rstart = 0, rend = 0, tse = 0, cnt = 0, bytes = 0; } sen;
-  DevArray<uint64_t> d_sen;        // the block (64-bit words)
+  // DTK_R_SENTENCES / dtk_batch_sentences_*: the sentence table (dtk_sentences.hip), built on the download stream into
+  // one block of dtk_mirror.h -- one copy brings all of it.  Sized for n_sent rows; the count word says whether that
+  // was enough (sen_need), as with the event list.
+  struct Sen : MirrorBlock {
+    Piece<uint64_t> off;                   // documents + 1
+    Piece<uint32_t> tok_end, bstart, bend; // rows
+    Piece<int32_t> rstart, rend;
+    Piece<uint32_t> tse, cnt;              // texts; the count word
+  } sen;
   DevArray<uint32_t> d_sen_ws;     // device only: a row's bit | document | first token, and the tiles' two words
-  PinBuf h_sen;
   Event ev_sen;                    // behind the table's kernels and its last enqueued copy
-  bool sen_built = false;          // the kernels have been enqueued for this run, for sen.rows rows
+  bool sen_built = false;          // the kernels have been enqueued for this run, for cap(sen.tok_end) rows
   bool sen_home = false;           // ... and the copy of the whole block (else at most the count word's)
   bool sen_waited = true;          // ev_sen has been waited for: what was enqueued is there
   bool sen_done = false;           // the count has been looked at and fits (and exact documents are spliced in)

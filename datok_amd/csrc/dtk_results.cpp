@@ -126,33 +126,24 @@ int pack_event_list(dtk_batch *b, uint64_t rows) {
 
 // ---- DTK_R_SENTENCES: the sentence table (dtk_sentences.hip; the definition is in include/datok_gpu.h)
 
-// Where the arrays lie in the device block and in its page-locked copy, for `rows` rows and `texts` text rows.
-dtk_batch::SenLayout sen_layout(uint64_t n_docs, uint64_t rows, uint64_t texts) {
-  dtk_batch::SenLayout L;
-  L.rows = rows; L.texts = texts;
-  uint64_t q = (n_docs + 1) * 8;  // sen_off
-  L.tok_end = q; q += rows * 4;
-  L.bstart = q; q += rows * 4;
-  L.bend = q; q += rows * 4;
-  L.rstart = q; q += rows * 4;
-  L.rend = q; q += rows * 4;
-  L.tse = q; q += texts * 4;
-  L.cnt = q; q += 4;
-  L.bytes = (q + 7) & ~(uint64_t)7;
-  return L;
+// The table's block and its page-locked copy, for `rows` rows and `texts` text rows: both with room for it.
+int sen_describe(dtk_batch *b, uint64_t rows, uint64_t texts) {
+  dtk_batch::Sen &L = b->sen;
+  L.clear();
+  L.add(L.off, (uint64_t)b->n_docs + 1);
+  L.add(L.tok_end, rows); L.add(L.bstart, rows); L.add(L.bend, rows); L.add(L.rstart, rows); L.add(L.rend, rows);
+  L.add(L.tse, texts); L.add(L.cnt, 1);
+  return L.fit();
 }
 
-void sen_view(const dtk_batch *b, const uint8_t *base, dtk_sentence_view *o) {
-  const dtk_batch::SenLayout &L = b->sen;
+void sen_view(const dtk_batch *b, void *block, dtk_sentence_view *o) {  // block: sen.d or sen.h
+  const dtk_batch::Sen &L = b->sen;
   const bool runes = !(b->last_flags & DTK_NO_RUNE_OFFSETS);
   o->n_sen = b->sen_n;
-  o->sen_off = (const uint64_t *)base;
-  o->sen_tok_end = (const uint32_t *)(base + L.tok_end);
-  o->sen_bstart = (const uint32_t *)(base + L.bstart);
-  o->sen_bend = (const uint32_t *)(base + L.bend);
-  o->sen_rstart = runes ? (const int32_t *)(base + L.rstart) : nullptr;
-  o->sen_rend = runes ? (const int32_t *)(base + L.rend) : nullptr;
-  o->text_sen_end = (const uint32_t *)(base + L.tse);
+  o->sen_off = L.in(block, L.off);
+  o->sen_tok_end = L.in(block, L.tok_end); o->sen_bstart = L.in(block, L.bstart); o->sen_bend = L.in(block, L.bend);
+  o->sen_rstart = runes ? L.in(block, L.rstart) : nullptr; o->sen_rend = runes ? L.in(block, L.rend) : nullptr;
+  o->text_sen_end = L.in(block, L.tse);
 }
 
 // Enqueues on the download stream what is still missing of: the table's kernels, and the copy of the whole block
@@ -168,38 +159,31 @@ int sen_enqueue(dtk_batch *b, bool home) {
   if (!dtk_batch_download_stream(b)) return hip_fail(hipGetLastError(), "download stream");
   int rc;
   if (b->sen_done && (b->sen_home || !home)) return DTK_OK;  // nothing is missing
-  if (!b->sen_built || (!b->sen_done && rows > b->sen.rows)) {
-    const dtk_batch::SenLayout L = sen_layout(b->n_docs, rows, b->totals.n_texts);
+  dtk_batch::Sen &L = b->sen;
+  if (!b->sen_built || (!b->sen_done && rows > L.cap(L.tok_end))) {
     const uint32_t tiles = dtk_sentences_tiles(n_bits, b->bit_words);
     const uint64_t ws = 3 * rows + 2 * (uint64_t)tiles;
-    if ((rc = b->d_sen.fit(L.bytes / 8, L.bytes / 8 + L.bytes / 64)) || (rc = b->d_sen_ws.fit(ws, ws + ws / 8)) ||
-        (rc = b->h_sen.fit((size_t)L.bytes)))
-      return rc;
-    b->sen = L;
-    uint8_t *base = (uint8_t *)b->d_sen.p;
+    if ((rc = sen_describe(b, rows, b->totals.n_texts)) || (rc = b->d_sen_ws.fit(ws, ws + ws / 8))) return rc;
     DtkSentencesArgs a{};
     a.bits = b->d_bits; a.bit_words = b->bit_words; a.n_docs = b->n_docs; a.doc_off = b->d_off; a.n_bits = n_bits;
     a.n_tiles = tiles; a.cap = (uint32_t)rows;
     a.tok_off = b->d_tok_off; a.text_off = b->d_text_off; a.tok_bstart = b->d_bstart; a.tok_bend = b->d_bend;
     if (!(b->last_flags & DTK_NO_RUNE_OFFSETS)) { a.tok_rstart = b->d_rstart; a.tok_rend = b->d_rend; }
     a.text_tok_end = b->d_ttok;
-    a.text_cap = L.texts;
+    a.text_cap = L.cap(L.tse);
     a.sen_bit = b->d_sen_ws; a.sen_doc = a.sen_bit + rows; a.sen_first = a.sen_doc + rows;
     a.tile_base = a.sen_first + rows; a.tile_in = a.tile_base + tiles;
-    a.count = (uint32_t *)(base + L.cnt);
-    a.sen_off = (uint64_t *)base;
-    a.sen_tok_end = (uint32_t *)(base + L.tok_end); a.sen_bstart = (uint32_t *)(base + L.bstart);
-    a.sen_bend = (uint32_t *)(base + L.bend); a.sen_rstart = (int32_t *)(base + L.rstart);
-    a.sen_rend = (int32_t *)(base + L.rend); a.text_sen_end = (uint32_t *)(base + L.tse);
+    a.count = L.dev(L.cnt); a.sen_off = L.dev(L.off);
+    a.sen_tok_end = L.dev(L.tok_end); a.sen_bstart = L.dev(L.bstart); a.sen_bend = L.dev(L.bend);
+    a.sen_rstart = L.dev(L.rstart); a.sen_rend = L.dev(L.rend); a.text_sen_end = L.dev(L.tse);
     if (dtk_launch_sentences(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "sentence table");
     b->sen_built = true;
     b->sen_home = b->sen_done = false;
   } else if (b->sen_home) {
     return DTK_OK;  // on its way
   }
-  uint8_t *h = b->h_sen.as<uint8_t>();
-  if (home) HIP_TRY(hipMemcpyAsync(h, b->d_sen.p, (size_t)b->sen.bytes, hipMemcpyDeviceToHost, b->dl_stream));
-  else HIP_TRY(hipMemcpyAsync(h + b->sen.cnt, (const uint8_t *)b->d_sen.p + b->sen.cnt, 4, hipMemcpyDeviceToHost, b->dl_stream));
+  if (home) HIP_TRY(hipMemcpyAsync(L.h.p, L.d.p, (size_t)L.bytes, hipMemcpyDeviceToHost, b->dl_stream));
+  else HIP_TRY(hipMemcpyAsync(L.host(L.cnt), L.dev(L.cnt), sizeof(uint32_t), hipMemcpyDeviceToHost, b->dl_stream));
   b->sen_home = home;
   if ((rc = b->ev_sen.ensure(hipEventDisableTiming)) != DTK_OK) return rc;
   HIP_TRY(hipEventRecord(b->ev_sen, b->dl_stream));
@@ -215,15 +199,13 @@ int sen_splice_exact(dtk_batch *b) {
   std::vector<uint64_t> csr(3 * ((size_t)nd + 1));
   HIP_TRY(hipMemcpy(csr.data(), b->d_csr, csr.size() * 8, hipMemcpyDeviceToHost));
   const uint64_t *tok_off = csr.data(), *text_off = csr.data() + 2 * ((size_t)nd + 1);
-  const dtk_batch::SenLayout old = b->sen;
-  const uint8_t *h = b->h_sen.as<uint8_t>();
-  const uint64_t *o_off = (const uint64_t *)h;
+  dtk_batch::Sen &L = b->sen;  // (as the kernels filled it; described anew below, for the spliced rows)
+  const uint64_t *o_off = L.host(L.off);
   struct Row { uint32_t tok_end, bstart, bend; int32_t rstart, rend; };
   std::vector<Row> rows;
   std::vector<uint64_t> off((size_t)nd + 1, 0);
-  std::vector<uint32_t> tse((const uint32_t *)(h + old.tse), (const uint32_t *)(h + old.tse) + old.texts);
+  std::vector<uint32_t> tse(L.host(L.tse), L.host(L.tse) + L.cap(L.tse));
   rows.reserve((size_t)b->sen_n);
-  auto field = [&](uint64_t at, uint64_t i) { return ((const uint32_t *)(h + at))[i]; };
   uint32_t e = 0;
   std::vector<uint32_t> firsts, bs, be, ttok;
   std::vector<int32_t> rs, re;
@@ -260,28 +242,22 @@ int sen_splice_exact(dtk_batch *b) {
         tse[x0 + g] = (uint32_t)(std::lower_bound(firsts.begin(), firsts.end(), ttok[g]) - firsts.begin());
     } else {
       for (uint64_t i = o_off[d]; i < o_off[d + 1]; i++)
-        rows.push_back(Row{field(old.tok_end, i), field(old.bstart, i), field(old.bend, i), (int32_t)field(old.rstart, i),
-                           (int32_t)field(old.rend, i)});
+        rows.push_back(Row{L.host(L.tok_end)[i], L.host(L.bstart)[i], L.host(L.bend)[i], L.host(L.rstart)[i], L.host(L.rend)[i]});
     }
   }
   off[nd] = rows.size();
   const uint64_t n = rows.size();
-  const dtk_batch::SenLayout L = sen_layout(nd, std::max<uint64_t>(n, 1), old.texts);
-  std::vector<uint64_t> blk(L.bytes / 8, 0);
-  uint8_t *q = (uint8_t *)blk.data();
-  memcpy(q, off.data(), off.size() * 8);
+  const int rc = sen_describe(b, std::max<uint64_t>(n, 1), tse.size());
+  if (rc != DTK_OK) return rc;
+  memset(L.h.p, 0, (size_t)L.bytes);
+  std::copy(off.begin(), off.end(), L.host(L.off));
   for (uint64_t i = 0; i < n; i++) {
-    ((uint32_t *)(q + L.tok_end))[i] = rows[i].tok_end; ((uint32_t *)(q + L.bstart))[i] = rows[i].bstart;
-    ((uint32_t *)(q + L.bend))[i] = rows[i].bend; ((int32_t *)(q + L.rstart))[i] = rows[i].rstart;
-    ((int32_t *)(q + L.rend))[i] = rows[i].rend;
+    L.host(L.tok_end)[i] = rows[i].tok_end; L.host(L.bstart)[i] = rows[i].bstart; L.host(L.bend)[i] = rows[i].bend;
+    L.host(L.rstart)[i] = rows[i].rstart; L.host(L.rend)[i] = rows[i].rend;
   }
-  if (!tse.empty()) memcpy(q + L.tse, tse.data(), tse.size() * 4);
-  *(uint32_t *)(q + L.cnt) = (uint32_t)n;
-  int rc;
-  if ((rc = b->d_sen.fit(L.bytes / 8, L.bytes / 8)) || (rc = b->h_sen.fit((size_t)L.bytes))) return rc;
-  memcpy(b->h_sen.p, q, (size_t)L.bytes);
-  HIP_TRY(hipMemcpy(b->d_sen.p, q, (size_t)L.bytes, hipMemcpyHostToDevice));
-  b->sen = L;
+  std::copy(tse.begin(), tse.end(), L.host(L.tse));
+  *L.host(L.cnt) = (uint32_t)n;
+  HIP_TRY(hipMemcpy(L.d.p, L.h.p, (size_t)L.bytes, hipMemcpyHostToDevice));
   b->sen_n = n;
   return DTK_OK;
 }
@@ -295,8 +271,8 @@ int sen_finish(dtk_batch *b, bool home) {
     if ((rc = sen_enqueue(b, home)) != DTK_OK) return rc;
     if (!b->sen_waited) { HIP_TRY(hipEventSynchronize(b->ev_sen)); b->sen_waited = true; }
     if (b->sen_done) return DTK_OK;  // (the count was looked at before: this call only brought the block home)
-    const uint64_t n = *(const uint32_t *)(b->h_sen.as<uint8_t>() + b->sen.cnt);
-    if (n <= b->sen.rows) { b->sen_n = n; break; }
+    const uint64_t n = *b->sen.host(b->sen.cnt);
+    if (n <= b->sen.cap(b->sen.tok_end)) { b->sen_n = n; break; }
     // more rows than the bound (not expected of regular documents): the kernels wrote nothing; again, for n rows
     b->sen_need = n;
     b->sen_built = false;
@@ -311,7 +287,7 @@ extern "C" int dtk_batch_sentences_device(dtk_batch *b, dtk_sentence_view *o) {
   if (!b || !o) return DTK_E_ARG;
   const int rc = sen_finish(b, false);
   if (rc != DTK_OK) return rc;
-  sen_view(b, (const uint8_t *)b->d_sen.p, o);
+  sen_view(b, b->sen.d.p, o);
   return DTK_OK;
 }
 
@@ -319,7 +295,7 @@ extern "C" int dtk_batch_sentences_host(dtk_batch *b, dtk_sentence_view *o) {
   if (!b || !o) return DTK_E_ARG;
   const int rc = sen_finish(b, true);
   if (rc != DTK_OK) return rc;
-  sen_view(b, b->h_sen.as<uint8_t>(), o);
+  sen_view(b, b->sen.h.p, o);
   return DTK_OK;
 }
 

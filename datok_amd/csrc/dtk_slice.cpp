@@ -28,28 +28,41 @@ void set_slice_inputs(const dtk_batch *b, A &a) {
   }
 }
 
+// What a first copy brings of a piece whose length only the trailer knows: `bound`, from the compaction's counts for
+// the window as a fresh document (the delivery brings the rest if the trailer counts more), or the debug key EVL_CAP,
+// so that ordinary text gets there.
+uint64_t first_copy(uint64_t bound) { return g_dbg.evl_cap >= 0 ? (uint64_t)g_dbg.evl_cap : bound; }
+
+// At delivery: what has been asked for beyond the first copies comes now, with one wait for all of it.  The kernels'
+// results stay where they are on the device, nothing is computed again.
+int bring_late(dtk_batch *b, MirrorBlock &m) {
+  const int rc = m.issue(b->dl_stream);
+  if (rc != DTK_OK || !m.in_flight) return rc;
+  HIP_TRY(hipStreamSynchronize(b->dl_stream));
+  m.landed();
+  return DTK_OK;
+}
+
 // kPlainBytes.  The output is sized here: a surface byte per window byte of the slice (three where the run saw invalid
 // UTF-8), a newline per token, SentenceEnd and TextEnd call, and the tail's two.
 int render_slice(dtk_batch *b) {
   SliceOut &o = b->slice;
+  SliceOut::Bytes &B = o.bytes;
   const uint64_t span = o.req.cut > o.req.first ? o.req.cut - o.req.first : 0;
   const uint64_t cap = span * (b->n_invalid ? 3u : 1u) + b->totals.n_tokens + b->totals.n_sent + b->totals.n_texts + 2;
-  const uint64_t cap8 = (cap + 7u) & ~7ull;  // (the length word lies behind the bytes)
   DtkStreamRenderArgs a{};
   a.bits = o.req.bits & 3u;
   set_slice_inputs(b, a);
   const uint64_t words = (uint64_t)a.tok_tiles + a.ent_tiles + a.evl_cap + 1;
+  B.clear(); B.add(B.out, cap); B.add(B.len, 1);
   int rc;
-  if ((rc = o.d_out.fit(cap8 + 8, cap8 + cap8 / 8 + 264)) || (rc = o.d_ws.fit(words, words + words / 8 + 16)) ||
-      (rc = o.h_out.fit((size_t)(cap8 + 8))))
-    return rc;
+  if ((rc = B.fit()) || (rc = o.d_ws.fit(words, words + words / 8 + 16))) return rc;
   a.tok_base = o.d_ws; a.ent_base = a.tok_base + a.tok_tiles; a.ew = a.ent_base + a.ent_tiles;
-  a.out = o.d_out; a.cap = cap; a.out_len = reinterpret_cast<uint64_t *>(o.d_out.p + cap8);
-  HIP_TRY(hipMemsetAsync(o.d_out, '\n', cap8, b->dl_stream));  // every byte that is no surface byte
+  a.out = B.dev(B.out); a.cap = cap; a.out_len = B.dev(B.len);
+  HIP_TRY(hipMemsetAsync(a.out, '\n', B.at(B.len), b->dl_stream));  // every byte that is no surface byte
   if (dtk_launch_streamrender(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "render slice");
-  HIP_TRY(hipMemcpyAsync(o.h_out.p, o.d_out, (size_t)(cap8 + 8), hipMemcpyDeviceToHost, b->dl_stream));
-  o.cap = cap;
-  return DTK_OK;
+  B.bring(B.out, cap); B.bring(B.len, 1);
+  return B.issue(b->dl_stream);
 }
 
 // kPosBytes.  The capacity is a bound the host can state before anything is enqueued: the
@@ -59,6 +72,7 @@ int render_slice(dtk_batch *b) {
 // the output inside the same bound.
 int render_slice_pos(dtk_batch *b) {
   SliceOut &o = b->slice;
+  SliceOut::Bytes &B = o.bytes;
   const SliceRequest &q = o.req;
   if (!q.carry_in || !q.carry_out) return DTK_E_STATE;
   const uint64_t span = q.cut > q.first ? q.cut - q.first : 0;
@@ -68,23 +82,19 @@ int render_slice_pos(dtk_batch *b) {
                         ((q.bits & DTK_SENTENCE_POS) ? std::min<uint64_t>(nt, calls + 1) + 2 * rows + 1 : 0);
   const uint64_t cap = ((q.bits & DTK_TOKENS) ? span * (b->n_invalid ? 3u : 1u) + nt : 0) + calls +
                        ints * ((uint64_t)q.digits + 1u) + 2 * (rows + 2);
-  const uint64_t cap8 = (cap + 7u) & ~7ull;
-  const uint64_t bytes = cap8 + sizeof(DtkPosTrailer);
   DtkStreamPosArgs a{};
   a.bits = q.bits & 31u;
   set_slice_inputs(b, a);
   const uint64_t words = dtk_streampos_ws(&a, nullptr);
+  B.clear(); B.add(B.out, cap); B.add(B.trailer, 1);
   int rc;
-  if ((rc = o.d_out.fit(bytes, bytes + bytes / 8 + 264)) || (rc = o.d_ws.fit(words, words + words / 8 + 16)) ||
-      (rc = o.h_out.fit((size_t)bytes)))
-    return rc;
+  if ((rc = B.fit()) || (rc = o.d_ws.fit(words, words + words / 8 + 16))) return rc;
   (void)dtk_streampos_ws(&a, o.d_ws);
-  a.out = o.d_out; a.cap = cap; a.trailer = reinterpret_cast<DtkPosTrailer *>(o.d_out.p + cap8);
-  HIP_TRY(hipMemsetAsync(o.d_out, '\n', cap8, b->dl_stream));  // every byte that is no surface byte and no integer's
+  a.out = B.dev(B.out); a.cap = cap; a.trailer = B.dev(B.trailer);
+  HIP_TRY(hipMemsetAsync(a.out, '\n', B.at(B.trailer), b->dl_stream));  // every byte that is no surface byte and no integer's
   if (dtk_launch_streampos(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "render slice positions");
-  HIP_TRY(hipMemcpyAsync(o.h_out.p, o.d_out, (size_t)bytes, hipMemcpyDeviceToHost, b->dl_stream));
-  o.cap = cap;
-  return DTK_OK;
+  B.bring(B.out, cap); B.bring(B.trailer, 1);
+  return B.issue(b->dl_stream);
 }
 
 // offs.  The capacities are bounds the host can state before anything is enqueued, from the
@@ -94,102 +104,72 @@ int render_slice_pos(dtk_batch *b) {
 // results) the form is the plain one and nothing is copied home.  *chain: the chain's arguments as they were launched.
 int slice_offsets(dtk_batch *b, DtkStreamOffsArgs *chain) {
   SliceOut &o = b->slice;
+  SliceOut::Offs &L = o.offs;
   const SliceRequest &q = o.req;
   if (!q.carry_in || !q.carry_out) return DTK_E_STATE;
   const uint64_t rows = b->evl_copied, nt = b->totals.n_tokens;
-  SoLayout L;
-  L.n = nt; L.sent_cap = std::min<uint64_t>(nt, 3 * rows + 3) + 2 * rows + 1; L.text_cap = rows + 1;
   L.blocked = q.offs && q.form == DTK_SO_BLOCKED;
-  // What the copies bring of sent and the text rows: the compaction's counts for the window as a fresh document, which
-  // differ from the stream's by the few calls in front of the slice's first token.  batch_offs_out brings the rest if
-  // the trailer counts more (the debug key EVL_CAP sizes these too, so that ordinary text gets there).
-  L.sent_home = std::min<uint64_t>(L.sent_cap, g_dbg.evl_cap >= 0 ? (uint64_t)g_dbg.evl_cap : b->totals.n_sent + 64);
-  L.text_home = std::min<uint64_t>(L.text_cap, g_dbg.evl_cap >= 0 ? (uint64_t)g_dbg.evl_cap : b->totals.n_texts + 2);
-  uint64_t at = 0;  // (bytes; every piece begins on a multiple of 8)
-  auto take = [&](uint64_t bytes) { const uint64_t p = at; at += (bytes + 7u) & ~7ull; return p; };
-  L.rstart = take(nt * 8); L.rend = take(nt * 8); L.sent = take(L.sent_cap * 8);
-  L.trailer = take(sizeof(DtkOffsTrailer)); L.ttok = take(L.text_cap * 4); L.tsent = take(L.text_cap * 4);
-  L.heads = take(L.blocked ? blocks_of(nt) * sizeof(DtkOffBlock64) : 0); L.words = take(L.blocked ? nt * 4 : 0);
-  L.bytes = at;
+  L.clear();
+  L.add(L.rstart, nt); L.add(L.rend, nt); L.add(L.sent, std::min<uint64_t>(nt, 3 * rows + 3) + 2 * rows + 1);
+  L.add(L.trailer, 1); L.add(L.ttok, rows + 1); L.add(L.tsent, rows + 1);
+  L.add(L.heads, L.blocked ? blocks_of(nt) : 0); L.add(L.words, L.blocked ? nt : 0);
   DtkStreamOffsArgs a{};
   DtkStreamPosArgs &f = a.front;
   f.bits = DTK_TOKEN_POS | DTK_SENTENCE_POS | (q.nl ? (uint32_t)DTK_NEWLINE_AFTER_EOT : 0u);
   set_slice_inputs(b, f);
-  const uint64_t words = dtk_streamoffs_ws(&a, nullptr), out_words = L.bytes / 8;
+  const uint64_t words = dtk_streamoffs_ws(&a, nullptr);
   int rc;
-  if ((rc = o.d_offs_ws.fit(words, words + words / 8 + 16)) || (rc = o.d_offs_out.fit(out_words, out_words + out_words / 8 + 32)) ||
-      (q.offs && (rc = o.h_offs_out.fit((size_t)L.bytes))))
-    return rc;
+  if ((rc = o.d_offs_ws.fit(words, words + words / 8 + 16)) || (rc = L.fit(q.offs))) return rc;
   (void)dtk_streamoffs_ws(&a, o.d_offs_ws);
-  uint8_t *d = reinterpret_cast<uint8_t *>(o.d_offs_out.p), *h = o.h_offs_out.as<uint8_t>();
-  f.rstart = reinterpret_cast<int64_t *>(d + L.rstart); f.rend = reinterpret_cast<int64_t *>(d + L.rend);
-  a.sent = reinterpret_cast<int64_t *>(d + L.sent); a.sent_cap = L.sent_cap; a.text_cap = L.text_cap;
-  a.trailer = reinterpret_cast<DtkOffsTrailer *>(d + L.trailer);
-  a.text_tok_end = reinterpret_cast<uint32_t *>(d + L.ttok); a.text_sent_end = reinterpret_cast<uint32_t *>(d + L.tsent);
+  f.rstart = L.dev(L.rstart); f.rend = L.dev(L.rend);
+  a.sent = L.dev(L.sent); a.sent_cap = L.cap(L.sent); a.text_cap = L.cap(L.ttok);
+  a.trailer = L.dev(L.trailer); a.text_tok_end = L.dev(L.ttok); a.text_sent_end = L.dev(L.tsent);
   a.blocked = L.blocked ? 1u : 0u; a.span = g_dbg.blk_span > 0 ? (uint32_t)g_dbg.blk_span : 65535u;
-  a.heads = reinterpret_cast<DtkOffBlock64 *>(d + L.heads); a.words = reinterpret_cast<uint32_t *>(d + L.words);
+  a.heads = L.dev(L.heads); a.words = L.dev(L.words);
   if (dtk_launch_streamoffs(&a, b->dl_stream, nullptr)) return hip_fail(hipGetLastError(), "slice offsets");
   *chain = a;
-  o.so = L;
   if (!q.offs) return DTK_OK;
-  // the plain offsets and sent lie back to back; then the trailer with text_tok_end, text_sent_end, the blocked form
-  const uint64_t piece[4][2] = {{L.blocked ? L.sent : 0, L.sent + L.sent_home * 8},
-                                {L.trailer, L.ttok + L.text_home * 4},
-                                {L.tsent, L.tsent + L.text_home * 4},
-                                {L.heads, L.blocked ? L.bytes : L.heads}};
-  for (const auto &p : piece)
-    if (p[1] > p[0]) HIP_TRY(hipMemcpyAsync(h + p[0], d + p[0], (size_t)(p[1] - p[0]), hipMemcpyDeviceToHost, b->dl_stream));
-  o.so.wide_home = !L.blocked;
-  return DTK_OK;
+  // the plain or the blocked offsets whole; sent and the text rows as far as the compaction's counts reach (they differ
+  // from the stream's by the few calls in front of the slice's first token); the trailer
+  if (!L.blocked) { L.bring(L.rstart, nt); L.bring(L.rend, nt); }
+  L.bring(L.sent, first_copy(b->totals.n_sent + 64));
+  L.bring(L.trailer, 1);
+  L.bring(L.ttok, first_copy(b->totals.n_texts + 2)); L.bring(L.tsent, first_copy(b->totals.n_texts + 2));
+  L.bring(L.heads, L.cap(L.heads)); L.bring(L.words, L.cap(L.words));
+  return L.issue(b->dl_stream);
 }
 
 // sens, behind the offsets chain `chain` of the same slice.  A sentence-first token needs a call or the carry in front
 // of it, and the carried row is one more: min(n_tok, 3 * rows + 3) + 1 rows, and a text row per TextEnd as above.
 int slice_sentences(dtk_batch *b, const DtkStreamOffsArgs &chain) {
   SliceOut &o = b->slice;
+  SliceOut::Sens &L = o.sens;
   const SliceRequest &q = o.req;
   if (!q.sen_carry_in || !q.sen_carry_out) return DTK_E_STATE;
-  const uint64_t rows = b->evl_copied, nt = b->totals.n_tokens;
-  SsLayout L;
-  L.n = nt; L.sen_cap = std::min<uint64_t>(nt, 3 * rows + 3) + 1; L.text_cap = rows + 1;
-  // What the copies bring of the rows, from the compaction's counts for the window as a fresh document: there every row
-  // pushes one sent int with its first token, and a second one unless a TextEnd or the window's end closes it, so
-  // 2 * rows <= n_sent + n_texts + 1 (half of n_sent + 64 rows' bytes on running text; the carried row and the calls in
-  // front of the first token are inside the 64).  batch_sens_out brings the rest if the trailer counts more.
-  L.sen_home = std::min<uint64_t>(L.sen_cap, g_dbg.evl_cap >= 0 ? (uint64_t)g_dbg.evl_cap
-                                                                : (b->totals.n_sent + b->totals.n_texts + 1) / 2 + 64);
-  L.text_home = std::min<uint64_t>(L.text_cap, g_dbg.evl_cap >= 0 ? (uint64_t)g_dbg.evl_cap : b->totals.n_texts + 2);
-  uint64_t at = 0;
-  auto take = [&](uint64_t bytes) { const uint64_t p = at; at += (bytes + 7u) & ~7ull; return p; };
-  L.trailer = take(sizeof(DtkSensTrailer)); L.tse = take(L.text_cap * 4);
-  L.tok_end = take(L.sen_cap * 4); L.bstart = take(L.sen_cap * 8); L.bend = take(L.sen_cap * 8);
-  L.rstart = take(L.sen_cap * 8); L.rend = take(L.sen_cap * 8);
-  L.bytes = at;
+  const uint64_t rows = b->evl_copied, nt = b->totals.n_tokens, sen_cap = std::min<uint64_t>(nt, 3 * rows + 3) + 1;
+  L.n = nt;
+  L.clear();
+  L.add(L.trailer, 1); L.add(L.tse, rows + 1);
+  L.add(L.tok_end, sen_cap); L.add(L.bstart, sen_cap); L.add(L.bend, sen_cap); L.add(L.rstart, sen_cap); L.add(L.rend, sen_cap);
   DtkStreamSensArgs a{};
   a.front = chain.front;
   a.base = q.base; a.carry_in = q.sen_carry_in; a.carry_out = q.sen_carry_out;
-  const uint64_t words = dtk_streamsens_ws(&a, nullptr), out_words = L.bytes / 8;
+  const uint64_t words = dtk_streamsens_ws(&a, nullptr);
   int rc;
-  if ((rc = o.d_sens_ws.fit(words + 1u, words + words / 8 + 16)) || (rc = o.d_sens_out.fit(out_words, out_words + out_words / 8 + 32)) ||
-      (rc = o.h_sens_out.fit((size_t)L.bytes)))
-    return rc;
+  if ((rc = o.d_sens_ws.fit(words + 1u, words + words / 8 + 16)) || (rc = L.fit())) return rc;
   (void)dtk_streamsens_ws(&a, o.d_sens_ws);
-  uint8_t *d = reinterpret_cast<uint8_t *>(o.d_sens_out.p), *h = o.h_sens_out.as<uint8_t>();
-  a.sen_cap = L.sen_cap; a.text_cap = L.text_cap;
-  a.trailer = reinterpret_cast<DtkSensTrailer *>(d + L.trailer);
-  a.text_sen_end = reinterpret_cast<uint32_t *>(d + L.tse);
-  a.sen_tok_end = reinterpret_cast<uint32_t *>(d + L.tok_end);
-  a.sen_bstart = reinterpret_cast<uint64_t *>(d + L.bstart); a.sen_bend = reinterpret_cast<uint64_t *>(d + L.bend);
-  a.sen_rstart = reinterpret_cast<int64_t *>(d + L.rstart); a.sen_rend = reinterpret_cast<int64_t *>(d + L.rend);
+  a.sen_cap = sen_cap; a.text_cap = L.cap(L.tse);
+  a.trailer = L.dev(L.trailer); a.text_sen_end = L.dev(L.tse); a.sen_tok_end = L.dev(L.tok_end);
+  a.sen_bstart = L.dev(L.bstart); a.sen_bend = L.dev(L.bend); a.sen_rstart = L.dev(L.rstart); a.sen_rend = L.dev(L.rend);
   if (dtk_launch_streamsens(&a, b->dl_stream, nullptr)) return hip_fail(hipGetLastError(), "slice sentences");
-  // the trailer with text_sen_end behind it, then the five arrays
-  const uint64_t piece[6][2] = {{L.trailer, L.tse + L.text_home * 4},       {L.tok_end, L.tok_end + L.sen_home * 4},
-                                {L.bstart, L.bstart + L.sen_home * 8},      {L.bend, L.bend + L.sen_home * 8},
-                                {L.rstart, L.rstart + L.sen_home * 8},      {L.rend, L.rend + L.sen_home * 8}};
-  for (const auto &p : piece)
-    if (p[1] > p[0]) HIP_TRY(hipMemcpyAsync(h + p[0], d + p[0], (size_t)(p[1] - p[0]), hipMemcpyDeviceToHost, b->dl_stream));
-  o.ss = L;
-  return DTK_OK;
+  // What the copies bring of the rows, from the compaction's counts for the window as a fresh document: there every row
+  // pushes one sent int with its first token, and a second one unless a TextEnd or the window's end closes it, so
+  // 2 * rows <= n_sent + n_texts + 1 (half of n_sent + 64 rows' bytes on running text; the carried row and the calls in
+  // front of the first token are inside the 64).
+  const uint64_t sen_home = first_copy((b->totals.n_sent + b->totals.n_texts + 1) / 2 + 64);
+  L.bring(L.trailer, 1); L.bring(L.tse, first_copy(b->totals.n_texts + 2));
+  L.bring(L.tok_end, sen_home); L.bring(L.bstart, sen_home); L.bring(L.bend, sen_home); L.bring(L.rstart, sen_home); L.bring(L.rend, sen_home);
+  return L.issue(b->dl_stream);
 }
 
 // the download that holds the slice's outputs has come home
@@ -197,7 +177,8 @@ bool slice_home(const dtk_batch *b) { return b->dl_begun && b->dl_waited; }
 }  // namespace
 
 int slice_outputs(dtk_batch *b) {
-  const SliceRequest &q = b->slice.req;
+  SliceOut &o = b->slice;
+  const SliceRequest &q = o.req;
   if (q.bytes == SliceRequest::kNoBytes && !q.offs && !q.sens) return DTK_OK;
   if (b->n_docs != 1 || b->total > 0xFFFFFFFFull) return DTK_E_STATE;
   int rc = DTK_OK;
@@ -205,16 +186,17 @@ int slice_outputs(dtk_batch *b) {
   DtkStreamOffsArgs chain{};  // (once per slice, whoever wants it)
   if (rc == DTK_OK && (q.offs || q.sens)) rc = slice_offsets(b, &chain);
   if (rc == DTK_OK && q.sens) rc = slice_sentences(b, chain);
+  // (the download's event lies behind these copies, and nothing is handed out before it has been waited for: slice_home)
+  o.bytes.landed(); o.offs.landed(); o.sens.landed();
   return rc;
 }
 
 int batch_render_out(dtk_batch *b, const uint8_t **out, uint64_t *out_len) {
-  const SliceOut &o = b->slice;
-  if (o.req.bytes != SliceRequest::kPlainBytes || !slice_home(b) || !o.h_out.p) return DTK_E_STATE;
-  const uint64_t cap8 = (o.cap + 7u) & ~7ull;
-  const uint64_t n = *reinterpret_cast<const uint64_t *>(o.h_out.as<uint8_t>() + cap8);
-  if (n > o.cap) return DTK_E_CAPACITY;  // (more calls than the totals count: no regular slice)
-  *out = o.h_out.as<uint8_t>();
+  const SliceOut::Bytes &B = b->slice.bytes;
+  if (b->slice.req.bytes != SliceRequest::kPlainBytes || !slice_home(b) || !B.h.p) return DTK_E_STATE;
+  const uint64_t n = *B.host(B.len);
+  if (n > B.cap(B.out)) return DTK_E_CAPACITY;  // (more calls than the totals count: no regular slice)
+  *out = B.host(B.out);
   *out_len = n;
   return DTK_OK;
 }
@@ -232,97 +214,51 @@ extern "C" int dtk_pos_trailer_check(const DtkPosTrailer *t, uint64_t cap) {
 }
 
 int batch_pos_out(dtk_batch *b, const uint8_t **out, const DtkPosTrailer **trailer) {
-  const SliceOut &o = b->slice;
-  if (o.req.bytes != SliceRequest::kPosBytes || !slice_home(b) || !o.h_out.p) return DTK_E_STATE;
-  const uint64_t cap8 = (o.cap + 7u) & ~7ull;
-  const DtkPosTrailer *t = reinterpret_cast<const DtkPosTrailer *>(o.h_out.as<uint8_t>() + cap8);
-  const int rc = dtk_pos_trailer_check(t, o.cap);
+  const SliceOut::Bytes &B = b->slice.bytes;
+  if (b->slice.req.bytes != SliceRequest::kPosBytes || !slice_home(b) || !B.h.p) return DTK_E_STATE;
+  const DtkPosTrailer *t = B.host(B.trailer);
+  const int rc = dtk_pos_trailer_check(t, B.cap(B.out));
   if (rc != DTK_OK) return rc;
-  *out = o.h_out.as<uint8_t>();
+  *out = B.host(B.out);
   *trailer = t;
   return DTK_OK;
 }
 
 int batch_offs_out(dtk_batch *b, SoView *v) {
-  SliceOut &o = b->slice;
-  if (!o.req.offs || !slice_home(b) || !o.h_offs_out.p) return DTK_E_STATE;
-  SoLayout &L = o.so;
-  const uint8_t *h = o.h_offs_out.as<uint8_t>();
-  const DtkOffsTrailer *t = reinterpret_cast<const DtkOffsTrailer *>(h + L.trailer);
+  SliceOut::Offs &L = b->slice.offs;
+  if (!b->slice.req.offs || !slice_home(b) || !L.h.p) return DTK_E_STATE;
+  const DtkOffsTrailer *t = L.host(L.trailer);
   // (a list longer than its arrays says so with n_tok = ~0; more calls than the bound counts: no regular slice)
-  if (t->n_tok != L.n || t->n_sent > L.sent_cap || t->n_text > L.text_cap) return DTK_E_CAPACITY;
+  if (t->n_tok != L.cap(L.rstart) || t->n_sent > L.cap(L.sent) || t->n_text > L.cap(L.ttok)) return DTK_E_CAPACITY;
   if (t->flags & 1u) return DTK_E_IRREGULAR;
   // The slow paths, as a list that is packed again: a segment of a block spans more than 16 bits, so the plain arrays
-  // come over now; the slice has more sent ints or text rows than the copies brought.  The kernels' results stay where
-  // they are on the device, nothing is computed again.
-  const uint8_t *d = reinterpret_cast<const uint8_t *>(o.d_offs_out.p);
-  uint8_t *hw = o.h_offs_out.as<uint8_t>();
-  bool late = false;
-  auto bring = [&](uint64_t from, uint64_t to) -> int {
-    if (to > from) HIP_TRY(hipMemcpyAsync(hw + from, d + from, (size_t)(to - from), hipMemcpyDeviceToHost, b->dl_stream));
-    late = true;
-    return DTK_OK;
-  };
-  int rc;
-  if (L.blocked && t->blk_fail && !L.wide_home) {
-    if ((rc = bring(0, L.sent)) != DTK_OK) return rc;
-    L.wide_home = true;
-  }
-  if (t->n_sent > L.sent_home) {
-    if ((rc = bring(L.sent + L.sent_home * 8, L.sent + t->n_sent * 8)) != DTK_OK) return rc;
-    L.sent_home = t->n_sent;
-  }
-  if (t->n_text > L.text_home) {
-    if ((rc = bring(L.ttok + L.text_home * 4, L.ttok + t->n_text * 4)) != DTK_OK ||
-        (rc = bring(L.tsent + L.text_home * 4, L.tsent + t->n_text * 4)) != DTK_OK)
-      return rc;
-    L.text_home = t->n_text;
-  }
-  if (late) HIP_TRY(hipStreamSynchronize(b->dl_stream));
+  // come over now; the slice has more sent ints or text rows than the copies brought.
   const bool plain = !L.blocked || t->blk_fail;
+  if (plain) { L.bring(L.rstart, t->n_tok); L.bring(L.rend, t->n_tok); }
+  L.bring(L.sent, t->n_sent); L.bring(L.ttok, t->n_text); L.bring(L.tsent, t->n_text);
+  const int rc = bring_late(b, L);
+  if (rc != DTK_OK) return rc;
   v->t = t;
-  v->rstart = plain ? reinterpret_cast<const int64_t *>(h + L.rstart) : nullptr;
-  v->rend = plain ? reinterpret_cast<const int64_t *>(h + L.rend) : nullptr;
-  v->words = plain ? nullptr : reinterpret_cast<const uint32_t *>(h + L.words);
-  v->heads = plain ? nullptr : reinterpret_cast<const DtkOffBlock64 *>(h + L.heads);
-  v->sent = reinterpret_cast<const int64_t *>(h + L.sent);
-  v->ttok = reinterpret_cast<const uint32_t *>(h + L.ttok); v->tsent = reinterpret_cast<const uint32_t *>(h + L.tsent);
+  v->rstart = plain ? L.host(L.rstart) : nullptr; v->rend = plain ? L.host(L.rend) : nullptr;
+  v->words = plain ? nullptr : L.host(L.words); v->heads = plain ? nullptr : L.host(L.heads);
+  v->sent = L.host(L.sent); v->ttok = L.host(L.ttok); v->tsent = L.host(L.tsent);
   return DTK_OK;
 }
 
 int batch_sens_out(dtk_batch *b, SsView *v) {
-  SliceOut &o = b->slice;
-  if (!o.req.sens || !slice_home(b) || !o.h_sens_out.p) return DTK_E_STATE;
-  SsLayout &L = o.ss;
-  uint8_t *h = o.h_sens_out.as<uint8_t>();
-  const DtkSensTrailer *t = reinterpret_cast<const DtkSensTrailer *>(h + L.trailer);
+  SliceOut::Sens &L = b->slice.sens;
+  if (!b->slice.req.sens || !slice_home(b) || !L.h.p) return DTK_E_STATE;
+  const DtkSensTrailer *t = L.host(L.trailer);
   // (a list longer than its arrays says so with n_tok = ~0; more rows than the bound counts: no regular slice)
-  if (t->n_tok != L.n || t->n_sen > L.sen_cap || t->n_text > L.text_cap || t->firsts > L.n) return DTK_E_CAPACITY;
+  if (t->n_tok != L.n || t->n_sen > L.cap(L.tok_end) || t->n_text > L.cap(L.tse) || t->firsts > L.n) return DTK_E_CAPACITY;
   if (t->flags & 1u) return DTK_E_IRREGULAR;
-  // the slice closed more rows or texts than the copies brought: the rest comes now, nothing is computed again
-  const uint8_t *d = reinterpret_cast<const uint8_t *>(o.d_sens_out.p);
-  bool late = false;
-  auto bring = [&](uint64_t at, uint64_t from, uint64_t to, uint64_t size) -> int {
-    HIP_TRY(hipMemcpyAsync(h + at + from * size, d + at + from * size, (size_t)((to - from) * size), hipMemcpyDeviceToHost, b->dl_stream));
-    late = true;
-    return DTK_OK;
-  };
-  int rc;
-  if (t->n_sen > L.sen_home) {
-    if ((rc = bring(L.tok_end, L.sen_home, t->n_sen, 4)) != DTK_OK || (rc = bring(L.bstart, L.sen_home, t->n_sen, 8)) != DTK_OK ||
-        (rc = bring(L.bend, L.sen_home, t->n_sen, 8)) != DTK_OK || (rc = bring(L.rstart, L.sen_home, t->n_sen, 8)) != DTK_OK ||
-        (rc = bring(L.rend, L.sen_home, t->n_sen, 8)) != DTK_OK)
-      return rc;
-    L.sen_home = t->n_sen;
-  }
-  if (t->n_text > L.text_home) {
-    if ((rc = bring(L.tse, L.text_home, t->n_text, 4)) != DTK_OK) return rc;
-    L.text_home = t->n_text;
-  }
-  if (late) HIP_TRY(hipStreamSynchronize(b->dl_stream));
+  // the slice closed more rows or texts than the copies brought
+  L.bring(L.tok_end, t->n_sen); L.bring(L.bstart, t->n_sen); L.bring(L.bend, t->n_sen); L.bring(L.rstart, t->n_sen); L.bring(L.rend, t->n_sen);
+  L.bring(L.tse, t->n_text);
+  const int rc = bring_late(b, L);
+  if (rc != DTK_OK) return rc;
   v->t = t;
-  v->tok_end = reinterpret_cast<const uint32_t *>(h + L.tok_end); v->tse = reinterpret_cast<const uint32_t *>(h + L.tse);
-  v->bstart = reinterpret_cast<const uint64_t *>(h + L.bstart); v->bend = reinterpret_cast<const uint64_t *>(h + L.bend);
-  v->rstart = reinterpret_cast<const int64_t *>(h + L.rstart); v->rend = reinterpret_cast<const int64_t *>(h + L.rend);
+  v->tok_end = L.host(L.tok_end); v->tse = L.host(L.tse);
+  v->bstart = L.host(L.bstart); v->bend = L.host(L.bend); v->rstart = L.host(L.rstart); v->rend = L.host(L.rend);
   return DTK_OK;
 }

@@ -892,6 +892,19 @@ class Stream:
         return int(st.value)
 
 
+def _host_array(ptr, n, dt):
+    """A copy of the n elements of dtype dt at the address ptr (none, or a null pointer: empty)."""
+    dt = np.dtype(dt)
+    if n == 0 or not ptr:
+        return np.zeros(0, dt)
+    return np.frombuffer((C.c_char * (n * dt.itemsize)).from_address(ptr), dtype=dt).copy()
+
+
+def _writer_carry(c):
+    """A dtk_stream_pos_carry as a tuple: the writer's state at a cut."""
+    return (int(c.posC), bool(c.sentB), bool(c.init), bool(c.pos_nonempty), bool(c.sent_nonempty))
+
+
 def _slice_positions(h) -> dict:
     """What dtk_stream_positions and dtk_stream_emit say about the slice being delivered ({}: no position rendering)."""
     sp = _lib.StreamPos()
@@ -904,13 +917,10 @@ def _slice_positions(h) -> dict:
         parts.append(C.string_at(p, n))
         return 0
     check(lib().dtk_stream_emit(h, _lib.WRITE_FN(wr), None), "dtk_stream_emit")
-
-    def carry(c):
-        return (int(c.posC), bool(c.sentB), bool(c.init), bool(c.pos_nonempty), bool(c.sent_nonempty))
     return dict(splice_pos=None if sp.splice_pos == none else int(sp.splice_pos),
                 splice_sent=None if sp.splice_sent == none else int(sp.splice_sent),
                 open_pos=C.string_at(sp.open_pos, int(sp.open_pos_len)), open_sent=C.string_at(sp.open_sent, int(sp.open_sent_len)),
-                carry_in=carry(sp.carry_in), carry_out=carry(sp.carry_out), written=b"".join(parts))
+                carry_in=_writer_carry(sp.carry_in), carry_out=_writer_carry(sp.carry_out), written=b"".join(parts))
 
 
 def _slice_offsets(h) -> dict:
@@ -918,15 +928,7 @@ def _slice_offsets(h) -> dict:
     so = _lib.StreamOffs()
     if not h or lib().dtk_stream_offsets(h, C.byref(so)) != _lib.OK:
         return {}
-
-    def arr(ptr, n, dt):
-        dt = np.dtype(dt)
-        if n == 0 or not ptr:
-            return np.zeros(0, dt)
-        return np.frombuffer((C.c_char * (n * dt.itemsize)).from_address(ptr), dtype=dt).copy()
-
-    def carry(c):
-        return (int(c.posC), bool(c.sentB), bool(c.init), bool(c.pos_nonempty), bool(c.sent_nonempty))
+    arr = _host_array
     nt, ns, nx = int(so.n_tok), int(so.n_sent), int(so.n_text)
     blocked = not so.tok_rstart and bool(so.tok_rblk)
     words = heads = None
@@ -937,7 +939,8 @@ def _slice_offsets(h) -> dict:
         rs, re = arr(so.tok_rstart, nt, np.int64), arr(so.tok_rend, nt, np.int64)
     return dict(r_tok_rstart=rs, r_tok_rend=re, r_blocked=blocked, r_rblk=words, r_rblk_head=heads,
                 r_sent=arr(so.sent, ns, np.int64), r_text_tok_end=arr(so.text_tok_end, nx, np.uint32),
-                r_text_sent_end=arr(so.text_sent_end, nx, np.uint32), r_carry_in=carry(so.carry_in), r_carry_out=carry(so.carry_out))
+                r_text_sent_end=arr(so.text_sent_end, nx, np.uint32), r_carry_in=_writer_carry(so.carry_in),
+                r_carry_out=_writer_carry(so.carry_out))
 
 
 def _slice_sentences(h) -> dict:
@@ -946,14 +949,9 @@ def _slice_sentences(h) -> dict:
     if not h or lib().dtk_stream_sentences(h, C.byref(ss)) != _lib.OK:
         return {}
 
-    def arr(ptr, n, dt):
-        dt = np.dtype(dt)
-        if n == 0 or not ptr:
-            return np.zeros(0, dt)
-        return np.frombuffer((C.c_char * (n * dt.itemsize)).from_address(ptr), dtype=dt).copy()
-
     def carry(c):
         return (bool(c.open), int(c.bstart), int(c.bend), int(c.rstart), int(c.rend))
+    arr = _host_array
     n, nx = int(ss.n_sen), int(ss.n_text)
     return dict(s_tok_end=arr(ss.sen_tok_end, n, np.uint32), s_bstart=arr(ss.sen_bstart, n, np.uint64),
                 s_bend=arr(ss.sen_bend, n, np.uint64), s_rstart=arr(ss.sen_rstart, n, np.int64),
@@ -964,11 +962,7 @@ def _slice_sentences(h) -> dict:
 def _slice_view(s, stream=None) -> SliceView:
     """Host copies of a dtk_stream_slice (its buffers are only valid inside the callback)."""
     v = s.view
-
-    def arr(ptr, n, dt):
-        if n == 0 or not ptr:
-            return np.zeros(0, dt)
-        return np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(ptr), dtype=dt).copy()
+    arr = _host_array
     nt = int(arr(v.tok_off, 2, np.uint64)[1])
     if v.tok_bend:
         bs, be = arr(v.tok_bstart, nt, np.uint32), arr(v.tok_bend, nt, np.uint32)

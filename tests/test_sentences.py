@@ -49,8 +49,10 @@ _hip = []
 def _from_device(ptr, n, dt):
     """n elements of a device array, copied back through the HIP runtime the library itself has loaded."""
     if not _hip:
-        path = next(l.split()[-1] for l in open("/proc/self/maps") if "libamdhip64" in l)
-        _hip.append(C.CDLL(path))
+        # (a lookup on the library's own handle searches what it is linked against: a process that has also imported
+        #  torch holds a second runtime, which does not know the library's memory)
+        import datok_amd
+        _hip.append(C.CDLL(datok_amd.lib()._name))
         _hip[0].hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     out = np.zeros(n, dt)
     if n:

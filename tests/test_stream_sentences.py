@@ -237,6 +237,39 @@ def test_a_slice_computed_twice_leaves_the_same_rows_and_carries(models, whole):
                 assert all(np.array_equal(x, y) for x, y in zip(sen_parts(a), sen_parts(b)))
 
 
+def many_texts(total=40 * 1024, every=2048):
+    """Running text with a text end (U+0004) behind a sentence end about every `every` bytes."""
+    raw = sc.running_text(total, seed=5)
+    parts, at = [], 0
+    while (k := raw.find(b". ", at + every)) >= 0:
+        parts.append(raw[at:k + 1] + b"\x04")
+        at = k + 1
+    return b"".join(parts) + raw[at:]
+
+
+def test_every_array_of_a_slice_comes_late(models):
+    """Several texts in a slice: where the first copies are sized for one element (EVL_CAP=1), the text rows, the sent ints
+    and the sentence rows of both tables all have elements that only the delivery brings."""
+    import datok_amd
+    tok, om = models("tokenizer_de.matok")
+    raw = many_texts()
+    calls, doc = sc.oracle_calls(om, raw)[0], om.transduce_doc(raw, 0)
+    assert doc.status == 0
+    with datok_amd.Stream(16384) as st:
+        plain = assert_sentences(st, tok, om, raw, 0, BLOCKED, calls=calls, doc=doc)
+        assert datok_amd.lib().dtk_debug_configure(b"EVL_CAP", b"1") == 0
+        try:
+            late = assert_sentences(st, tok, om, raw, 0, BLOCKED, calls=calls, doc=doc)
+        finally:
+            assert datok_amd.lib().dtk_debug_configure(b"EVL_CAP", os.environ.get("DATOK_EVL_CAP", "-1").encode()) == 0
+    assert any(min(len(sl.r_text_tok_end), len(sl.s_text_sen_end), len(sl.r_sent), len(sl.s_tok_end)) >= 3 for sl in plain)
+    assert len(late) == len(plain) >= 2
+    for a, b in zip(late, plain):
+        assert (a.s_carry_in, a.s_carry_out, a.r_carry_in, a.r_carry_out) == (b.s_carry_in, b.s_carry_out, b.r_carry_in, b.r_carry_out)
+        assert all(np.array_equal(x, y) for x, y in zip(sen_parts(a) + slice_parts(a), sen_parts(b) + slice_parts(b)))
+        assert a.r_blocked == b.r_blocked and np.array_equal(a.r_rblk, b.r_rblk) and np.array_equal(a.r_rblk_head, b.r_rblk_head)
+
+
 # ---- 9. beyond 32 bits
 def test_rune_spans_beyond_32_bits(models):
     import datok_amd

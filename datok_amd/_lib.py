@@ -39,7 +39,12 @@ EXPORTS = [
     "dtk_stream_set_offsets", "dtk_stream_offsets", "dtk_blk64_start", "dtk_blk64_end",
     "dtk_batch_sentences_device", "dtk_batch_sentences_host",
     "dtk_stream_set_sentences", "dtk_stream_sentences",
+    "dtk_vocab_create", "dtk_vocab_free", "dtk_vocab_size", "dtk_vocab_probe_mem",
+    "dtk_tally_create", "dtk_tally_read", "dtk_tally_reset", "dtk_tally_free",
+    "dtk_batch_set_vocab", "dtk_batch_token_ids_device", "dtk_batch_token_ids_host",
+    "dtk_pipeline_set_vocab", "dtk_stream_set_vocab", "dtk_stream_token_ids",
 ]
+ID_UNKNOWN = -1   # DTK_ID_UNKNOWN
 
 
 class ModelInfo(C.Structure):
@@ -77,6 +82,11 @@ class SentenceView(C.Structure):
     _fields_ = [("n_sen", C.c_uint64), ("sen_off", C.c_void_p), ("sen_tok_end", C.c_void_p),
                 ("sen_bstart", C.c_void_p), ("sen_bend", C.c_void_p), ("sen_rstart", C.c_void_p), ("sen_rend", C.c_void_p),
                 ("text_sen_end", C.c_void_p)]
+
+
+class TokenIdView(C.Structure):
+    """dtk_token_id_view: a run's tokens looked up in a vocabulary (dtk_batch_token_ids_host / _device)."""
+    _fields_ = [("n_tok", C.c_uint64), ("n_unknown", C.c_uint64), ("tok_id", C.c_void_p)]
 
 
 SLICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)
@@ -251,6 +261,23 @@ def lib():
     L.dtk_stream_sentences.argtypes = [vp, C.POINTER(StreamSens)]
     for f in (L.dtk_blk64_start, L.dtk_blk64_end):
         f.argtypes, f.restype = [vp, vp, u64], C.c_int64
+    L.dtk_vocab_create.argtypes = [vp, vp, u32, C.POINTER(vp)]
+    L.dtk_vocab_free.argtypes = [vp]
+    L.dtk_vocab_free.restype = None
+    L.dtk_vocab_size.argtypes = [vp]
+    L.dtk_vocab_size.restype = u32
+    L.dtk_vocab_probe_mem.argtypes = [vp, vp, u32, vp, sz, C.POINTER(C.c_int32)]
+    L.dtk_tally_create.argtypes = [vp, C.POINTER(vp)]
+    L.dtk_tally_read.argtypes = [vp, vp]
+    L.dtk_tally_reset.argtypes = [vp]
+    L.dtk_tally_free.argtypes = [vp]
+    L.dtk_tally_free.restype = None
+    L.dtk_batch_set_vocab.argtypes = [vp, vp, vp, C.c_int]
+    L.dtk_batch_token_ids_device.argtypes = [vp, C.POINTER(TokenIdView)]
+    L.dtk_batch_token_ids_host.argtypes = [vp, C.POINTER(TokenIdView)]
+    L.dtk_pipeline_set_vocab.argtypes = [vp, vp, vp, C.c_int]
+    L.dtk_stream_set_vocab.argtypes = [vp, vp, vp, C.c_int]
+    L.dtk_stream_token_ids.argtypes = [vp, C.POINTER(TokenIdView)]
     L.dtk_stream_run.argtypes = [vp, vp, READ_FN, vp, u32, STREAM_SLICE_FN, vp, C.POINTER(u32)]
     L.dtk_stream_transduce.argtypes = [vp, vp, READ_FN, vp, u32, C.POINTER(vp), C.POINTER(sz), C.POINTER(u32)]
     for f in (L.dtk_blk_start, L.dtk_blk_end):

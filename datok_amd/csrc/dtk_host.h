@@ -11,6 +11,7 @@
 #include "dtk_internal.h"
 #include "dtk_own.h"  // the error state (hip_fail, HIP_TRY) and the owning types
 #include "dtk_mirror.h"
+#include "dtk_vocab_core.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -44,6 +45,8 @@ struct DtkDebug {
                          // delivery also sizes its first copies of sent and the text rows with it (the late copy at delivery)
   int sen_cap = -1;      // rows the sentence table (DTK_R_SENTENCES) is first sized for, in place of n_sent (-1: off), so that
                          // ordinary text reaches the second build of a table that outgrew the bound
+  int vocab_hash_bits = -1;  // a vocabulary built from now on keeps only this many low bits of its hash, in the builder, the host
+                         // probe and the kernel alike (-1: off), so that a handful of words collide, share tags and wrap
   long long sp_posc0 = 0; // posC in front of a stream's first slice in a position mode or with offset delivery (dtk_stream_run reads it once, at its
                          // start): integers beyond 2^32 and of 11 digits from a stream of a few hundred bytes
 };
@@ -82,6 +85,22 @@ int gunzip(const uint8_t *gz, size_t n, std::vector<uint8_t> &out);
 bool special_ids_ok(const dtk_model *m);
 int layout_matrix(dtk_model *m, const std::vector<uint32_t> &arr, uint64_t n_states, bool da_dense);
 int build_foma(dtk_model *m, const std::vector<uint8_t> &raw);
+
+// ------------------------------------------------------ vocabulary and tally (dtk_vocab.cpp)
+//
+// The table of dtk_vocab_core.h on one device, immutable after creation; the counters of dtk_tally beside it.
+struct dtk_vocab {
+  int device = 0;
+  uint32_t n_words = 0;
+  DevArray<uint64_t> d_slots;
+  DevArray<uint32_t> d_off, d_bytes;  // (the words' bytes in whole 32-bit words: the kernel reads them as such)
+  DtkVocabDev dev{};
+};
+struct dtk_tally {
+  int device = 0;
+  uint32_t n_words = 0;
+  DevArray<unsigned long long> d_counts;  // n_words + 1, the last: unknown
+};
 
 // ------------------------------------------------------ a stream slice's device outputs
 //
@@ -280,6 +299,20 @@ struct dtk_batch {
   bool sen_done = false;           // the count has been looked at and fits (and exact documents are spliced in)
   uint64_t sen_n = 0;              // rows of the finished table
   uint64_t sen_need = 0;           // nonzero: this run's table has that many rows, more than the bound
+  // dtk_batch_set_vocab: every token of a run looked up in a vocabulary (dtk_tokenid.hip), on the download stream behind
+  // finish().  One block of dtk_mirror.h: the unknown counter, then one id per token; the counter always comes home,
+  // the ids with ids_home or when dtk_batch_token_ids_host asks.  The kernel runs once per run, so a tally gets a run's
+  // tokens once however often the ids are asked for or copied.
+  const dtk_vocab *vocab = nullptr;
+  dtk_tally *tally = nullptr;
+  bool ids_home = false;
+  struct Ids : MirrorBlock {
+    Piece<uint64_t> cnt;
+    Piece<int32_t> id;
+  } ids;
+  Event ev_ids;                    // behind the lookup and the last enqueued copy of its block
+  bool ids_built = false;          // the lookup has been enqueued for this run
+  bool ids_waited = true;          // ev_ids has been waited for
   uint64_t max_doc_bytes = 0;     // of the current input (what decides whether the narrow form exists)
   bool max_doc_valid = false;
   Stream dl_stream;                 // created with the first download, unless the caller lends one (a pipeline's slices share one:
@@ -313,6 +346,7 @@ DtkSym sym_of(const dtk_batch *b);
 DtkWalkArgs walk_args(dtk_batch *b);
 int finish(dtk_batch *b);
 int launch_to_host(dtk_batch *b);
+int ids_wait(dtk_batch *b);  // what the last lookup enqueued has finished (the text and the block may be touched again)
 // The next runs of a one-document batch walk a slice of a stream: open_slice (0: the window ends where the stream
 // does) and the record to start from (null: the stream's beginning).  batch_cut: the last run's cut block, behind finish().
 int batch_set_slice(dtk_batch *b, uint32_t open_slice, const DtkLaneState *carry);

@@ -61,7 +61,7 @@ extern "C" int dtk_debug_configure(const char *key, const char *value) {
       {"COMPACT_FULL", &g_dbg.compact_full, true}, {"CLEAR_KERNEL", &g_dbg.clear_kernel, true},
       {"ROUND_LIMIT", &g_dbg.round_limit, false}, {"DEBUG_REPAIR", &g_dbg.debug_repair, true},
       {"BLK_SPAN", &g_dbg.blk_span, false}, {"EVL_CAP", &g_dbg.evl_cap, false},
-      {"SEN_CAP", &g_dbg.sen_cap, false}};
+      {"SEN_CAP", &g_dbg.sen_cap, false}, {"VOCAB_HASH_BITS", &g_dbg.vocab_hash_bits, false}};
   if (strncmp(key, "DATOK_", 6) == 0) key += 6;
   if (strcmp(key, "SP_POSC0") == 0) {  // (a 64-bit value)
     g_dbg.sp_posc0 = value ? atoll(value) : 0;

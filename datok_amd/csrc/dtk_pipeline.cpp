@@ -23,6 +23,8 @@ struct dtk_pipeline {
   std::vector<uint8_t> touched;        // an upload into the slot may be under way (error paths wait for it)
   std::vector<uint64_t> off;           // rebased offsets of the slice being submitted
   uint32_t fields = 0;                 // DTK_R_*: result arrays brought to the host for every slice (0: none)
+  bool vocab = false;                  // dtk_pipeline_set_vocab: every slice's tokens are looked up before it is handed over
+  uint32_t run_flags = 0;              // of the run in progress
   // Three streams for the whole pipeline, whatever its depth: uploads, kernels, downloads (the HIP runtime maps streams
   // onto four hardware queues; streams that share a queue serialise -- a stream per slot made depth 4 slower than 3).
   // Slices take turns on each: the link carries slice i + 2 in and slice i out while slice i + 1 is walked.
@@ -89,6 +91,16 @@ extern "C" int dtk_pipeline_set_result_fields(dtk_pipeline *p, uint32_t fields) 
   return DTK_OK;
 }
 
+extern "C" int dtk_pipeline_set_vocab(dtk_pipeline *p, const dtk_vocab *v, dtk_tally *t, int ids_home) {
+  if (!p) return DTK_E_ARG;
+  for (dtk_batch *b : p->slots) {
+    const int rc = dtk_batch_set_vocab(b, v, t, ids_home);
+    if (rc != DTK_OK) return rc;
+  }
+  p->vocab = v != nullptr;
+  return DTK_OK;
+}
+
 // Slices whose kernels have finished start their way home now (nothing here blocks; the copies queue up on the download
 // stream in slice order): the download of slice i runs under the walk of slice i + 1 and the upload of slice i + 2.
 static void begin_downloads(dtk_pipeline *p, uint32_t oldest) {
@@ -109,6 +121,12 @@ static int deliver(dtk_pipeline *p, uint32_t slot, dtk_slice_fn fn, void *user) 
   int rc = dtk_batch_totals(p->slots[slot], &t);  // waits for the slice; repairs, capacity check
   if (rc == DTK_OK && p->fields) rc = dtk_batch_download_begin(p->slots[slot]);
   begin_downloads(p, slot);  // (the next slices' copies behind this one's, before the callback waits for its own)
+  // the slice's lookup has run when the slice is handed over (with result fields it started with the download above;
+  // a run without byte offsets has no ids)
+  if (rc == DTK_OK && p->vocab && !(p->run_flags & DTK_NO_BYTE_OFFSETS)) {
+    dtk_token_id_view ids;
+    rc = dtk_batch_token_ids_device(p->slots[slot], &ids);
+  }
   const uint32_t first = p->first[slot], n = p->count[slot];
   p->count[slot] = 0;
   p->touched[slot] = 0;
@@ -153,6 +171,7 @@ struct HostLock {
 static int run_slices(dtk_pipeline *p, const dtk_model *m, const uint8_t *text, const uint64_t *doc_off, const Slice *sl,
                       size_t n_slices, uint32_t flags, dtk_slice_fn fn, void *user, const volatile int *stop) {
   const uint32_t depth = (uint32_t)p->slots.size();
+  p->run_flags = flags;
   int rc = DTK_OK;
   size_t k = 0;
   for (; k < n_slices && rc == DTK_OK; k++) {

@@ -281,7 +281,83 @@ int sen_finish(dtk_batch *b, bool home) {
   b->sen_done = true;
   return DTK_OK;
 }
+
+// ---- dtk_batch_set_vocab: the tokens' ids (dtk_tokenid.hip; the definition is in include/datok_gpu.h)
+
+// Enqueues on the download stream what is still missing of: the lookup (once per run: it also feeds the tally), the
+// copy of the unknown counter, and (home) the copy of the ids.  The run is complete (finish()), so the token count is
+// final and the block is sized exactly.
+int ids_enqueue(dtk_batch *b, bool home) {
+  if (!b->vocab || (b->last_flags & DTK_NO_BYTE_OFFSETS)) return DTK_E_STATE;  // (the keys are cut out with tok_bstart / tok_bend)
+  if (!dtk_batch_download_stream(b)) return hip_fail(hipGetLastError(), "download stream");
+  dtk_batch::Ids &L = b->ids;
+  const uint64_t nt = b->totals.n_tokens;
+  int rc;
+  if (!b->ids_built) {
+    L.clear();
+    L.add(L.cnt, 1); L.add(L.id, nt);
+    if ((rc = L.fit()) != DTK_OK) return rc;
+    HIP_TRY(hipMemsetAsync(L.dev(L.cnt), 0, sizeof(uint64_t), b->dl_stream));
+    DtkTokenIdArgs a{};
+    a.text = b->d_text; a.total = b->total; a.doc_off = b->d_off; a.n_docs = b->n_docs;
+    a.tok_off = b->d_tok_off; a.tok_bstart = b->d_bstart; a.tok_bend = b->d_bend; a.n_tok = nt;
+    if (b->n_invalid) { const DtkSym s = sym_of(b); a.sym_base = s.base; a.sym_lut = s.lut; }
+    a.vocab = b->vocab->dev;
+    a.tok_id = L.dev(L.id);
+    a.n_unknown = reinterpret_cast<unsigned long long *>(L.dev(L.cnt));
+    a.tally = b->tally ? b->tally->d_counts.p : nullptr;
+    if (dtk_launch_token_ids(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "token ids");
+    b->ids_built = true;
+    L.bring(L.cnt, 1);
+  }
+  if (home) L.bring(L.id, nt);
+  if (L.pending.empty()) return DTK_OK;
+  if ((rc = L.issue(b->dl_stream)) != DTK_OK || (rc = b->ev_ids.ensure(hipEventDisableTiming)) != DTK_OK) return rc;
+  HIP_TRY(hipEventRecord(b->ev_ids, b->dl_stream));
+  b->ids_waited = false;
+  return DTK_OK;
+}
+
+// The ids, complete: on the device, and (home) in the page-locked block.
+int ids_finish(dtk_batch *b, bool home, dtk_token_id_view *o) {
+  int rc = finish(b);
+  if (rc != DTK_OK) return rc;
+  if ((rc = ids_enqueue(b, home || b->ids_home)) != DTK_OK || (rc = ids_wait(b)) != DTK_OK) return rc;
+  const dtk_batch::Ids &L = b->ids;
+  o->n_tok = b->totals.n_tokens;
+  o->n_unknown = *L.host(L.cnt);
+  o->tok_id = L.in(home ? L.h.p : static_cast<void *>(L.d.p), L.id);
+  return DTK_OK;
+}
 }  // namespace
+
+int ids_wait(dtk_batch *b) {
+  if (b->ids_waited) return DTK_OK;
+  HIP_TRY(hipEventSynchronize(b->ev_ids));
+  b->ids_waited = true;
+  b->ids.landed();
+  return DTK_OK;
+}
+
+extern "C" int dtk_batch_set_vocab(dtk_batch *b, const dtk_vocab *v, dtk_tally *t, int ids_home) {
+  if (!b || (!v && t)) return DTK_E_ARG;
+  if (v && (v->device != b->device || (t && (t->device != b->device || t->n_words != v->n_words)))) return DTK_E_ARG;
+  const int rc = ids_wait(b);  // (a lookup under way reads the vocabulary that was attached)
+  if (rc != DTK_OK) return rc;
+  // (another vocabulary: the finished run, if any, is looked up anew when its ids are asked for; the same one again
+  //  keeps what was computed, so a run's tokens reach a tally once)
+  if (v != b->vocab) b->ids_built = false;
+  b->vocab = v; b->tally = t; b->ids_home = v && ids_home != 0;
+  return DTK_OK;
+}
+
+extern "C" int dtk_batch_token_ids_device(dtk_batch *b, dtk_token_id_view *o) {
+  return !b || !o ? DTK_E_ARG : ids_finish(b, false, o);
+}
+
+extern "C" int dtk_batch_token_ids_host(dtk_batch *b, dtk_token_id_view *o) {
+  return !b || !o ? DTK_E_ARG : ids_finish(b, true, o);
+}
 
 extern "C" int dtk_batch_sentences_device(dtk_batch *b, dtk_sentence_view *o) {
   if (!b || !o) return DTK_E_ARG;
@@ -365,6 +441,8 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
   if (!b) return DTK_E_ARG;
   int rc = finish(b);
   if (rc != DTK_OK) return rc;
+  // the tokens' ids (dtk_batch_set_vocab): no result field, they ride in front of the fields' copies
+  if (b->vocab && !(b->last_flags & DTK_NO_BYTE_OFFSETS) && (rc = ids_enqueue(b, b->ids_home)) != DTK_OK) return rc;
   uint32_t sel = b->fields & (DTK_R_ALL | DTK_R_TOK_RUNE16 | kBlkFields | DTK_R_EVENT_LIST | DTK_R_SENTENCES);
   if (sel & DTK_R_TOK_RUNE16) {
     // the narrow form holds every offset of a document of at most 32 767 bytes; a batch with a longer one gets the
@@ -437,6 +515,7 @@ extern "C" int dtk_batch_result_host(dtk_batch *b, dtk_result_view *o) {
   int rc = dtk_batch_download_begin(b);
   if (rc != DTK_OK) return rc;
   if (!b->dl_waited) { HIP_TRY(hipEventSynchronize(b->ev_dl)); b->dl_waited = true; }
+  if ((rc = ids_wait(b)) != DTK_OK) return rc;  // (a lookup that download_begin enqueued: the batch has been waited for)
   if (b->blk_pending) {
     // A blocked pair with a block that does not fit 16 bits: its 32-bit arrays come over now and the blocked pointers
     // stay NULL.  blk_failed holds for the rest of the run: a second call neither copies again nor flips forms.

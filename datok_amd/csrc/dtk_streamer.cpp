@@ -36,6 +36,9 @@ struct dtk_stream {
   // slots of its own with the same rule.
   bool sens = false;
   DevArray<DtkSenCarry> d_sen_carry;  // depth + 1
+  // dtk_stream_set_vocab: the slots' batches look their tokens up (dtk_batch_set_vocab); nothing crosses a cut
+  bool vocab = false;
+  bool ids_home = false;
   // Position rendering and offset delivery follow the writer's state, which is chained on the device: slice k reads
   // carry slot k % (depth + 1) and writes the next one -- never the slot it read, and a slot is written again only by
   // slice k + depth, which takes the batch that slice k has left by then.
@@ -52,6 +55,8 @@ struct dtk_stream {
     SoView offs{};
     bool sens_set = false;                // the sentence rows: sens is this slice's
     SsView sens{};
+    bool ids_set = false;                 // the tokens' ids: ids is this slice's
+    dtk_token_id_view ids{};
   } cur;
   Stream s_up, s_run, s_down;
   std::vector<dtk_batch *> slots;
@@ -159,6 +164,24 @@ extern "C" int dtk_stream_set_sentences(dtk_stream *s, int on) {
   if (!s) return DTK_E_ARG;
   if (on && s->bytes == SliceRequest::kPosBytes) return DTK_E_ARG;
   s->sens = on != 0;
+  return DTK_OK;
+}
+
+extern "C" int dtk_stream_set_vocab(dtk_stream *s, const dtk_vocab *v, dtk_tally *t, int ids_home) {
+  if (!s) return DTK_E_ARG;
+  for (dtk_batch *b : s->slots) {
+    const int rc = dtk_batch_set_vocab(b, v, t, ids_home);
+    if (rc != DTK_OK) return rc;
+  }
+  s->vocab = v != nullptr;
+  s->ids_home = v && ids_home != 0;
+  return DTK_OK;
+}
+
+extern "C" int dtk_stream_token_ids(dtk_stream *s, dtk_token_id_view *o) {
+  if (!s || !o) return DTK_E_ARG;
+  if (!s->cur.ids_set) return DTK_E_STATE;
+  *o = s->cur.ids;
   return DTK_OK;
 }
 
@@ -379,6 +402,13 @@ struct Run {
     if (s->sens) {
       if ((rc = batch_sens_out(b, &s->cur.sens)) != DTK_OK) return rc;
       s->cur.sens_set = true;
+    }
+    if (s->vocab) {
+      // (the lookup was enqueued with the slice's download, take_cut; this waits for it, so a tally holds the slice)
+      rc = s->ids_home ? dtk_batch_token_ids_host(b, &s->cur.ids) : dtk_batch_token_ids_device(b, &s->cur.ids);
+      if (rc != DTK_OK) return rc;
+      if (!s->ids_home) s->cur.ids.tok_id = nullptr;  // (host pointers only)
+      s->cur.ids_set = true;
     }
     rc = slice_fn ? slice_fn(slice_user, &sl) : DTK_OK;
     s->cur = {};

@@ -245,16 +245,20 @@ class SliceView:
     With Stream.set_sentences the slice brings the sentences its calls close, as rows (dtk_stream_sentences; None when
     it is off): s_tok_end (uint32: tokens of THIS slice up to and including the row's last), s_bstart / s_bend (uint64,
     stream byte offsets), s_rstart / s_rend (int64, the writer's rune offsets), s_text_sen_end (rows of THIS slice closed
-    in front of each TextEnd), s_carry_in / s_carry_out (the row open at the cut: (open, bstart, bend, rstart, rend))."""
+    in front of each TextEnd), s_carry_in / s_carry_out (the row open at the cut: (open, bstart, bend, rstart, rend)).
+    With Stream.set_vocab the slice brings tok_id (np.int32, one per token of the slice; None with ids_home=False) and
+    n_unknown (dtk_stream_token_ids; both None when it is off)."""
     __slots__ = ("base", "first", "cut", "text", "last", "status", "tok_bstart", "tok_bend", "evl_pos", "evl_kind", "tail",
                  "out", "splice_pos", "splice_sent", "open_pos", "open_sent", "carry_in", "carry_out", "written",
                  "r_tok_rstart", "r_tok_rend", "r_blocked", "r_rblk", "r_rblk_head", "r_sent", "r_text_tok_end",
                  "r_text_sent_end", "r_carry_in", "r_carry_out",
-                 "s_tok_end", "s_bstart", "s_bend", "s_rstart", "s_rend", "s_text_sen_end", "s_carry_in", "s_carry_out")
+                 "s_tok_end", "s_bstart", "s_bend", "s_rstart", "s_rend", "s_text_sen_end", "s_carry_in", "s_carry_out",
+                 "tok_id", "n_unknown")
     _NONE = ("out", "splice_pos", "splice_sent", "open_pos", "open_sent", "carry_in", "carry_out", "written",
              "r_tok_rstart", "r_tok_rend", "r_blocked", "r_rblk", "r_rblk_head", "r_sent", "r_text_tok_end",
              "r_text_sent_end", "r_carry_in", "r_carry_out",
-             "s_tok_end", "s_bstart", "s_bend", "s_rstart", "s_rend", "s_text_sen_end", "s_carry_in", "s_carry_out")
+             "s_tok_end", "s_bstart", "s_bend", "s_rstart", "s_rend", "s_text_sen_end", "s_carry_in", "s_carry_out",
+             "tok_id", "n_unknown")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -509,6 +513,81 @@ class SentenceTable:
                     sen_rend=None if self.sen_rend is None else self.sen_rend[a:b])
 
 
+def _pack_words(words):
+    """A list of bytes objects as dtk_vocab_create takes it: the bytes back to back and n + 1 uint64 offsets."""
+    words = [bytes(w) for w in words]
+    off = np.zeros(len(words) + 1, np.uint64)
+    if words:
+        off[1:] = np.cumsum([len(w) for w in words], dtype=np.uint64)
+    blob = np.frombuffer(b"".join(words), dtype=np.uint8) if int(off[-1]) else np.zeros(1, np.uint8)
+    return blob, off, len(words)
+
+
+class Vocab:
+    """dtk_vocab: an ordered list of byte strings on the device; a token's id is the index of the word equal to its
+    surface as the writer prints it (invalid bytes as U+FFFD), the lowest one of equal words, or -1.  Immutable and
+    shareable between batches."""
+
+    def __init__(self, words):
+        blob, off, n = _pack_words(words)
+        self._h = C.c_void_p()
+        check(lib().dtk_vocab_create(blob.ctypes.data, off.ctypes.data, n, C.byref(self._h)), "dtk_vocab_create")
+
+    @property
+    def size(self):
+        return int(lib().dtk_vocab_size(self._h))
+
+    @staticmethod
+    def probe(words, key: bytes) -> int:
+        """dtk_vocab_probe_mem: the id of `key` (its bytes after replacement) in `words`, looked up on the host with the
+        table and the probe the kernel uses.  Needs no device."""
+        blob, off, n = _pack_words(words)
+        key = bytes(key)
+        kb = np.frombuffer(key, dtype=np.uint8) if key else np.zeros(1, np.uint8)
+        out = C.c_int32(0)
+        check(lib().dtk_vocab_probe_mem(blob.ctypes.data, off.ctypes.data, n, kb.ctypes.data, len(key), C.byref(out)),
+              "dtk_vocab_probe_mem")
+        return int(out.value)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib().dtk_vocab_free(h)
+
+    __del__ = close
+
+
+class Tally:
+    """dtk_tally: size + 1 exact 64-bit counters beside a vocabulary; every run of a batch, pipeline or stream it is
+    attached to adds its tokens once, the unknown ones to the last counter."""
+
+    def __init__(self, vocab: Vocab):
+        self._h = C.c_void_p()
+        self._vocab = vocab   # (kept alive)
+        self.size = vocab.size
+        check(lib().dtk_tally_create(vocab._h, C.byref(self._h)), "dtk_tally_create")
+
+    def read(self) -> np.ndarray:
+        out = np.zeros(self.size + 1, np.uint64)
+        check(lib().dtk_tally_read(self._h, out.ctypes.data), "dtk_tally_read")
+        return out
+
+    def reset(self):
+        check(lib().dtk_tally_reset(self._h), "dtk_tally_reset")
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib().dtk_tally_free(h)
+
+    __del__ = close
+
+
+def _set_vocab(fn, name, owner, v, tally, ids_home):
+    check(fn(owner._h, v._h if v is not None else None, tally._h if tally is not None else None, 1 if ids_home else 0), name)
+    owner._vocab = (v, tally)   # (they must outlive the owner's use of them)
+
+
 class Batch:
     """dtk_batch: device buffers + one HIP stream for many documents per launch."""
 
@@ -663,6 +742,27 @@ class Batch:
                 setattr(t, n, a.copy() if copy else a)
         return t
 
+    def set_vocab(self, v, tally=None, ids_home=True):
+        """Every token of the next runs is looked up in the Vocab `v` (None: off) behind the run, on the download
+        stream; `tally` (a Tally of v) gets each run's tokens once.  ids_home: the ids come home with the other result
+        copies (download_begin / result); False: they stay in HBM until token_ids() asks."""
+        _set_vocab(lib().dtk_batch_set_vocab, "dtk_batch_set_vocab", self, v, tally, ids_home)
+
+    def token_ids(self, device=False, copy=True):
+        """The last run's ids: (np.int32 array in the order tok_off indexes, n_unknown).  copy=False: a view of the batch's
+        page-locked block, valid until its next run.  device=True: the raw dtk_token_id_view (tok_id is a device
+        pointer).  E_STATE before a run, without a vocabulary and after a run with NO_BYTE_OFFSETS."""
+        v = _lib.TokenIdView()
+        fn = lib().dtk_batch_token_ids_device if device else lib().dtk_batch_token_ids_host
+        check(fn(self._h, C.byref(v)), "dtk_batch_token_ids_device" if device else "dtk_batch_token_ids_host")
+        if device:
+            return v
+        n = int(v.n_tok)
+        if n == 0:
+            return np.zeros(0, np.int32), int(v.n_unknown)
+        a = np.frombuffer((C.c_char * (n * 4)).from_address(v.tok_id), dtype=np.int32)
+        return (a.copy() if copy else a), int(v.n_unknown)
+
     def set_result_fields(self, fields=R_ALL):
         """Which arrays result() brings to the host (the others come back empty)."""
         check(lib().dtk_batch_set_result_fields(self._h, int(fields)), "dtk_batch_set_result_fields")
@@ -757,6 +857,11 @@ class Pipeline:
     def set_chunking(self, chunk_bytes=0xFFFFFFFF, warm_bytes=8):
         check(lib().dtk_pipeline_set_chunking(self._h, int(chunk_bytes), int(warm_bytes)), "dtk_pipeline_set_chunking")
 
+    def set_vocab(self, v, tally=None, ids_home=True):
+        """Batch.set_vocab for every slice: on_slice reads a slice's ids with batch.token_ids(); every slice's lookup
+        has run when the slice is handed over, so a Tally holds the whole corpus when run() returns."""
+        _set_vocab(lib().dtk_pipeline_set_vocab, "dtk_pipeline_set_vocab", self, v, tally, ids_home)
+
     def set_result_fields(self, fields):
         """Bring these result arrays (Batch.R_*) of every slice to the host, overlapped with the next slices' work."""
         check(lib().dtk_pipeline_set_result_fields(self._h, int(fields)), "dtk_pipeline_set_result_fields")
@@ -819,6 +924,12 @@ class Stream:
         unpack_blocked64); None turns it off.  Works beside set_render; E_ARG while set_position_render is on."""
         check(lib().dtk_stream_set_offsets(self._h, 0 if form is None else 1, 0 if form is None else int(form)),
               "dtk_stream_set_offsets")
+
+    def set_vocab(self, v, tally=None, ids_home=True):
+        """Every SliceView brings tok_id (np.int32, one per token of the slice: the slices' ids one behind the other are
+        the ids of the stream as one document) and n_unknown; `tally` gets every slice's tokens once.  ids_home=False:
+        tok_id stays None (a tally alone: nothing per token leaves the device).  None turns it off."""
+        _set_vocab(lib().dtk_stream_set_vocab, "dtk_stream_set_vocab", self, v, tally, ids_home)
 
     def set_sentences(self, on):
         """Every SliceView brings the sentences its calls close as rows (s_tok_end, s_bstart, s_bend, s_rstart, s_rend,
@@ -959,6 +1070,15 @@ def _slice_sentences(h) -> dict:
                 s_carry_in=carry(ss.carry_in), s_carry_out=carry(ss.carry_out))
 
 
+def _slice_token_ids(h) -> dict:
+    """What dtk_stream_token_ids says about the slice being delivered ({}: no vocabulary is attached)."""
+    v = _lib.TokenIdView()
+    if not h or lib().dtk_stream_token_ids(h, C.byref(v)) != _lib.OK:
+        return {}
+    return dict(tok_id=_host_array(v.tok_id, int(v.n_tok), np.int32) if v.tok_id or not v.n_tok else None,
+                n_unknown=int(v.n_unknown))
+
+
 def _slice_view(s, stream=None) -> SliceView:
     """Host copies of a dtk_stream_slice (its buffers are only valid inside the callback)."""
     v = s.view
@@ -976,7 +1096,7 @@ def _slice_view(s, stream=None) -> SliceView:
                      tok_bstart=bs, tok_bend=be, evl_pos=arr(v.evl_pos, ne, np.uint32)[int(off[0]):],
                      evl_kind=arr(v.evl_kind, ne, np.uint8)[int(off[0]):], tail=int(arr(v.doc_tail, 1, np.uint32)[0]),
                      out=C.string_at(s.out, int(s.out_len)) if s.out else None, **_slice_positions(stream),
-                     **_slice_offsets(stream), **_slice_sentences(stream))
+                     **_slice_offsets(stream), **_slice_sentences(stream), **_slice_token_ids(stream))
 
 
 def _slice_callback(on_slice, doc_off, err):

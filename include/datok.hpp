@@ -567,4 +567,62 @@ inline std::vector<SentenceRow> sentence_rows(const dtk_sentence_view &v, uint32
   return rows;
 }
 
+// ---- every token looked up in a vocabulary on the device (dtk_vocab, dtk_tally, datok_gpu.h): type ids and a
+// frequency list.  A token's id is the index of the word equal to its surface as the writer prints it (invalid bytes
+// as U+FFFD), the lowest one of equal words, or DTK_ID_UNKNOWN.
+class Vocab {
+ public:
+  // ok() is false, with a log line, when the table could not be made (no device, more than 2^31 - 2 words, 2^32 bytes).
+  explicit Vocab(const std::vector<std::string> &words) {
+    std::string bytes;
+    std::vector<uint64_t> off(1, 0);
+    for (const std::string &w : words) { bytes += w; off.push_back(bytes.size()); }
+    const int rc = dtk_vocab_create(reinterpret_cast<const uint8_t *>(bytes.data()), off.data(), (uint32_t)words.size(), &v_);
+    if (rc != DTK_OK) std::fprintf(stderr, "datok: vocabulary: %s\n", dtk_strerror(rc));
+  }
+  ~Vocab() { dtk_vocab_free(v_); }
+  Vocab(const Vocab &) = delete;
+  Vocab &operator=(const Vocab &) = delete;
+  bool ok() const { return v_ != nullptr; }
+  uint32_t size() const { return dtk_vocab_size(v_); }
+  const dtk_vocab *get() const { return v_; }
+
+ private:
+  dtk_vocab *v_ = nullptr;
+};
+
+// The counters of a frequency list beside a Vocab: attach with dtk_batch_set_vocab / dtk_pipeline_set_vocab /
+// dtk_stream_set_vocab; every run adds its tokens once.
+class Tally {
+ public:
+  explicit Tally(const Vocab &v) : n_(v.size()) {
+    const int rc = dtk_tally_create(v.get(), &t_);
+    if (rc != DTK_OK) std::fprintf(stderr, "datok: tally: %s\n", dtk_strerror(rc));
+  }
+  ~Tally() { dtk_tally_free(t_); }
+  Tally(const Tally &) = delete;
+  Tally &operator=(const Tally &) = delete;
+  bool ok() const { return t_ != nullptr; }
+  dtk_tally *get() const { return t_; }
+  // size() + 1 counts, the last one the unknown tokens'; empty on failure
+  std::vector<uint64_t> read() const {
+    std::vector<uint64_t> counts((size_t)n_ + 1);
+    if (!t_ || dtk_tally_read(t_, counts.data()) != DTK_OK) counts.clear();
+    return counts;
+  }
+  bool reset() { return t_ && dtk_tally_reset(t_) == DTK_OK; }
+
+ private:
+  dtk_tally *t_ = nullptr;
+  uint32_t n_ = 0;
+};
+
+// The last run's ids in page-locked host memory (device: device pointers), valid until the batch's next run; false + log
+// line on failure (before a run, without a vocabulary, or after a run with DTK_NO_BYTE_OFFSETS).
+inline bool token_ids(dtk_batch *b, dtk_token_id_view *out, bool device = false) {
+  const int rc = device ? dtk_batch_token_ids_device(b, out) : dtk_batch_token_ids_host(b, out);
+  if (rc != DTK_OK) std::fprintf(stderr, "datok: token ids: %s\n", dtk_strerror(rc));
+  return rc == DTK_OK;
+}
+
 }  // namespace datok

@@ -438,6 +438,55 @@ typedef struct {
 int dtk_batch_sentences_device(dtk_batch *b, dtk_sentence_view *out);
 int dtk_batch_sentences_host(dtk_batch *b, dtk_sentence_view *out);
 
+/* ---- every token looked up in a vocabulary, on the device: type ids and a frequency list.
+ *      A VOCABULARY is an ordered list of n_words byte strings (any bytes, empty ones too; at most 2^31 - 2 words and
+ *      less than 2^32 bytes in all; of equal words the lowest index wins).  The KEY of a token is its surface as the
+ *      reference's writer prints it, string(buf[offset:]) (token_writer.go:85,93): the document's bytes
+ *      [tok_bstart, tok_bend) with every byte that does not decode (Go's DecodeRune: U+FFFD of width 1) replaced by
+ *      EF BF BD -- what dtk_batch_render_* print, so a literal U+FFFD and an invalid byte give the same key.
+ *      tok_id[i], in the batch-wide token order that tok_off indexes, is the index of the word equal to token i's key,
+ *      or DTK_ID_UNKNOWN.  A row with tok_bstart > tok_bend (DTK_ST_BAD_OFFSET documents only) gets DTK_ID_UNKNOWN; the
+ *      rows of a document with a status bit are looked up by the same rule on what was delivered for them, clamped to
+ *      the document.  The result is exact: the table is hashed, but a match is decided by comparing the bytes.
+ *        The object is built on the host and copied to the device of the calling thread (dtk_set_device); immutable
+ *      afterwards and shareable between batches and threads, like a dtk_model.  Without a device dtk_vocab_create
+ *      returns DTK_E_NO_DEVICE; offsets that do not ascend from 0 or exceed the limits are DTK_E_ARG.
+ *      dtk_vocab_probe_mem needs no device: it builds the same table on the host and looks one key (the bytes after
+ *      replacement) up with the code the kernel uses. ---- */
+#define DTK_ID_UNKNOWN (-1)
+typedef struct dtk_vocab dtk_vocab;
+/* words: bytes[off[w] .. off[w+1]), off[0] == 0 */
+int dtk_vocab_create(const uint8_t *bytes, const uint64_t *off, uint32_t n_words, dtk_vocab **out);
+void dtk_vocab_free(dtk_vocab *v);
+uint32_t dtk_vocab_size(const dtk_vocab *v);
+int dtk_vocab_probe_mem(const uint8_t *bytes, const uint64_t *off, uint32_t n_words,
+                        const uint8_t *key, size_t key_len, int32_t *id);
+/* A tally: n_words + 1 64-bit counters on the vocabulary's device (the calling thread's must be that one, else
+ * DTK_E_ARG), zero at creation.  Every run of a batch it is attached to adds that run's tokens exactly once -- 1 to the
+ * counter of each token's id, unknown tokens to counter n_words -- when the run's lookup executes, however often the ids
+ * are asked for or copied afterwards.  Integer adds: the counts are exact.  dtk_tally_read copies the counters to
+ * counts[n_words + 1]: the sum over all lookups whose batch has been waited for -- an ids view was obtained,
+ * dtk_batch_result_host returned, or the pipeline or stream run returned.  A frequency list needs nothing per token to
+ * leave the device. */
+typedef struct dtk_tally dtk_tally;
+int dtk_tally_create(const dtk_vocab *v, dtk_tally **out);
+int dtk_tally_read(dtk_tally *t, uint64_t *counts);
+int dtk_tally_reset(dtk_tally *t);
+void dtk_tally_free(dtk_tally *t);
+/* v == NULL: off (the default; t must then be NULL too).  t may be NULL.  ids_home != 0: the ids are copied to
+ * page-locked memory with the other result copies (dtk_batch_download_begin); 0: they stay in HBM until
+ * dtk_batch_token_ids_host asks.  The vocabulary and the tally must outlive the batch's use of them and live on the
+ * batch's device (else DTK_E_ARG, also for a tally of another vocabulary size).
+ *   With a vocabulary attached dtk_batch_download_begin enqueues the lookup on the download stream, in front of the
+ * copies; dtk_batch_token_ids_* begin it if nobody has, wait for it, and return device resp. page-locked host pointers,
+ * valid until the batch's next run or free.  n_unknown counts the DTK_ID_UNKNOWN among the n_tok ids.  DTK_E_STATE before
+ * a run, without a vocabulary, and after a run with DTK_NO_BYTE_OFFSETS.  No DTK_R_* bit belongs to the ids, and
+ * dtk_result_view does not know them. */
+int dtk_batch_set_vocab(dtk_batch *b, const dtk_vocab *v, dtk_tally *t, int ids_home);
+typedef struct { uint64_t n_tok, n_unknown; const int32_t *tok_id; } dtk_token_id_view;
+int dtk_batch_token_ids_device(dtk_batch *b, dtk_token_id_view *out);
+int dtk_batch_token_ids_host(dtk_batch *b, dtk_token_id_view *out);
+
 /* bit of position 0 of document d in the bitmaps of dtk_result_view.ev_bits */
 #define DTK_EVENT_BIT(doc_off_d, d) (((uint64_t)(doc_off_d)) + (uint64_t)(d))
 
@@ -484,6 +533,11 @@ int dtk_pipeline_set_chunking(dtk_pipeline *p, uint32_t chunk_bytes, uint32_t wa
  * soon as its kernels have finished and run under the walk of slice i + 1 and the upload of slice i + 2; `fn` finds them
  * through dtk_batch_result_host.  0 (the default): results stay in HBM unless fn asks. */
 int dtk_pipeline_set_result_fields(dtk_pipeline *p, uint32_t fields);
+/* dtk_batch_set_vocab for every slice: `fn` finds a slice's ids through dtk_batch_token_ids_host (with result fields
+ * selected and ids_home set, the ids of slice i come home under the walk of slice i + 1); every slice's lookup has been
+ * waited for when `fn` gets the slice, so a tally holds the whole corpus when dtk_pipeline_run returns.  (dtk_multi_* has
+ * no counterpart: a vocabulary lives on one device.) */
+int dtk_pipeline_set_vocab(dtk_pipeline *p, const dtk_vocab *v, dtk_tally *t, int ids_home);
 int dtk_pipeline_run(dtk_pipeline *p, const dtk_model *m, const uint8_t *text, const uint64_t *doc_off,
                      uint32_t n_docs, uint32_t flags, dtk_slice_fn fn, void *user);
 /* ---- one stream of any length: the reference tokenizes whatever its reader delivers (bufio.Reader, matrix.go:373;
@@ -662,6 +716,15 @@ typedef struct {
 /* Inside slice_fn, with the sentence rows on: the slice being delivered (else DTK_E_STATE).  Page-locked host memory,
  * valid until slice_fn returns. */
 int dtk_stream_sentences(dtk_stream *s, dtk_stream_sens *o);
+/* ---- a stream's tokens looked up in a vocabulary (dtk_batch_set_vocab above), slice by slice.  A slice's batch is one
+ *      document whose token rows are exactly the slice's Token calls, its bytes lie in the window, and a token never
+ *      spans a cut: nothing is carried, every slice runs the batch's lookup behind its other outputs, and the slices' ids
+ *      one behind the other are the ids of the stream as one document.  dtk_stream_token_ids, inside slice_fn: the slice
+ *      being delivered (else DTK_E_STATE), page-locked host memory valid until slice_fn returns; with ids_home == 0 (a
+ *      tally alone) tok_id is NULL and the counts are still there.  Every slice's lookup has been waited for when it is
+ *      delivered.  dtk_stream_transduce leaves the vocabulary as set. ---- */
+int dtk_stream_set_vocab(dtk_stream *s, const dtk_vocab *v, dtk_tally *t, int ids_home);
+int dtk_stream_token_ids(dtk_stream *s, dtk_token_id_view *out);
 /* flags: DTK_NEWLINE_AFTER_EOT is accepted and changes nothing here (it only moves the writer's rune offsets), except
  * that with position rendering on it must be the bit dtk_stream_set_position_render got.  Short
  * reads are retried until a buffer is full; read_fn is not called again after it has returned 0. */

@@ -43,6 +43,8 @@ EXPORTS = [
     "dtk_tally_create", "dtk_tally_read", "dtk_tally_reset", "dtk_tally_free",
     "dtk_batch_set_vocab", "dtk_batch_token_ids_device", "dtk_batch_token_ids_host",
     "dtk_pipeline_set_vocab", "dtk_stream_set_vocab", "dtk_stream_token_ids",
+    "dtk_wordpiece_probe_mem", "dtk_batch_set_wordpiece", "dtk_batch_pieces_device", "dtk_batch_pieces_host",
+    "dtk_pipeline_set_wordpiece", "dtk_stream_set_wordpiece", "dtk_stream_pieces",
 ]
 ID_UNKNOWN = -1   # DTK_ID_UNKNOWN
 
@@ -87,6 +89,12 @@ class SentenceView(C.Structure):
 class TokenIdView(C.Structure):
     """dtk_token_id_view: a run's tokens looked up in a vocabulary (dtk_batch_token_ids_host / _device)."""
     _fields_ = [("n_tok", C.c_uint64), ("n_unknown", C.c_uint64), ("tok_id", C.c_void_p)]
+
+
+class PieceView(C.Structure):
+    """dtk_piece_view: a run's tokens split into WordPiece ids (dtk_batch_pieces_host / _device)."""
+    _fields_ = [("n_tok", C.c_uint64), ("n_pieces", C.c_uint64), ("n_unknown", C.c_uint64), ("piece_off", C.c_void_p),
+                ("piece_id", C.c_void_p), ("piece_bend", C.c_void_p)]
 
 
 SLICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)
@@ -278,6 +286,12 @@ def lib():
     L.dtk_pipeline_set_vocab.argtypes = [vp, vp, vp, C.c_int]
     L.dtk_stream_set_vocab.argtypes = [vp, vp, vp, C.c_int]
     L.dtk_stream_token_ids.argtypes = [vp, C.POINTER(TokenIdView)]
+    L.dtk_wordpiece_probe_mem.argtypes = [vp, vp, u32, vp, u32, C.c_int32, u32, vp, sz, vp, vp, u32, C.POINTER(u32)]
+    for f in (L.dtk_batch_set_wordpiece, L.dtk_pipeline_set_wordpiece, L.dtk_stream_set_wordpiece):
+        f.argtypes = [vp, vp, vp, u32, C.c_int32, u32, C.c_int]
+    L.dtk_batch_pieces_device.argtypes = [vp, C.POINTER(PieceView)]
+    L.dtk_batch_pieces_host.argtypes = [vp, C.POINTER(PieceView)]
+    L.dtk_stream_pieces.argtypes = [vp, C.POINTER(PieceView)]
     L.dtk_stream_run.argtypes = [vp, vp, READ_FN, vp, u32, STREAM_SLICE_FN, vp, C.POINTER(u32)]
     L.dtk_stream_transduce.argtypes = [vp, vp, READ_FN, vp, u32, C.POINTER(vp), C.POINTER(sz), C.POINTER(u32)]
     for f in (L.dtk_blk_start, L.dtk_blk_end):

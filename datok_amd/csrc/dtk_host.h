@@ -12,6 +12,7 @@
 #include "dtk_own.h"  // the error state (hip_fail, HIP_TRY) and the owning types
 #include "dtk_mirror.h"
 #include "dtk_vocab_core.h"
+#include "dtk_wordpiece_core.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -96,6 +97,11 @@ struct dtk_vocab {
   DevArray<uint32_t> d_off, d_bytes;  // (the words' bytes in whole 32-bit words: the kernel reads them as such)
   DtkVocabDev dev{};
 };
+// the words' longest, in bytes (DtkVocabDev::max_word)
+uint32_t vocab_max_word(const uint64_t *off, uint32_t n_words);
+// a split's arguments checked (DTK_E_ARG) and made into the rule of dtk_wordpiece_core.h
+int wordpiece_rule(uint32_t n_words, const uint8_t *prefix, uint32_t prefix_len, int32_t unk_id, uint32_t max_runes,
+                   DtkWpRule *rule);
 struct dtk_tally {
   int device = 0;
   uint32_t n_words = 0;
@@ -313,6 +319,25 @@ struct dtk_batch {
   Event ev_ids;                    // behind the lookup and the last enqueued copy of its block
   bool ids_built = false;          // the lookup has been enqueued for this run
   bool ids_waited = true;          // ev_ids has been waited for
+  // dtk_batch_set_wordpiece: every token of a run split into WordPiece ids (dtk_wordpiece.hip), on the download stream
+  // behind finish(), once per run.  One block of dtk_mirror.h: the two counters (pieces, unknown tokens), piece_off, then
+  // the pieces' ids and ends at a capacity the host states before the count is known (wp_cap_of); the counters always
+  // come home, and a run with more pieces than that is split again into a block that holds them (wp_finish).
+  const dtk_vocab *wp_vocab = nullptr;
+  DtkWpRule wp_rule{};
+  bool wp_home = false;
+  struct Pieces : MirrorBlock {
+    Piece<uint64_t> cnt;           // [n_pieces, n_unknown]
+    Piece<uint64_t> off;           // n_tok + 1
+    Piece<int32_t> id;             // wp_cap
+    Piece<uint32_t> bend;          // wp_cap
+  } pieces;
+  DevArray<uint64_t> d_wp_ws;      // the scan's tile sums (tiles + 1), then 8 bytes per token between the two passes
+  uint64_t wp_cap = 0;             // pieces the block holds
+  uint64_t wp_need = 0;            // the most pieces a run of this batch had beyond what its first block held (kept for the next runs)
+  Event ev_wp;                     // behind the split and the last enqueued copy of its block
+  bool wp_built = false;           // the split has been enqueued for this run
+  bool wp_waited = true;           // ev_wp has been waited for
   uint64_t max_doc_bytes = 0;     // of the current input (what decides whether the narrow form exists)
   bool max_doc_valid = false;
   Stream dl_stream;                 // created with the first download, unless the caller lends one (a pipeline's slices share one:
@@ -347,6 +372,7 @@ DtkWalkArgs walk_args(dtk_batch *b);
 int finish(dtk_batch *b);
 int launch_to_host(dtk_batch *b);
 int ids_wait(dtk_batch *b);  // what the last lookup enqueued has finished (the text and the block may be touched again)
+int wp_wait(dtk_batch *b);   // ... and the last WordPiece split
 // The next runs of a one-document batch walk a slice of a stream: open_slice (0: the window ends where the stream
 // does) and the record to start from (null: the stream's beginning).  batch_cut: the last run's cut block, behind finish().
 int batch_set_slice(dtk_batch *b, uint32_t open_slice, const DtkLaneState *carry);

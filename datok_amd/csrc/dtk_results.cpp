@@ -329,7 +329,118 @@ int ids_finish(dtk_batch *b, bool home, dtk_token_id_view *o) {
   o->tok_id = L.in(home ? L.h.p : static_cast<void *>(L.d.p), L.id);
   return DTK_OK;
 }
+
+// ---- dtk_batch_set_wordpiece: the tokens' pieces (dtk_wordpiece.hip; the definition is in include/datok_gpu.h)
+
+// Pieces the first block of a run holds: the count is known only behind the split, and nothing here waits for it.
+// Running text splits few of its tokens, so half as many pieces again as tokens; a run that needs more says so
+// (wp_need) and is split again into a block of that size -- which the batch's later runs start with, so a pipeline's
+// slices of one kind of text pay for the second split once per slot.
+uint64_t wp_cap_of(const dtk_batch *b) {
+  const uint64_t nt = b->totals.n_tokens;
+  return std::max(b->wp_need, nt + nt / 2 + 64);
+}
+
+// Enqueues on the download stream what is still missing of: the split (once per run and block), the copy of the two
+// counters, and (home) the copies of piece_off and of the pieces -- as many as there are tokens, the rest follows
+// when the count is known (wp_finish).
+int wp_enqueue(dtk_batch *b, bool home) {
+  if (!b->wp_vocab || (b->last_flags & DTK_NO_BYTE_OFFSETS)) return DTK_E_STATE;  // (the keys are cut out with tok_bstart / tok_bend)
+  if (!dtk_batch_download_stream(b)) return hip_fail(hipGetLastError(), "download stream");
+  dtk_batch::Pieces &L = b->pieces;
+  const uint64_t nt = b->totals.n_tokens;
+  int rc;
+  if (!b->wp_built) {
+    const uint64_t tiles = dtk_wp_tiles(nt);
+    b->wp_cap = wp_cap_of(b);
+    L.clear();
+    L.add(L.cnt, 2); L.add(L.off, nt + 1); L.add(L.id, b->wp_cap); L.add(L.bend, b->wp_cap);
+    if ((rc = L.fit()) != DTK_OK || (rc = b->d_wp_ws.fit(tiles + 1 + nt, tiles + 1 + nt + nt / 8)) != DTK_OK) return rc;
+    HIP_TRY(hipMemsetAsync(L.dev(L.cnt), 0, 2 * sizeof(uint64_t), b->dl_stream));
+    DtkWordPieceArgs a{};
+    a.text = b->d_text; a.total = b->total; a.doc_off = b->d_off; a.n_docs = b->n_docs;
+    a.tok_off = b->d_tok_off; a.tok_bstart = b->d_bstart; a.tok_bend = b->d_bend; a.n_tok = nt;
+    if (b->n_invalid) { const DtkSym s = sym_of(b); a.sym_base = s.base; a.sym_lut = s.lut; }
+    a.vocab = b->wp_vocab->dev;
+    a.rule = b->wp_rule;
+    a.tile_base = b->d_wp_ws.p;
+    a.first = reinterpret_cast<DtkWpFirst *>(b->d_wp_ws.p + tiles + 1);
+    a.cnt = reinterpret_cast<unsigned long long *>(L.dev(L.cnt));
+    a.piece_off = L.dev(L.off); a.piece_id = L.dev(L.id); a.piece_bend = L.dev(L.bend);
+    a.cap = b->wp_cap;
+    if (dtk_launch_wordpiece(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "wordpiece");
+    b->wp_built = true;
+    L.bring(L.cnt, 2);
+  }
+  // (The first copies bring nt ids and ends whatever the count turns out to be: with fewer pieces -- tokens of an empty
+  //  key -- or a run that overflowed the block and wrote none, device memory nobody wrote comes home behind them.  No
+  //  view shows it: n_pieces bounds every view, and an overflowed run is split and copied again.)
+  if (home) { L.bring(L.off, nt + 1); L.bring(L.id, nt); L.bring(L.bend, nt); }
+  if (L.pending.empty()) return DTK_OK;
+  if ((rc = L.issue(b->dl_stream)) != DTK_OK || (rc = b->ev_wp.ensure(hipEventDisableTiming)) != DTK_OK) return rc;
+  HIP_TRY(hipEventRecord(b->ev_wp, b->dl_stream));
+  b->wp_waited = false;
+  return DTK_OK;
+}
+
+// The pieces, complete: on the device, and (home, or pieces_home) in the page-locked block.  The view's pointers are
+// the caller's choice alone: device pointers for home == false, whatever has been brought home beside them.
+int wp_finish(dtk_batch *b, bool home, dtk_piece_view *o) {
+  int rc = finish(b);
+  if (rc != DTK_OK) return rc;
+  const bool copies = home || b->wp_home;
+  dtk_batch::Pieces &L = b->pieces;
+  for (int round = 0;; round++) {
+    if ((rc = wp_enqueue(b, copies)) != DTK_OK || (rc = wp_wait(b)) != DTK_OK) return rc;
+    const uint64_t np = L.host(L.cnt)[0];
+    if (np <= b->wp_cap) break;
+    if (round) return DTK_E_STATE;  // (the same run's count cannot have grown)
+    b->wp_need = np;                // no piece was written: once more, into a block that holds them
+    b->wp_built = false;
+  }
+  const uint64_t np = L.host(L.cnt)[0];
+  if (copies) {  // (what the first copies left out)
+    L.bring(L.id, np); L.bring(L.bend, np);
+    if ((rc = wp_enqueue(b, true)) != DTK_OK || (rc = wp_wait(b)) != DTK_OK) return rc;
+  }
+  void *base = home ? L.h.p : static_cast<void *>(L.d.p);
+  o->n_tok = b->totals.n_tokens;
+  o->n_pieces = np;
+  o->n_unknown = L.host(L.cnt)[1];
+  o->piece_off = L.in(base, L.off);
+  o->piece_id = L.in(base, L.id);
+  o->piece_bend = L.in(base, L.bend);
+  return DTK_OK;
+}
 }  // namespace
+
+int wp_wait(dtk_batch *b) {
+  if (b->wp_waited) return DTK_OK;
+  HIP_TRY(hipEventSynchronize(b->ev_wp));
+  b->wp_waited = true;
+  b->pieces.landed();
+  return DTK_OK;
+}
+
+extern "C" int dtk_batch_set_wordpiece(dtk_batch *b, const dtk_vocab *v, const uint8_t *prefix, uint32_t prefix_len,
+                                       int32_t unk_id, uint32_t max_runes, int pieces_home) {
+  if (!b || (v && v->device != b->device)) return DTK_E_ARG;
+  DtkWpRule rule{};
+  int rc = v ? wordpiece_rule(v->n_words, prefix, prefix_len, unk_id, max_runes, &rule) : DTK_OK;
+  if (rc != DTK_OK || (rc = wp_wait(b)) != DTK_OK) return rc;  // (a split under way reads the vocabulary that was attached)
+  // (the finished run, if any, is split anew under the new rule when its pieces are asked for)
+  b->wp_built = false;
+  b->wp_vocab = v; b->wp_rule = rule; b->wp_home = v && pieces_home != 0;
+  return DTK_OK;
+}
+
+extern "C" int dtk_batch_pieces_device(dtk_batch *b, dtk_piece_view *o) {
+  return !b || !o ? DTK_E_ARG : wp_finish(b, false, o);
+}
+
+extern "C" int dtk_batch_pieces_host(dtk_batch *b, dtk_piece_view *o) {
+  return !b || !o ? DTK_E_ARG : wp_finish(b, true, o);
+}
 
 int ids_wait(dtk_batch *b) {
   if (b->ids_waited) return DTK_OK;
@@ -443,6 +554,8 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
   if (rc != DTK_OK) return rc;
   // the tokens' ids (dtk_batch_set_vocab): no result field, they ride in front of the fields' copies
   if (b->vocab && !(b->last_flags & DTK_NO_BYTE_OFFSETS) && (rc = ids_enqueue(b, b->ids_home)) != DTK_OK) return rc;
+  // ... and their pieces (dtk_batch_set_wordpiece), the same way
+  if (b->wp_vocab && !(b->last_flags & DTK_NO_BYTE_OFFSETS) && (rc = wp_enqueue(b, b->wp_home)) != DTK_OK) return rc;
   uint32_t sel = b->fields & (DTK_R_ALL | DTK_R_TOK_RUNE16 | kBlkFields | DTK_R_EVENT_LIST | DTK_R_SENTENCES);
   if (sel & DTK_R_TOK_RUNE16) {
     // the narrow form holds every offset of a document of at most 32 767 bytes; a batch with a longer one gets the
@@ -516,6 +629,7 @@ extern "C" int dtk_batch_result_host(dtk_batch *b, dtk_result_view *o) {
   if (rc != DTK_OK) return rc;
   if (!b->dl_waited) { HIP_TRY(hipEventSynchronize(b->ev_dl)); b->dl_waited = true; }
   if ((rc = ids_wait(b)) != DTK_OK) return rc;  // (a lookup that download_begin enqueued: the batch has been waited for)
+  if ((rc = wp_wait(b)) != DTK_OK) return rc;   // (and a split)
   if (b->blk_pending) {
     // A blocked pair with a block that does not fit 16 bits: its 32-bit arrays come over now and the blocked pointers
     // stay NULL.  blk_failed holds for the rest of the run: a second call neither copies again nor flips forms.

@@ -39,6 +39,9 @@ struct dtk_stream {
   // dtk_stream_set_vocab: the slots' batches look their tokens up (dtk_batch_set_vocab); nothing crosses a cut
   bool vocab = false;
   bool ids_home = false;
+  // dtk_stream_set_wordpiece: ... and split them (dtk_batch_set_wordpiece), the same way
+  bool wordpiece = false;
+  bool pieces_home = false;
   // Position rendering and offset delivery follow the writer's state, which is chained on the device: slice k reads
   // carry slot k % (depth + 1) and writes the next one -- never the slot it read, and a slot is written again only by
   // slice k + depth, which takes the batch that slice k has left by then.
@@ -57,6 +60,8 @@ struct dtk_stream {
     SsView sens{};
     bool ids_set = false;                 // the tokens' ids: ids is this slice's
     dtk_token_id_view ids{};
+    bool pieces_set = false;              // the tokens' pieces: pieces is this slice's
+    dtk_piece_view pieces{};
   } cur;
   Stream s_up, s_run, s_down;
   std::vector<dtk_batch *> slots;
@@ -182,6 +187,25 @@ extern "C" int dtk_stream_token_ids(dtk_stream *s, dtk_token_id_view *o) {
   if (!s || !o) return DTK_E_ARG;
   if (!s->cur.ids_set) return DTK_E_STATE;
   *o = s->cur.ids;
+  return DTK_OK;
+}
+
+extern "C" int dtk_stream_set_wordpiece(dtk_stream *s, const dtk_vocab *v, const uint8_t *prefix, uint32_t prefix_len,
+                                        int32_t unk_id, uint32_t max_runes, int pieces_home) {
+  if (!s) return DTK_E_ARG;
+  for (dtk_batch *b : s->slots) {
+    const int rc = dtk_batch_set_wordpiece(b, v, prefix, prefix_len, unk_id, max_runes, pieces_home);
+    if (rc != DTK_OK) return rc;
+  }
+  s->wordpiece = v != nullptr;
+  s->pieces_home = v && pieces_home != 0;
+  return DTK_OK;
+}
+
+extern "C" int dtk_stream_pieces(dtk_stream *s, dtk_piece_view *o) {
+  if (!s || !o) return DTK_E_ARG;
+  if (!s->cur.pieces_set) return DTK_E_STATE;
+  *o = s->cur.pieces;
   return DTK_OK;
 }
 
@@ -409,6 +433,12 @@ struct Run {
       if (rc != DTK_OK) return rc;
       if (!s->ids_home) s->cur.ids.tok_id = nullptr;  // (host pointers only)
       s->cur.ids_set = true;
+    }
+    if (s->wordpiece) {
+      rc = s->pieces_home ? dtk_batch_pieces_host(b, &s->cur.pieces) : dtk_batch_pieces_device(b, &s->cur.pieces);
+      if (rc != DTK_OK) return rc;
+      if (!s->pieces_home) s->cur.pieces.piece_off = nullptr, s->cur.pieces.piece_id = nullptr, s->cur.pieces.piece_bend = nullptr;
+      s->cur.pieces_set = true;
     }
     rc = slice_fn ? slice_fn(slice_user, &sl) : DTK_OK;
     s->cur = {};

@@ -2,6 +2,7 @@
 // a frequency list (dtk_tally).  The table is built on the host with the functions of dtk_vocab_core.h -- the ones the
 // lookup kernel (dtk_tokenid.hip) probes it with -- and copied to the device; dtk_vocab_probe_mem builds the same image
 // and probes it on the host, on a machine without a GPU too.
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -43,7 +44,8 @@ int build_image(const uint8_t *bytes, const uint64_t *off, uint32_t n_words, Voc
     return DTK_E_NOMEM;
   }
   for (uint32_t w = 0; w <= n_words; w++) img.off[w] = (uint32_t)off[w];
-  img.view = DtkVocabDev{img.slots.data(), img.off.data(), bytes, (uint32_t)(n_slots - 1), n_words, g_dbg.vocab_hash_bits};
+  img.view = DtkVocabDev{img.slots.data(), img.off.data(), bytes, (uint32_t)(n_slots - 1), n_words, g_dbg.vocab_hash_bits,
+                         vocab_max_word(off, n_words)};
   // in ascending order, and a word that is there already is left out: of equal words the lowest index wins
   for (uint32_t w = 0; w < n_words; w++) {
     const uint8_t *key = bytes + off[w];
@@ -54,6 +56,40 @@ int build_image(const uint8_t *bytes, const uint64_t *off, uint32_t n_words, Voc
   return DTK_OK;
 }
 }  // namespace
+
+uint32_t vocab_max_word(const uint64_t *off, uint32_t n_words) {
+  uint64_t m = 0;
+  for (uint32_t w = 0; w < n_words; w++) m = std::max(m, off[w + 1] - off[w]);
+  return (uint32_t)m;  // (build_image has checked that every offset is below 2^32)
+}
+
+// The arguments of a split, as dtk_batch_set_wordpiece and dtk_wordpiece_probe_mem take them.
+int wordpiece_rule(uint32_t n_words, const uint8_t *prefix, uint32_t prefix_len, int32_t unk_id, uint32_t max_runes,
+                   DtkWpRule *rule) {
+  if (prefix_len > DTK_WP_MAX_PREFIX || (prefix_len && !prefix) || unk_id < 0 || (uint32_t)unk_id >= n_words) return DTK_E_ARG;
+  *rule = dtk_wp_rule(prefix, prefix_len, unk_id, max_runes);
+  return DTK_OK;
+}
+
+extern "C" int dtk_wordpiece_probe_mem(const uint8_t *bytes, const uint64_t *off, uint32_t n_words, const uint8_t *prefix,
+                                       uint32_t prefix_len, int32_t unk_id, uint32_t max_runes, const uint8_t *key,
+                                       size_t key_len, int32_t *ids, uint32_t *ends, uint32_t cap, uint32_t *n_out) {
+  if (!n_out || (key_len && !key) || key_len >= (1ull << 32) || (cap && (!ids || !ends))) return DTK_E_ARG;
+  VocabImage img;
+  DtkWpRule rule;
+  int rc = build_image(bytes, off, n_words, img);
+  if (rc != DTK_OK || (rc = wordpiece_rule(n_words, prefix, prefix_len, unk_id, max_runes, &rule)) != DTK_OK) return rc;
+  // pieces beyond cap are counted and not stored; an unknown token's single piece replaces whatever was stored
+  uint32_t n = dtk_wp_split(img.view, rule, DtkWpBytesKey{key, (uint32_t)key_len}, [&](uint32_t k, int32_t id, uint32_t end) {
+    if (k < cap) { ids[k] = id; ends[k] = end; }
+  });
+  if (n == DTK_WP_BAD) {
+    n = 1;
+    if (cap) { ids[0] = unk_id; ends[0] = (uint32_t)key_len; }
+  }
+  *n_out = n;
+  return n > cap ? DTK_E_CAPACITY : DTK_OK;
+}
 
 extern "C" int dtk_vocab_probe_mem(const uint8_t *bytes, const uint64_t *off, uint32_t n_words, const uint8_t *key,
                                    size_t key_len, int32_t *id) {
@@ -84,7 +120,7 @@ extern "C" int dtk_vocab_create(const uint8_t *bytes, const uint64_t *off, uint3
   HIP_TRY(hipMemset(v->d_bytes.p, 0, byte_words * 4));
   if (n_bytes) HIP_TRY(hipMemcpy(v->d_bytes.p, bytes, n_bytes, hipMemcpyHostToDevice));
   v->dev = DtkVocabDev{v->d_slots.p, v->d_off.p, reinterpret_cast<const uint8_t *>(v->d_bytes.p), img.view.mask, n_words,
-                       img.view.hash_bits};
+                       img.view.hash_bits, img.view.max_word};
   *out = v.release();
   return DTK_OK;
 }

@@ -22,6 +22,7 @@ struct DtkVocabDev {
   uint32_t mask;          // slots - 1
   uint32_t n_words;
   int32_t hash_bits;      // test hook VOCAB_HASH_BITS as it stood when the table was built: >= 0 keeps the hash's low bits
+  uint32_t max_word;      // the longest word's bytes: no longer key can match (the bound of dtk_wordpiece_core.h's candidates)
 };
 
 // The hash: two 32-bit lanes fed byte by byte (FNV-1a, and a Murmur3-style rotate-multiply), folded with the length

@@ -247,18 +247,21 @@ class SliceView:
     stream byte offsets), s_rstart / s_rend (int64, the writer's rune offsets), s_text_sen_end (rows of THIS slice closed
     in front of each TextEnd), s_carry_in / s_carry_out (the row open at the cut: (open, bstart, bend, rstart, rend)).
     With Stream.set_vocab the slice brings tok_id (np.int32, one per token of the slice; None with ids_home=False) and
-    n_unknown (dtk_stream_token_ids; both None when it is off)."""
+    n_unknown (dtk_stream_token_ids; both None when it is off).
+    With Stream.set_wordpiece the slice brings its tokens' pieces (dtk_stream_pieces; all None when it is off): piece_off
+    (np.uint64, tokens of THIS slice + 1, from 0), piece_id (np.int32), piece_bend (np.uint32, relative to the slice's
+    window like tok_bend) -- the three None with pieces_home=False -- and n_pieces, n_piece_unknown."""
     __slots__ = ("base", "first", "cut", "text", "last", "status", "tok_bstart", "tok_bend", "evl_pos", "evl_kind", "tail",
                  "out", "splice_pos", "splice_sent", "open_pos", "open_sent", "carry_in", "carry_out", "written",
                  "r_tok_rstart", "r_tok_rend", "r_blocked", "r_rblk", "r_rblk_head", "r_sent", "r_text_tok_end",
                  "r_text_sent_end", "r_carry_in", "r_carry_out",
                  "s_tok_end", "s_bstart", "s_bend", "s_rstart", "s_rend", "s_text_sen_end", "s_carry_in", "s_carry_out",
-                 "tok_id", "n_unknown")
+                 "tok_id", "n_unknown", "piece_off", "piece_id", "piece_bend", "n_pieces", "n_piece_unknown")
     _NONE = ("out", "splice_pos", "splice_sent", "open_pos", "open_sent", "carry_in", "carry_out", "written",
              "r_tok_rstart", "r_tok_rend", "r_blocked", "r_rblk", "r_rblk_head", "r_sent", "r_text_tok_end",
              "r_text_sent_end", "r_carry_in", "r_carry_out",
              "s_tok_end", "s_bstart", "s_bend", "s_rstart", "s_rend", "s_text_sen_end", "s_carry_in", "s_carry_out",
-             "tok_id", "n_unknown")
+             "tok_id", "n_unknown", "piece_off", "piece_id", "piece_bend", "n_pieces", "n_piece_unknown")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -588,6 +591,59 @@ def _set_vocab(fn, name, owner, v, tally, ids_home):
     owner._vocab = (v, tally)   # (they must outlive the owner's use of them)
 
 
+def _set_wordpiece(fn, name, owner, v, prefix, unk_id, max_runes, pieces_home):
+    prefix = bytes(prefix)
+    pb = np.frombuffer(prefix, dtype=np.uint8) if prefix else np.zeros(1, np.uint8)
+    check(fn(owner._h, v._h if v is not None else None, pb.ctypes.data, len(prefix), int(unk_id), int(max_runes),
+             1 if pieces_home else 0), name)
+    owner._wp_vocab = v   # (it must outlive the owner's use of it)
+
+
+class Pieces:
+    """A run's tokens split into WordPiece ids (dtk_piece_view): token i's pieces are piece_id[piece_off[i]:piece_off[i + 1]]
+    (np.int32; piece_off np.uint64, n_tok + 1), piece_bend (np.uint32) each piece's end as a byte offset in its document,
+    in source bytes; n_unknown counts the tokens that became the single unk_id piece."""
+    __slots__ = ("piece_off", "piece_id", "piece_bend", "n_pieces", "n_unknown")
+
+    def __init__(self, piece_off, piece_id, piece_bend, n_pieces, n_unknown):
+        self.piece_off, self.piece_id, self.piece_bend = piece_off, piece_id, piece_bend
+        self.n_pieces, self.n_unknown = n_pieces, n_unknown
+
+
+def _pieces_of(v, copy=True) -> Pieces:
+    """Host arrays of a dtk_piece_view whose pointers are host pointers."""
+    def arr(ptr, n, dt):
+        if n == 0 or not ptr:
+            return np.zeros(0, dt)
+        a = np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(ptr), dtype=dt)
+        return a.copy() if copy else a
+    n_tok, n_pieces = int(v.n_tok), int(v.n_pieces)
+    return Pieces(arr(v.piece_off, n_tok + 1, np.uint64), arr(v.piece_id, n_pieces, np.int32),
+                  arr(v.piece_bend, n_pieces, np.uint32), n_pieces, int(v.n_unknown))
+
+
+def wordpiece_probe(words, key: bytes, prefix=b"##", unk_id=0, max_runes=0, cap=None):
+    """dtk_wordpiece_probe_mem: `key` (its bytes after replacement) split over `words` on the host with the table and the
+    rule the kernels use: (ids, ends), ends in key bytes.  Needs no device.  cap: room for that many pieces (default:
+    enough); with more the call raises DatokGpuError E_CAPACITY whose .needed is the count."""
+    blob, off, n = _pack_words(words)
+    key, prefix = bytes(key), bytes(prefix)
+    kb = np.frombuffer(key, dtype=np.uint8) if key else np.zeros(1, np.uint8)
+    pb = np.frombuffer(prefix, dtype=np.uint8) if prefix else np.zeros(1, np.uint8)
+    room = len(key) + 1 if cap is None else int(cap)
+    ids, ends = np.zeros(max(room, 1), np.int32), np.zeros(max(room, 1), np.uint32)
+    n_out = C.c_uint32(0)
+    rc = lib().dtk_wordpiece_probe_mem(blob.ctypes.data, off.ctypes.data, n, pb.ctypes.data, len(prefix), int(unk_id),
+                                       int(max_runes), kb.ctypes.data, len(key), ids.ctypes.data, ends.ctypes.data, room,
+                                       C.byref(n_out))
+    if rc != _lib.OK:
+        e = _lib.DatokGpuError(rc, "dtk_wordpiece_probe_mem")
+        e.needed = int(n_out.value) if rc == _lib.E_CAPACITY else None
+        raise e
+    k = int(n_out.value)
+    return ids[:k].copy(), ends[:k].copy()
+
+
 class Batch:
     """dtk_batch: device buffers + one HIP stream for many documents per launch."""
 
@@ -763,6 +819,23 @@ class Batch:
         a = np.frombuffer((C.c_char * (n * 4)).from_address(v.tok_id), dtype=np.int32)
         return (a.copy() if copy else a), int(v.n_unknown)
 
+    def set_wordpiece(self, v, prefix=b"##", unk_id=0, max_runes=0, pieces_home=True):
+        """Every token of the next runs is split into WordPiece ids over the Vocab `v` (None: off) behind the run, on the
+        download stream: greedy longest-match-first, continuation pieces looked up behind `prefix` (0..16 bytes), a token
+        that cannot be split or has more than max_runes runes (0: 100) becomes the single piece unk_id.  pieces_home: the
+        pieces come home with the other result copies; False: they stay in HBM until pieces() asks.  A vocabulary
+        (set_vocab) may be attached beside it."""
+        _set_wordpiece(lib().dtk_batch_set_wordpiece, "dtk_batch_set_wordpiece", self, v, prefix, unk_id, max_runes, pieces_home)
+
+    def pieces(self, device=False, copy=True):
+        """The last run's pieces: a Pieces.  copy=False: views of the batch's page-locked block, valid until its next
+        run.  device=True: the raw dtk_piece_view (device pointers).  E_STATE before a run, without a split and after a
+        run with NO_BYTE_OFFSETS."""
+        v = _lib.PieceView()
+        fn = lib().dtk_batch_pieces_device if device else lib().dtk_batch_pieces_host
+        check(fn(self._h, C.byref(v)), "dtk_batch_pieces_device" if device else "dtk_batch_pieces_host")
+        return v if device else _pieces_of(v, copy)
+
     def set_result_fields(self, fields=R_ALL):
         """Which arrays result() brings to the host (the others come back empty)."""
         check(lib().dtk_batch_set_result_fields(self._h, int(fields)), "dtk_batch_set_result_fields")
@@ -862,6 +935,12 @@ class Pipeline:
         has run when the slice is handed over, so a Tally holds the whole corpus when run() returns."""
         _set_vocab(lib().dtk_pipeline_set_vocab, "dtk_pipeline_set_vocab", self, v, tally, ids_home)
 
+    def set_wordpiece(self, v, prefix=b"##", unk_id=0, max_runes=0, pieces_home=True):
+        """Batch.set_wordpiece for every slice: on_slice reads a slice's pieces with batch.pieces(); a slice is handed
+        over when its split has finished."""
+        _set_wordpiece(lib().dtk_pipeline_set_wordpiece, "dtk_pipeline_set_wordpiece", self, v, prefix, unk_id, max_runes,
+                       pieces_home)
+
     def set_result_fields(self, fields):
         """Bring these result arrays (Batch.R_*) of every slice to the host, overlapped with the next slices' work."""
         check(lib().dtk_pipeline_set_result_fields(self._h, int(fields)), "dtk_pipeline_set_result_fields")
@@ -930,6 +1009,14 @@ class Stream:
         the ids of the stream as one document) and n_unknown; `tally` gets every slice's tokens once.  ids_home=False:
         tok_id stays None (a tally alone: nothing per token leaves the device).  None turns it off."""
         _set_vocab(lib().dtk_stream_set_vocab, "dtk_stream_set_vocab", self, v, tally, ids_home)
+
+    def set_wordpiece(self, v, prefix=b"##", unk_id=0, max_runes=0, pieces_home=True):
+        """Every SliceView brings its tokens' pieces (piece_off from 0 in every slice, piece_id, piece_bend relative to the
+        slice's window, n_pieces, n_piece_unknown): a token never spans a cut, so the slices' pieces one behind the other
+        are the pieces of the stream as one document.  pieces_home=False: the arrays stay None, the counts come.  None
+        turns it off."""
+        _set_wordpiece(lib().dtk_stream_set_wordpiece, "dtk_stream_set_wordpiece", self, v, prefix, unk_id, max_runes,
+                       pieces_home)
 
     def set_sentences(self, on):
         """Every SliceView brings the sentences its calls close as rows (s_tok_end, s_bstart, s_bend, s_rstart, s_rend,
@@ -1079,6 +1166,16 @@ def _slice_token_ids(h) -> dict:
                 n_unknown=int(v.n_unknown))
 
 
+def _slice_pieces(h) -> dict:
+    """What dtk_stream_pieces says about the slice being delivered ({}: no split is attached)."""
+    v = _lib.PieceView()
+    if not h or lib().dtk_stream_pieces(h, C.byref(v)) != _lib.OK:
+        return {}
+    p = _pieces_of(v) if v.piece_off else None
+    return dict(piece_off=p and p.piece_off, piece_id=p and p.piece_id, piece_bend=p and p.piece_bend,
+                n_pieces=int(v.n_pieces), n_piece_unknown=int(v.n_unknown))
+
+
 def _slice_view(s, stream=None) -> SliceView:
     """Host copies of a dtk_stream_slice (its buffers are only valid inside the callback)."""
     v = s.view
@@ -1096,7 +1193,8 @@ def _slice_view(s, stream=None) -> SliceView:
                      tok_bstart=bs, tok_bend=be, evl_pos=arr(v.evl_pos, ne, np.uint32)[int(off[0]):],
                      evl_kind=arr(v.evl_kind, ne, np.uint8)[int(off[0]):], tail=int(arr(v.doc_tail, 1, np.uint32)[0]),
                      out=C.string_at(s.out, int(s.out_len)) if s.out else None, **_slice_positions(stream),
-                     **_slice_offsets(stream), **_slice_sentences(stream), **_slice_token_ids(stream))
+                     **_slice_offsets(stream), **_slice_sentences(stream), **_slice_token_ids(stream),
+                     **_slice_pieces(stream))
 
 
 def _slice_callback(on_slice, doc_off, err):

@@ -625,4 +625,31 @@ inline bool token_ids(dtk_batch *b, dtk_token_id_view *out, bool device = false)
   return rc == DTK_OK;
 }
 
+// ---- every token split into WordPiece ids over a Vocab on the device (dtk_batch_set_wordpiece, datok_gpu.h): greedy
+// longest-match-first, continuation pieces looked up behind `prefix`; a token that cannot be split, or has more than
+// max_runes runes, is the single piece unk_id.
+struct WordPiece {
+  std::string prefix = "##";   // 0..16 bytes
+  int32_t unk_id = 0;          // 0 <= unk_id < the vocabulary's size
+  uint32_t max_runes = 0;      // 0: 100, BERT's max_input_chars_per_word
+  bool pieces_home = true;     // the pieces come home with the batch's other result copies
+};
+
+// Attaches the split to a batch (v == nullptr: off); false + log line for options outside their ranges.
+inline bool set_wordpiece(dtk_batch *b, const Vocab *v, const WordPiece &o = WordPiece()) {
+  const int rc = dtk_batch_set_wordpiece(b, v ? v->get() : nullptr, reinterpret_cast<const uint8_t *>(o.prefix.data()),
+                                         (uint32_t)o.prefix.size(), o.unk_id, o.max_runes, o.pieces_home ? 1 : 0);
+  if (rc != DTK_OK) std::fprintf(stderr, "datok: wordpiece: %s\n", dtk_strerror(rc));
+  return rc == DTK_OK;
+}
+
+// The last run's pieces in page-locked host memory (device: device pointers), valid until the batch's next run: token
+// i's are piece_id[piece_off[i] .. piece_off[i + 1]).  false + log line on failure (before a run, without a split, or
+// after a run with DTK_NO_BYTE_OFFSETS).
+inline bool pieces(dtk_batch *b, dtk_piece_view *out, bool device = false) {
+  const int rc = device ? dtk_batch_pieces_device(b, out) : dtk_batch_pieces_host(b, out);
+  if (rc != DTK_OK) std::fprintf(stderr, "datok: pieces: %s\n", dtk_strerror(rc));
+  return rc == DTK_OK;
+}
+
 }  // namespace datok

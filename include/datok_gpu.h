@@ -487,6 +487,60 @@ typedef struct { uint64_t n_tok, n_unknown; const int32_t *tok_id; } dtk_token_i
 int dtk_batch_token_ids_device(dtk_batch *b, dtk_token_id_view *out);
 int dtk_batch_token_ids_host(dtk_batch *b, dtk_token_id_view *out);
 
+/* ---- every token split into WordPiece ids, on the device: what a BERT-style model takes.
+ *      A SPLIT has four inputs: a dtk_vocab; a continuation PREFIX of 0..16 bytes ("##" for BERT vocabularies; empty is
+ *      allowed); an unk_id with 0 <= unk_id < n_words; and max_runes, where 0 means 100, BERT's
+ *      max_input_chars_per_word.  Anything outside these ranges is DTK_E_ARG.
+ *        For token i the key K is exactly the key of dtk_batch_set_vocab above: the surface with every byte that does
+ *      not decode replaced by EF BF BD, so K is valid UTF-8.  Then:
+ *        - no key: a row with tok_bstart > tok_bend gives one piece, unk_id;
+ *        - empty key: K empty gives zero pieces (BERT returns [] here);
+ *        - too long: a key of more than max_runes runes gives one piece, unk_id;
+ *        - otherwise, with start = 0, until start == len(K): take the largest end > start on a rune boundary of K such
+ *          that a vocabulary word equals K[start:end) when start == 0, or prefix + K[start:end) otherwise (words are
+ *          compared as bytes; of equal words the lowest index wins, as in dtk_vocab).  If there is no such end the whole
+ *          token is the single piece unk_id (BERT's is_bad: no partial result, no backtracking).  Otherwise that word's
+ *          index is the next piece and start = end.
+ *      The text is taken as it is: no lower-casing, no accent stripping, no CJK splitting -- what BERT's BasicTokenizer
+ *      does in front of WordPiece is the caller's.  A word that ends or begins inside a rune can never match, because
+ *      cuts lie on rune boundaries only; neither can an empty word or the bare prefix.
+ *        The outputs, in the batch-wide token order that tok_off indexes: piece_off[n_tok + 1], CSR; piece_id[n_pieces];
+ *      piece_bend[n_pieces], the piece's end as a byte offset in its document, in SOURCE bytes (a replaced byte is one
+ *      source byte and three key bytes): a piece begins at tok_bstart[i] or at its predecessor's end, and an unk_id piece
+ *      for the whole token ends at tok_bend[i].  Rows of flagged documents are clamped to the document, as for the ids.
+ *      n_unknown counts the tokens that became the single unk_id piece (no key, too long, or no such end).  The result
+ *      is exact: the hash only picks where to look, the bytes decide.
+ *        dtk_wordpiece_probe_mem needs no device: it builds the table on the host and splits one key -- the bytes after
+ *      replacement, so `ends` are offsets in key bytes -- with the code the kernels use.  It stores up to `cap` pieces;
+ *      with more it returns DTK_E_CAPACITY and *n_out is the needed count. ---- */
+int dtk_wordpiece_probe_mem(const uint8_t *bytes, const uint64_t *off, uint32_t n_words,
+                            const uint8_t *prefix, uint32_t prefix_len, int32_t unk_id, uint32_t max_runes,
+                            const uint8_t *key, size_t key_len, int32_t *ids, uint32_t *ends, uint32_t cap, uint32_t *n_out);
+/* v == NULL: off (the default).  pieces_home != 0: the pieces are copied to page-locked memory with the other result
+ * copies (dtk_batch_download_begin); 0: they stay in HBM until dtk_batch_pieces_host asks.  The vocabulary must outlive
+ * the batch's use of it and live on the batch's device (else DTK_E_ARG).  A vocabulary (dtk_batch_set_vocab) and a split
+ * may be attached together, over the same dtk_vocab or different ones, and do not disturb each other.
+ *   With a split attached dtk_batch_download_begin enqueues it on the download stream, in front of the copies, once per
+ * run; dtk_batch_pieces_* begin it if nobody has and wait for it.  Which pointers a view holds is decided by the call
+ * alone: dtk_batch_pieces_device always returns device pointers, also when pieces_home has brought a copy home beside
+ * them, and dtk_batch_pieces_host always returns page-locked host pointers.  Both are valid until the batch's next run,
+ * its next dtk_batch_set_wordpiece or its free.
+ *   The output block is sized before the piece count is known, for half as many pieces again as tokens; a run with
+ * more is split a second time when its pieces are asked for, and the batch's later runs start with a block of that
+ * size.
+ *   DTK_E_STATE before a run, without a split, and after a run with DTK_NO_BYTE_OFFSETS.  No DTK_R_* bit belongs to the
+ * pieces, and dtk_result_view does not know them. */
+int dtk_batch_set_wordpiece(dtk_batch *b, const dtk_vocab *v, const uint8_t *prefix, uint32_t prefix_len,
+                            int32_t unk_id, uint32_t max_runes, int pieces_home);
+typedef struct {
+  uint64_t n_tok, n_pieces, n_unknown;
+  const uint64_t *piece_off;
+  const int32_t *piece_id;
+  const uint32_t *piece_bend;
+} dtk_piece_view;
+int dtk_batch_pieces_device(dtk_batch *b, dtk_piece_view *out);
+int dtk_batch_pieces_host(dtk_batch *b, dtk_piece_view *out);
+
 /* bit of position 0 of document d in the bitmaps of dtk_result_view.ev_bits */
 #define DTK_EVENT_BIT(doc_off_d, d) (((uint64_t)(doc_off_d)) + (uint64_t)(d))
 
@@ -538,6 +592,10 @@ int dtk_pipeline_set_result_fields(dtk_pipeline *p, uint32_t fields);
  * waited for when `fn` gets the slice, so a tally holds the whole corpus when dtk_pipeline_run returns.  (dtk_multi_* has
  * no counterpart: a vocabulary lives on one device.) */
 int dtk_pipeline_set_vocab(dtk_pipeline *p, const dtk_vocab *v, dtk_tally *t, int ids_home);
+/* dtk_batch_set_wordpiece for every slice: `fn` finds a slice's pieces through dtk_batch_pieces_host; a slice is handed
+ * over when its split has finished. */
+int dtk_pipeline_set_wordpiece(dtk_pipeline *p, const dtk_vocab *v, const uint8_t *prefix, uint32_t prefix_len,
+                               int32_t unk_id, uint32_t max_runes, int pieces_home);
 int dtk_pipeline_run(dtk_pipeline *p, const dtk_model *m, const uint8_t *text, const uint64_t *doc_off,
                      uint32_t n_docs, uint32_t flags, dtk_slice_fn fn, void *user);
 /* ---- one stream of any length: the reference tokenizes whatever its reader delivers (bufio.Reader, matrix.go:373;
@@ -725,6 +783,15 @@ int dtk_stream_sentences(dtk_stream *s, dtk_stream_sens *o);
  *      delivered.  dtk_stream_transduce leaves the vocabulary as set. ---- */
 int dtk_stream_set_vocab(dtk_stream *s, const dtk_vocab *v, dtk_tally *t, int ids_home);
 int dtk_stream_token_ids(dtk_stream *s, dtk_token_id_view *out);
+/* ---- a stream's tokens split into WordPiece ids (dtk_batch_set_wordpiece above), slice by slice.  A token never spans
+ *      a cut, so the slot's batch runs the batch's own split and nothing is carried: the slices' pieces one behind the
+ *      other are the pieces of the stream as one document, except that piece_off counts from 0 in every slice and
+ *      piece_bend is relative to the slice's window, as the slice's byte offsets are.  dtk_stream_pieces, inside
+ *      slice_fn: the slice being delivered (else DTK_E_STATE), page-locked host memory valid until slice_fn returns; with
+ *      pieces_home == 0 the three pointers are NULL and the counts are still there. ---- */
+int dtk_stream_set_wordpiece(dtk_stream *s, const dtk_vocab *v, const uint8_t *prefix, uint32_t prefix_len,
+                             int32_t unk_id, uint32_t max_runes, int pieces_home);
+int dtk_stream_pieces(dtk_stream *s, dtk_piece_view *out);
 /* flags: DTK_NEWLINE_AFTER_EOT is accepted and changes nothing here (it only moves the writer's rune offsets), except
  * that with position rendering on it must be the bit dtk_stream_set_position_render got.  Short
  * reads are retried until a buffer is full; read_fn is not called again after it has returned 0. */

@@ -25,6 +25,8 @@ HIP kernels behind the C-ABI of libdatok_gpu.so (include/datok_gpu.h):
                                            vocabulary on the device, type ids and a frequency list (addition)
     --                                   Batch.set_wordpiece / pieces, wordpiece_probe: every token split into WordPiece
                                            ids over a Vocab on the device, what a BERT-style model takes (addition)
+    --                                   Batch.set_encode / encoded, encode_rows: sentences or documents as fixed-length
+                                           model input rows (input_ids, row_len, word_id) on the device (addition)
     --                                   Pipeline: a corpus larger than a batch, uploads overlapped (addition)
     --                                   MultiPipeline: ... sharded over several GPUs of a node (addition)
     tok.TransduceTokenWriter(r, tw)      Tokenizer.transduce_token_writer(r, tw, slice_bytes=N): a reader of any length,
@@ -35,4 +37,5 @@ from ._lib import (DatokGpuError, ST_BAD_MODEL, ST_BAD_OFFSET, ST_EMPTY_TEXT, ST
 from .host import (NEWLINE_AFTER_EOT, NO_BYTE_OFFSETS, NO_RUNE_OFFSETS, OFFSETS_ONLY, SENTENCE_POS, SENTENCES, SIMPLE, TOKEN_POS, TOKENS, Batch,  # noqa: F401
                    BatchResult, MultiPipeline, PinnedBuffer, Pipeline, TokenWriter, Tokenizer, foma_to_datok, foma_to_matok, load_foma_file,
                    load_tokenizer_file, model_info, new_token_writer, replay, replay_list, unpack_blocked,
-                   SentenceTable, SliceView, Stream, replay_slice, slice_calls, Tally, Vocab, Pieces, wordpiece_probe)
+                   SentenceTable, SliceView, Stream, replay_slice, slice_calls, Tally, Vocab, Pieces, wordpiece_probe,
+                   Encoded, encode_rows)

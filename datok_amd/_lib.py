@@ -45,6 +45,8 @@ EXPORTS = [
     "dtk_pipeline_set_vocab", "dtk_stream_set_vocab", "dtk_stream_token_ids",
     "dtk_wordpiece_probe_mem", "dtk_batch_set_wordpiece", "dtk_batch_pieces_device", "dtk_batch_pieces_host",
     "dtk_pipeline_set_wordpiece", "dtk_stream_set_wordpiece", "dtk_stream_pieces",
+    "dtk_encode_rows_mem", "dtk_batch_set_encode", "dtk_batch_encoded_device", "dtk_batch_encoded_host",
+    "dtk_pipeline_set_encode",
 ]
 ID_UNKNOWN = -1   # DTK_ID_UNKNOWN
 
@@ -95,6 +97,23 @@ class PieceView(C.Structure):
     """dtk_piece_view: a run's tokens split into WordPiece ids (dtk_batch_pieces_host / _device)."""
     _fields_ = [("n_tok", C.c_uint64), ("n_pieces", C.c_uint64), ("n_unknown", C.c_uint64), ("piece_off", C.c_void_p),
                 ("piece_id", C.c_void_p), ("piece_bend", C.c_void_p)]
+
+
+ENC_SENTENCE, ENC_DOCUMENT = 0, 1          # dtk_encode_spec.unit
+ENC_FIRST_WINDOW, ENC_WORD_IDS = 1, 2      # dtk_encode_spec.flags
+
+
+class EncodeSpec(C.Structure):
+    """dtk_encode_spec: how sentences or documents become fixed-length model input rows (dtk_batch_set_encode)."""
+    _fields_ = [("max_len", C.c_uint32), ("cls_id", C.c_int32), ("sep_id", C.c_int32), ("pad_id", C.c_int32),
+                ("unit", C.c_uint32), ("stride", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class EncodeView(C.Structure):
+    """dtk_encode_view: a run's model input rows (dtk_batch_encoded_host / _device)."""
+    _fields_ = [("n_units", C.c_uint64), ("n_rows", C.c_uint64), ("n_cut", C.c_uint64), ("max_len", C.c_uint32),
+                ("unit_row_off", C.c_void_p), ("input_ids", C.c_void_p), ("row_len", C.c_void_p),
+                ("row_piece0", C.c_void_p), ("word_id", C.c_void_p)]
 
 
 SLICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)
@@ -292,6 +311,13 @@ def lib():
     L.dtk_batch_pieces_device.argtypes = [vp, C.POINTER(PieceView)]
     L.dtk_batch_pieces_host.argtypes = [vp, C.POINTER(PieceView)]
     L.dtk_stream_pieces.argtypes = [vp, C.POINTER(PieceView)]
+    u64 = C.c_uint64
+    L.dtk_encode_rows_mem.argtypes = [C.POINTER(EncodeSpec), vp, u64, vp, vp, u64, vp, u32, u64, vp, vp, vp, vp, vp,
+                                      C.POINTER(u64), C.POINTER(u64)]
+    L.dtk_batch_set_encode.argtypes = [vp, C.POINTER(EncodeSpec), C.c_int]
+    L.dtk_pipeline_set_encode.argtypes = [vp, C.POINTER(EncodeSpec), C.c_int]
+    L.dtk_batch_encoded_device.argtypes = [vp, C.POINTER(EncodeView)]
+    L.dtk_batch_encoded_host.argtypes = [vp, C.POINTER(EncodeView)]
     L.dtk_stream_run.argtypes = [vp, vp, READ_FN, vp, u32, STREAM_SLICE_FN, vp, C.POINTER(u32)]
     L.dtk_stream_transduce.argtypes = [vp, vp, READ_FN, vp, u32, C.POINTER(vp), C.POINTER(sz), C.POINTER(u32)]
     for f in (L.dtk_blk_start, L.dtk_blk_end):

@@ -75,6 +75,7 @@ dtk_batch::~dtk_batch() {
   if (dl_begun && !dl_waited) (void)hipEventSynchronize(ev_dl);
   (void)ids_wait(this);
   (void)wp_wait(this);
+  (void)enc_wait(this);
 }
 
 extern "C" void dtk_batch_free(dtk_batch *b) { delete b; }
@@ -116,6 +117,7 @@ extern "C" int dtk_batch_set_input(dtk_batch *b, const uint8_t *text, const uint
   { int rc = wait_own(b); if (rc != DTK_OK) return rc; }  // the previous run may still read the buffers
   { int rc = ids_wait(b); if (rc != DTK_OK) return rc; }  // (and its lookup on the download stream, the text)
   { int rc = wp_wait(b); if (rc != DTK_OK) return rc; }
+  { int rc = enc_wait(b); if (rc != DTK_OK) return rc; }
   hipStream_t us = b->up_stream ? b->up_stream : b->stream;
   if (total) HIP_TRY(hipMemcpyAsync(b->d_text_own, text, total, hipMemcpyHostToDevice, us));
   memcpy(b->h_off_pin.p, doc_off, ((size_t)n_docs + 1) * 8);
@@ -148,6 +150,7 @@ extern "C" int dtk_batch_set_input_device(dtk_batch *b, const void *d_text, cons
   HIP_TRY(hipMemcpy(off.data(), d_doc_off, ((size_t)n_docs + 1) * 8, hipMemcpyDeviceToHost));
   { const int rc = ids_wait(b); if (rc != DTK_OK) return rc; }  // (a lookup still reads the input it belongs to)
   { const int rc = wp_wait(b); if (rc != DTK_OK) return rc; }
+  { const int rc = enc_wait(b); if (rc != DTK_OK) return rc; }
   if (off[0] != 0 || off[n_docs] != total_bytes) return DTK_E_ARG;
   for (uint32_t d = 0; d < n_docs; d++)
     if (off[d + 1] < off[d] || off[d + 1] - off[d] >= 0x7FFFFFF0ull) return DTK_E_ARG;
@@ -454,6 +457,8 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
   b->ids_built = false;
   { const int rc_ = wp_wait(b); if (rc_ != DTK_OK) return rc_; }
   b->wp_built = false;
+  { const int rc_ = enc_wait(b); if (rc_ != DTK_OK) return rc_; }
+  b->enc_built = false; b->enc_need = 0;
   if (b->up_pending) {  // the kernels wait for the input's upload on the other stream
     HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_up, 0));
     b->up_pending = false;

@@ -13,6 +13,7 @@
 #include "dtk_mirror.h"
 #include "dtk_vocab_core.h"
 #include "dtk_wordpiece_core.h"
+#include "dtk_encode_core.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -305,6 +306,7 @@ struct dtk_batch {
   bool sen_done = false;           // the count has been looked at and fits (and exact documents are spliced in)
   uint64_t sen_n = 0;              // rows of the finished table
   uint64_t sen_need = 0;           // nonzero: this run's table has that many rows, more than the bound
+  uint32_t sen_gen = 0;            // counts the table's launches and splices (dtk_batch_set_encode reads the table)
   // dtk_batch_set_vocab: every token of a run looked up in a vocabulary (dtk_tokenid.hip), on the download stream behind
   // finish().  One block of dtk_mirror.h: the unknown counter, then one id per token; the counter always comes home,
   // the ids with ids_home or when dtk_batch_token_ids_host asks.  The kernel runs once per run, so a tally gets a run's
@@ -338,6 +340,30 @@ struct dtk_batch {
   Event ev_wp;                     // behind the split and the last enqueued copy of its block
   bool wp_built = false;           // the split has been enqueued for this run
   bool wp_waited = true;           // ev_wp has been waited for
+  uint32_t wp_gen = 0;             // counts the split's launches: what was computed from the pieces knows which it read
+  // dtk_batch_set_encode: the run's sentences or documents as model input rows (dtk_encode.hip), on the download stream
+  // behind the split and, for the sentence unit, behind the sentence table.  One block of dtk_mirror.h, sized by a bound
+  // the host states before any count is known (enc_enqueue); the counter block travels beside it and always comes home.
+  // A run whose pieces or sentence table were made anew since (wp_gen, sen_gen), or whose rows outgrew the block, wrote
+  // no row and is encoded again (enc_finish).
+  bool enc_on = false;
+  DtkEncRule enc_rule{};
+  bool enc_home = false;
+  struct Enc : MirrorBlock {
+    Piece<int32_t> ids, word;      // rows_cap * max_len each (word: 0 without DTK_ENC_WORD_IDS); 16-byte aligned
+    Piece<uint64_t> piece0;        // rows_cap
+    Piece<uint64_t> off;           // units_cap + 1
+    Piece<uint32_t> len;           // rows_cap
+  } enc;
+  DevArray<uint64_t> d_enc_cnt;    // [n_rows, n_cut, n_units, ok]
+  PinBuf h_enc_cnt;
+  DevArray<uint64_t> d_enc_ws;     // the scan's tile sums (tiles + 1), then a DtkEncUnit per unit
+  uint64_t enc_rows_cap = 0;       // rows the block holds
+  uint64_t enc_need = 0;           // nonzero: this run has that many rows, more than the bound
+  uint32_t enc_wp_gen = 0, enc_sen_gen = 0;  // what the enqueued encode read
+  Event ev_enc;                    // behind the encode and the last enqueued copy of its block
+  bool enc_built = false;          // the encode has been enqueued for this run
+  bool enc_waited = true;          // ev_enc has been waited for
   uint64_t max_doc_bytes = 0;     // of the current input (what decides whether the narrow form exists)
   bool max_doc_valid = false;
   Stream dl_stream;                 // created with the first download, unless the caller lends one (a pipeline's slices share one:
@@ -373,6 +399,8 @@ int finish(dtk_batch *b);
 int launch_to_host(dtk_batch *b);
 int ids_wait(dtk_batch *b);  // what the last lookup enqueued has finished (the text and the block may be touched again)
 int wp_wait(dtk_batch *b);   // ... and the last WordPiece split
+int enc_wait(dtk_batch *b);  // ... and the last encode
+bool enc_rule_of(const dtk_encode_spec *s, DtkEncRule *r);  // dtk_encode.cpp: a spec checked and made into the rule (false: DTK_E_ARG)
 // The next runs of a one-document batch walk a slice of a stream: open_slice (0: the window ends where the stream
 // does) and the record to start from (null: the stream's beginning).  batch_cut: the last run's cut block, behind finish().
 int batch_set_slice(dtk_batch *b, uint32_t open_slice, const DtkLaneState *carry);

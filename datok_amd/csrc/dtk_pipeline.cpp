@@ -25,6 +25,7 @@ struct dtk_pipeline {
   uint32_t fields = 0;                 // DTK_R_*: result arrays brought to the host for every slice (0: none)
   bool vocab = false;                  // dtk_pipeline_set_vocab: every slice's tokens are looked up before it is handed over
   bool wordpiece = false;              // dtk_pipeline_set_wordpiece: ... and split into pieces
+  bool encode = false;                 // dtk_pipeline_set_encode: ... and packed into model input rows
   uint32_t run_flags = 0;              // of the run in progress
   // Three streams for the whole pipeline, whatever its depth: uploads, kernels, downloads (the HIP runtime maps streams
   // onto four hardware queues; streams that share a queue serialise -- a stream per slot made depth 4 slower than 3).
@@ -113,6 +114,16 @@ extern "C" int dtk_pipeline_set_wordpiece(dtk_pipeline *p, const dtk_vocab *v, c
   return DTK_OK;
 }
 
+extern "C" int dtk_pipeline_set_encode(dtk_pipeline *p, const dtk_encode_spec *spec, int rows_home) {
+  if (!p) return DTK_E_ARG;
+  for (dtk_batch *b : p->slots) {
+    const int rc = dtk_batch_set_encode(b, spec, rows_home);
+    if (rc != DTK_OK) return rc;
+  }
+  p->encode = spec != nullptr;
+  return DTK_OK;
+}
+
 // Slices whose kernels have finished start their way home now (nothing here blocks; the copies queue up on the download
 // stream in slice order): the download of slice i runs under the walk of slice i + 1 and the upload of slice i + 2.
 static void begin_downloads(dtk_pipeline *p, uint32_t oldest) {
@@ -142,6 +153,10 @@ static int deliver(dtk_pipeline *p, uint32_t slot, dtk_slice_fn fn, void *user) 
   if (rc == DTK_OK && p->wordpiece && !(p->run_flags & DTK_NO_BYTE_OFFSETS)) {  // (and its split)
     dtk_piece_view pieces;
     rc = dtk_batch_pieces_device(p->slots[slot], &pieces);
+  }
+  if (rc == DTK_OK && p->encode && p->wordpiece && !(p->run_flags & DTK_NO_BYTE_OFFSETS)) {  // (and its rows)
+    dtk_encode_view rows;
+    rc = dtk_batch_encoded_device(p->slots[slot], &rows);
   }
   const uint32_t first = p->first[slot], n = p->count[slot];
   p->count[slot] = 0;

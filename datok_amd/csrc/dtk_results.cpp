@@ -178,6 +178,7 @@ int sen_enqueue(dtk_batch *b, bool home) {
     a.sen_rstart = L.dev(L.rstart); a.sen_rend = L.dev(L.rend); a.text_sen_end = L.dev(L.tse);
     if (dtk_launch_sentences(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "sentence table");
     b->sen_built = true;
+    b->sen_gen++;
     b->sen_home = b->sen_done = false;
   } else if (b->sen_home) {
     return DTK_OK;  // on its way
@@ -259,6 +260,7 @@ int sen_splice_exact(dtk_batch *b) {
   *L.host(L.cnt) = (uint32_t)n;
   HIP_TRY(hipMemcpy(L.d.p, L.h.p, (size_t)L.bytes, hipMemcpyHostToDevice));
   b->sen_n = n;
+  b->sen_gen++;
   return DTK_OK;
 }
 
@@ -370,6 +372,7 @@ int wp_enqueue(dtk_batch *b, bool home) {
     a.cap = b->wp_cap;
     if (dtk_launch_wordpiece(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "wordpiece");
     b->wp_built = true;
+    b->wp_gen++;
     L.bring(L.cnt, 2);
   }
   // (The first copies bring nt ids and ends whatever the count turns out to be: with fewer pieces -- tokens of an empty
@@ -412,7 +415,153 @@ int wp_finish(dtk_batch *b, bool home, dtk_piece_view *o) {
   o->piece_bend = L.in(base, L.bend);
   return DTK_OK;
 }
+
+// ---- dtk_batch_set_encode: the model input rows (dtk_encode.hip; the definition is in include/datok_gpu.h)
+
+bool enc_state(const dtk_batch *b) { return b->enc_on && b->wp_vocab && !(b->last_flags & DTK_NO_BYTE_OFFSETS); }
+
+// Enqueues on the download stream what is still missing of: the split and (sentence unit) the sentence table, the encode
+// (once per run, per block and per state of the tables it reads), the copy of its counters, and (home) the copies of
+// unit_row_off and of as many rows as there are units -- the rest follows when the count is known (enc_finish).
+// Nothing here waits.  The block is sized by n_rows <= n_units + n_pieces / step, with the bounds the host has: the
+// split's capacity for the pieces, the documents or the sentence table's capacity for the units.
+int enc_enqueue(dtk_batch *b, bool home) {
+  if (!enc_state(b)) return DTK_E_STATE;
+  if (!dtk_batch_download_stream(b)) return hip_fail(hipGetLastError(), "download stream");
+  const DtkEncRule &R = b->enc_rule;
+  const bool sentences = R.unit == DTK_ENC_SENTENCE, words = (R.flags & DTK_ENC_WORD_IDS) != 0;
+  int rc;
+  if ((rc = wp_enqueue(b, b->wp_home)) != DTK_OK) return rc;
+  if (sentences) {
+    // documents the exact pass walked get their rows on the host (sen_splice_exact): the encode waits until somebody
+    // asks for it
+    if (!b->h_exact_ids.empty() && !b->sen_done) return DTK_OK;
+    if (!b->sen_built && (rc = sen_enqueue(b, false)) != DTK_OK) return rc;
+  }
+  dtk_batch::Enc &L = b->enc;
+  bool issued = false;
+  if (b->enc_built && (b->enc_wp_gen != b->wp_gen || (sentences && b->enc_sen_gen != b->sen_gen))) b->enc_built = false;
+  if (!b->enc_built) {
+    const uint64_t units_cap = sentences ? b->sen.cap(b->sen.tok_end) : b->n_docs;
+    uint64_t rows = units_cap + ((R.flags & DTK_ENC_FIRST_WINDOW) ? 0u : b->wp_cap / R.step);
+    rows = (std::max<uint64_t>(std::max(rows, b->enc_need), 1) + 3u) & ~3ull;  // (whole 16 bytes of ids: word_id stays aligned)
+    const uint64_t cells = rows * R.max_len, tiles = dtk_enc_tiles(units_cap);
+    const uint64_t ws = tiles + 1 + units_cap * (sizeof(DtkEncUnit) / 8);
+    static_assert(sizeof(DtkEncUnit) % 8 == 0, "the workspace is laid out in 64-bit words");
+    L.clear();
+    L.add(L.ids, cells); L.add(L.word, words ? cells : 0); L.add(L.piece0, rows); L.add(L.off, units_cap + 1); L.add(L.len, rows);
+    if ((rc = L.fit(false)) != DTK_OK || (rc = b->d_enc_ws.fit(ws, ws + ws / 8)) != DTK_OK ||
+        (rc = b->d_enc_cnt.fit(4, 4)) != DTK_OK || (rc = b->h_enc_cnt.fit(4 * sizeof(uint64_t))) != DTK_OK)
+      return rc;
+    HIP_TRY(hipMemsetAsync(b->d_enc_cnt.p, 0, 4 * sizeof(uint64_t), b->dl_stream));
+    DtkEncodeArgs a{};
+    a.rule = R;
+    a.tok_off = b->d_tok_off; a.n_docs = b->n_docs; a.n_tok = b->totals.n_tokens;
+    if (sentences) {
+      a.sen_off = b->sen.dev(b->sen.off); a.sen_tok_end = b->sen.dev(b->sen.tok_end); a.sen_count = b->sen.dev(b->sen.cnt);
+      a.sen_cap = units_cap;
+    }
+    a.piece_off = b->pieces.dev(b->pieces.off); a.piece_id = b->pieces.dev(b->pieces.id); a.piece_cap = b->wp_cap;
+    a.units_cap = units_cap; a.rows_cap = rows;
+    a.tile_base = b->d_enc_ws.p;
+    a.unit = reinterpret_cast<DtkEncUnit *>(b->d_enc_ws.p + tiles + 1);
+    a.cnt = reinterpret_cast<unsigned long long *>(b->d_enc_cnt.p);
+    a.unit_row_off = L.dev(L.off); a.input_ids = L.dev(L.ids); a.row_len = L.dev(L.len); a.row_piece0 = L.dev(L.piece0);
+    a.word_id = words ? L.dev(L.word) : nullptr;
+    if (dtk_launch_encode(&a, b->dl_stream)) return hip_fail(hipGetLastError(), "encode");
+    b->enc_built = true;
+    b->enc_rows_cap = rows;
+    b->enc_wp_gen = b->wp_gen; b->enc_sen_gen = b->sen_gen;
+    HIP_TRY(hipMemcpyAsync(b->h_enc_cnt.p, b->d_enc_cnt.p, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, b->dl_stream));
+    issued = true;
+  }
+  if (home) {
+    // (as with the pieces: rows nobody wrote may come home behind the written ones, and no view shows them)
+    if ((rc = L.h.fit((size_t)L.bytes)) != DTK_OK) return rc;
+    const uint64_t first = std::min(L.cap(L.off) - 1, b->enc_rows_cap);
+    L.bring(L.ids, first * R.max_len); L.bring(L.word, first * R.max_len); L.bring(L.piece0, first);
+    L.bring(L.off, L.cap(L.off)); L.bring(L.len, first);
+  }
+  if (!L.pending.empty()) {
+    if ((rc = L.issue(b->dl_stream)) != DTK_OK) return rc;
+    issued = true;
+  }
+  if (!issued) return DTK_OK;
+  if ((rc = b->ev_enc.ensure(hipEventDisableTiming)) != DTK_OK) return rc;
+  HIP_TRY(hipEventRecord(b->ev_enc, b->dl_stream));
+  b->enc_waited = false;
+  return DTK_OK;
+}
+
+// The rows, complete: on the device, and (home, or rows_home) in the page-locked block.  The pieces and the sentence
+// table are completed first; an encode that read an earlier state of either, or outgrew its block, is done again.
+int enc_finish(dtk_batch *b, bool home, dtk_encode_view *o) {
+  int rc = finish(b);
+  if (rc != DTK_OK) return rc;
+  if (!enc_state(b)) return DTK_E_STATE;
+  if ((rc = enc_wait(b)) != DTK_OK) return rc;  // (nothing reads the tables while they are made anew)
+  dtk_piece_view pieces;
+  if ((rc = wp_finish(b, false, &pieces)) != DTK_OK) return rc;
+  const DtkEncRule &R = b->enc_rule;
+  if (R.unit == DTK_ENC_SENTENCE && (rc = sen_finish(b, false)) != DTK_OK) return rc;
+  const bool copies = home || b->enc_home;
+  dtk_batch::Enc &L = b->enc;
+  const uint64_t *cnt = nullptr;
+  for (int round = 0;; round++) {
+    if ((rc = enc_enqueue(b, copies)) != DTK_OK || (rc = enc_wait(b)) != DTK_OK) return rc;
+    cnt = b->h_enc_cnt.as<uint64_t>();
+    if (cnt[3]) break;
+    if (round) return DTK_E_STATE;  // (the same run's count cannot have grown)
+    b->enc_need = cnt[0];           // no row was written: once more, into a block that holds them
+    b->enc_built = false;
+  }
+  const uint64_t n_rows = cnt[0], n_units = cnt[2];
+  if (copies) {  // (what the first copies left out)
+    L.bring(L.ids, n_rows * R.max_len); L.bring(L.word, n_rows * R.max_len); L.bring(L.piece0, n_rows);
+    L.bring(L.off, n_units + 1); L.bring(L.len, n_rows);
+    if ((rc = enc_enqueue(b, true)) != DTK_OK || (rc = enc_wait(b)) != DTK_OK) return rc;
+  }
+  void *base = home ? L.h.p : static_cast<void *>(L.d.p);
+  o->n_units = n_units; o->n_rows = n_rows; o->n_cut = cnt[1];
+  o->max_len = R.max_len;
+  o->unit_row_off = L.in(base, L.off);
+  o->input_ids = L.in(base, L.ids);
+  o->row_len = L.in(base, L.len);
+  o->row_piece0 = L.in(base, L.piece0);
+  o->word_id = (R.flags & DTK_ENC_WORD_IDS) ? L.in(base, L.word) : nullptr;
+  return DTK_OK;
+}
 }  // namespace
+
+int enc_wait(dtk_batch *b) {
+  if (b->enc_waited) return DTK_OK;
+  HIP_TRY(hipEventSynchronize(b->ev_enc));
+  b->enc_waited = true;
+  b->enc.landed();
+  return DTK_OK;
+}
+
+extern "C" int dtk_batch_set_encode(dtk_batch *b, const dtk_encode_spec *spec, int rows_home) {
+  if (!b) return DTK_E_ARG;
+  DtkEncRule rule{};
+  if (spec && !enc_rule_of(spec, &rule)) return DTK_E_ARG;
+  const int rc = enc_wait(b);
+  if (rc != DTK_OK) return rc;
+  // (the finished run, if any, is encoded anew under the new spec when its rows are asked for)
+  b->enc_built = false; b->enc_need = 0;
+  b->enc_on = spec != nullptr;
+  b->enc_rule = rule;
+  b->enc_home = spec && rows_home != 0;
+  return DTK_OK;
+}
+
+extern "C" int dtk_batch_encoded_device(dtk_batch *b, dtk_encode_view *o) {
+  return !b || !o ? DTK_E_ARG : enc_finish(b, false, o);
+}
+
+extern "C" int dtk_batch_encoded_host(dtk_batch *b, dtk_encode_view *o) {
+  return !b || !o ? DTK_E_ARG : enc_finish(b, true, o);
+}
 
 int wp_wait(dtk_batch *b) {
   if (b->wp_waited) return DTK_OK;
@@ -556,6 +705,8 @@ extern "C" int dtk_batch_download_begin(dtk_batch *b) {
   if (b->vocab && !(b->last_flags & DTK_NO_BYTE_OFFSETS) && (rc = ids_enqueue(b, b->ids_home)) != DTK_OK) return rc;
   // ... and their pieces (dtk_batch_set_wordpiece), the same way
   if (b->wp_vocab && !(b->last_flags & DTK_NO_BYTE_OFFSETS) && (rc = wp_enqueue(b, b->wp_home)) != DTK_OK) return rc;
+  // ... and the model input rows made of them (dtk_batch_set_encode)
+  if (enc_state(b) && (rc = enc_enqueue(b, b->enc_home)) != DTK_OK) return rc;
   uint32_t sel = b->fields & (DTK_R_ALL | DTK_R_TOK_RUNE16 | kBlkFields | DTK_R_EVENT_LIST | DTK_R_SENTENCES);
   if (sel & DTK_R_TOK_RUNE16) {
     // the narrow form holds every offset of a document of at most 32 767 bytes; a batch with a longer one gets the
@@ -630,6 +781,7 @@ extern "C" int dtk_batch_result_host(dtk_batch *b, dtk_result_view *o) {
   if (!b->dl_waited) { HIP_TRY(hipEventSynchronize(b->ev_dl)); b->dl_waited = true; }
   if ((rc = ids_wait(b)) != DTK_OK) return rc;  // (a lookup that download_begin enqueued: the batch has been waited for)
   if ((rc = wp_wait(b)) != DTK_OK) return rc;   // (and a split)
+  if ((rc = enc_wait(b)) != DTK_OK) return rc;  // (and an encode)
   if (b->blk_pending) {
     // A blocked pair with a block that does not fit 16 bits: its 32-bit arrays come over now and the blocked pointers
     // stay NULL.  blk_failed holds for the rest of the run: a second call neither copies again nor flips forms.

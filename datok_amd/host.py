@@ -644,6 +644,86 @@ def wordpiece_probe(words, key: bytes, prefix=b"##", unk_id=0, max_runes=0, cap=
     return ids[:k].copy(), ends[:k].copy()
 
 
+def _encode_spec(max_len, cls_id, sep_id, pad_id, unit, stride, first_window, word_ids):
+    units = {"sentence": _lib.ENC_SENTENCE, "document": _lib.ENC_DOCUMENT}
+    flags = (_lib.ENC_FIRST_WINDOW if first_window else 0) | (_lib.ENC_WORD_IDS if word_ids else 0)
+    return _lib.EncodeSpec(int(max_len), int(cls_id), int(sep_id), int(pad_id),
+                           units[unit] if isinstance(unit, str) else int(unit), int(stride), flags)
+
+
+def _set_encode(fn, name, owner, max_len, kw):
+    spec = None if max_len is None else _encode_spec(max_len, kw["cls_id"], kw["sep_id"], kw["pad_id"], kw["unit"],
+                                                     kw["stride"], kw["first_window"], kw["word_ids"])
+    check(fn(owner._h, C.byref(spec) if spec is not None else None, 1 if kw["rows_home"] else 0), name)
+
+
+class Encoded:
+    """A run's sentences or documents as fixed-length model input rows (dtk_encode_view): row unit_row_off[u] + k is
+    window k of unit u; input_ids (np.int32, (n_rows, max_len)): cls_id, the window's piece ids, sep_id, pad_id; row_len
+    (np.uint32) the positions in front of the padding; row_piece0 (np.uint64) the batch-wide index into piece_id of the
+    row's first body piece; word_id (np.int32, (n_rows, max_len), None without word_ids) the document-relative index of
+    each body position's token, -1 elsewhere; n_cut counts the units with more pieces than a row's body holds."""
+    __slots__ = ("unit_row_off", "input_ids", "row_len", "row_piece0", "word_id", "n_units", "n_rows", "n_cut", "max_len")
+
+    def __init__(self, unit_row_off, input_ids, row_len, row_piece0, word_id, n_units, n_rows, n_cut, max_len):
+        self.unit_row_off, self.input_ids, self.row_len, self.row_piece0, self.word_id = unit_row_off, input_ids, row_len, row_piece0, word_id
+        self.n_units, self.n_rows, self.n_cut, self.max_len = n_units, n_rows, n_cut, max_len
+
+    def attention_mask(self):
+        """(n_rows, max_len) np.int32: 1 in front of the padding."""
+        return (np.arange(self.max_len, dtype=np.uint32)[None, :] < self.row_len[:, None]).astype(np.int32)
+
+
+def _encoded_of(v, copy=True) -> Encoded:
+    """Host arrays of a dtk_encode_view whose pointers are host pointers."""
+    def arr(ptr, n, dt):
+        if n == 0 or not ptr:
+            return np.zeros(0, dt)
+        a = np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(ptr), dtype=dt)
+        return a.copy() if copy else a
+    nu, nr, ml = int(v.n_units), int(v.n_rows), int(v.max_len)
+    return Encoded(arr(v.unit_row_off, nu + 1, np.uint64), arr(v.input_ids, nr * ml, np.int32).reshape(nr, ml),
+                   arr(v.row_len, nr, np.uint32), arr(v.row_piece0, nr, np.uint64),
+                   arr(v.word_id, nr * ml, np.int32).reshape(nr, ml) if v.word_id else None, nu, nr, int(v.n_cut), ml)
+
+
+def encode_rows(piece_off, piece_id, unit_tok_end, max_len, cls_id, sep_id, pad_id, stride=0, first_window=False,
+                word_ids=False, tok_off=None, cap_rows=None) -> Encoded:
+    """dtk_encode_rows_mem: the encoding rule on the host, with the code the kernels run.  The units are token ranges:
+    unit u is [unit_tok_end[u - 1], unit_tok_end[u]) batch-wide, from 0; tok_off is needed for word_ids.  Needs no
+    device.  cap_rows: room for that many rows (default: enough); with more the call raises DatokGpuError E_CAPACITY
+    whose .needed is the count."""
+    piece_off = np.ascontiguousarray(piece_off, dtype=np.uint64)
+    piece_id = np.ascontiguousarray(piece_id, dtype=np.int32)
+    ends = np.ascontiguousarray(unit_tok_end, dtype=np.uint64)
+    toff = None if tok_off is None else np.ascontiguousarray(tok_off, dtype=np.uint64)
+    spec = _encode_spec(max_len, cls_id, sep_id, pad_id, _lib.ENC_DOCUMENT, stride, first_window, word_ids)
+    n_tok, n_units = len(piece_off) - 1, len(ends)
+    n_rows, n_cut = C.c_uint64(0), C.c_uint64(0)
+    off = np.zeros(n_units + 1, np.uint64)
+    ml = max(int(max_len), 1)
+
+    def call(cap):
+        ids = np.zeros((max(cap, 1), ml), np.int32)
+        words = np.zeros((max(cap, 1), ml), np.int32) if word_ids else None
+        rl, p0 = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint64)
+        rc = lib().dtk_encode_rows_mem(C.byref(spec), piece_off.ctypes.data, n_tok, piece_id.ctypes.data if len(piece_id) else None,
+                                       ends.ctypes.data if n_units else None, n_units,
+                                       toff.ctypes.data if toff is not None else None, 0 if toff is None else len(toff) - 1,
+                                       cap, off.ctypes.data, ids.ctypes.data, rl.ctypes.data, p0.ctypes.data,
+                                       words.ctypes.data if words is not None else None, C.byref(n_rows), C.byref(n_cut))
+        return rc, ids, words, rl, p0
+    rc, ids, words, rl, p0 = call(0 if cap_rows is None else int(cap_rows))
+    if rc == _lib.E_CAPACITY and cap_rows is None:
+        rc, ids, words, rl, p0 = call(int(n_rows.value))
+    if rc != _lib.OK:
+        e = _lib.DatokGpuError(rc, "dtk_encode_rows_mem")
+        e.needed = int(n_rows.value) if rc == _lib.E_CAPACITY else None
+        raise e
+    n = int(n_rows.value)
+    return Encoded(off, ids[:n], rl[:n], p0[:n], None if words is None else words[:n], n_units, n, int(n_cut.value), int(max_len))
+
+
 class Batch:
     """dtk_batch: device buffers + one HIP stream for many documents per launch."""
 
@@ -836,6 +916,27 @@ class Batch:
         check(fn(self._h, C.byref(v)), "dtk_batch_pieces_device" if device else "dtk_batch_pieces_host")
         return v if device else _pieces_of(v, copy)
 
+    def set_encode(self, max_len, cls_id=-1, sep_id=-1, pad_id=0, unit="sentence", stride=0, first_window=False,
+                   word_ids=False, rows_home=True):
+        """The next runs' sentences (unit="sentence") or documents ("document") become fixed-length model input rows
+        behind the WordPiece split (set_wordpiece must be attached too): cls_id, the pieces, sep_id, pad_id up to
+        max_len; -1 for cls_id / sep_id leaves the position out.  A unit with more pieces than a row's body is cut into
+        windows that share `stride` pieces (first_window: only the first is kept).  word_ids: also each position's token.
+        rows_home: the rows come home with the other result copies; False: they stay in HBM until encoded() asks.
+        max_len=None turns it off."""
+        _set_encode(lib().dtk_batch_set_encode, "dtk_batch_set_encode", self, max_len,
+                    dict(cls_id=cls_id, sep_id=sep_id, pad_id=pad_id, unit=unit, stride=stride, first_window=first_window,
+                         word_ids=word_ids, rows_home=rows_home))
+
+    def encoded(self, device=False, copy=True):
+        """The last run's model input rows: an Encoded.  copy=False: views of the batch's page-locked block, valid until
+        its next run.  device=True: the raw dtk_encode_view (device pointers).  E_STATE before a run, without an
+        encoding, without a split and after a run with NO_BYTE_OFFSETS."""
+        v = _lib.EncodeView()
+        fn = lib().dtk_batch_encoded_device if device else lib().dtk_batch_encoded_host
+        check(fn(self._h, C.byref(v)), "dtk_batch_encoded_device" if device else "dtk_batch_encoded_host")
+        return v if device else _encoded_of(v, copy)
+
     def set_result_fields(self, fields=R_ALL):
         """Which arrays result() brings to the host (the others come back empty)."""
         check(lib().dtk_batch_set_result_fields(self._h, int(fields)), "dtk_batch_set_result_fields")
@@ -940,6 +1041,14 @@ class Pipeline:
         over when its split has finished."""
         _set_wordpiece(lib().dtk_pipeline_set_wordpiece, "dtk_pipeline_set_wordpiece", self, v, prefix, unk_id, max_runes,
                        pieces_home)
+
+    def set_encode(self, max_len, cls_id=-1, sep_id=-1, pad_id=0, unit="sentence", stride=0, first_window=False,
+                   word_ids=False, rows_home=True):
+        """Batch.set_encode for every slice: on_slice reads a slice's rows with batch.encoded(); a slice is handed over
+        when its encode has finished.  Units and row_piece0 count from 0 in every slice."""
+        _set_encode(lib().dtk_pipeline_set_encode, "dtk_pipeline_set_encode", self, max_len,
+                    dict(cls_id=cls_id, sep_id=sep_id, pad_id=pad_id, unit=unit, stride=stride, first_window=first_window,
+                         word_ids=word_ids, rows_home=rows_home))
 
     def set_result_fields(self, fields):
         """Bring these result arrays (Batch.R_*) of every slice to the host, overlapped with the next slices' work."""

@@ -652,4 +652,38 @@ inline bool pieces(dtk_batch *b, dtk_piece_view *out, bool device = false) {
   return rc == DTK_OK;
 }
 
+// ---- sentences or documents as fixed-length model input rows on the device (dtk_batch_set_encode, datok_gpu.h): behind
+// the WordPiece split, cls_id / the unit's pieces / sep_id / pad_id up to max_len; a unit with more pieces than a row's
+// body is cut into windows that share `stride` pieces.
+struct EncodeSpec {
+  uint32_t max_len = 128;                 // the row width, counted with the special positions (at most 65 535)
+  int32_t cls_id = -1, sep_id = -1;       // -1: the position does not exist
+  int32_t pad_id = 0;
+  uint32_t unit = DTK_ENC_SENTENCE;       // or DTK_ENC_DOCUMENT
+  uint32_t stride = 0;                    // 0 <= stride < max_len - n_special
+  bool first_window = false;              // keep only window 0 of every unit: plain truncation
+  bool word_ids = false;                  // also deliver word_id
+  bool rows_home = true;                  // the rows come home with the batch's other result copies
+};
+
+// Attaches the encoding to a batch (spec == nullptr: off); false + log line for a spec outside its ranges.
+inline bool set_encode(dtk_batch *b, const EncodeSpec *spec) {
+  dtk_encode_spec s{};
+  if (spec)
+    s = dtk_encode_spec{spec->max_len, spec->cls_id, spec->sep_id, spec->pad_id, spec->unit, spec->stride,
+                        (spec->first_window ? (uint32_t)DTK_ENC_FIRST_WINDOW : 0u) | (spec->word_ids ? (uint32_t)DTK_ENC_WORD_IDS : 0u)};
+  const int rc = dtk_batch_set_encode(b, spec ? &s : nullptr, spec && spec->rows_home ? 1 : 0);
+  if (rc != DTK_OK) std::fprintf(stderr, "datok: encode: %s\n", dtk_strerror(rc));
+  return rc == DTK_OK;
+}
+
+// The last run's rows in page-locked host memory (device: device pointers), valid until the batch's next run: row
+// unit_row_off[u] + k is window k of unit u, input_ids[r * max_len + p] its position p.  false + log line on failure
+// (before a run, without an encoding, without a split, or after a run with DTK_NO_BYTE_OFFSETS).
+inline bool encoded(dtk_batch *b, dtk_encode_view *out, bool device = false) {
+  const int rc = device ? dtk_batch_encoded_device(b, out) : dtk_batch_encoded_host(b, out);
+  if (rc != DTK_OK) std::fprintf(stderr, "datok: encoded: %s\n", dtk_strerror(rc));
+  return rc == DTK_OK;
+}
+
 }  // namespace datok

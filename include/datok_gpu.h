@@ -541,6 +541,77 @@ typedef struct {
 int dtk_batch_pieces_device(dtk_batch *b, dtk_piece_view *out);
 int dtk_batch_pieces_host(dtk_batch *b, dtk_piece_view *out);
 
+/* ---- sentences or documents as fixed-length model input rows, on the device: the matrix input_ids[n_rows x max_len]
+ *      a BERT-style model takes, built behind the WordPiece split from what is resident in HBM.
+ *      An ENCODING is a dtk_encode_spec: max_len, the row width, counted with the special positions; cls_id and sep_id,
+ *      where a value >= 0 is written in front of / behind the body and -1 means that the position does not exist
+ *      (n_special is the number of the two that exist); pad_id >= 0; unit; stride, the pieces consecutive windows of one
+ *      unit share; flags.  With body = max_len - n_special and step = body - stride: body >= 1, 0 <= stride < body,
+ *      max_len <= 65 535, unit one of the two values, no unknown flag, cls_id and sep_id >= -1, pad_id >= 0 -- anything
+ *      else is DTK_E_ARG.
+ *        UNITS.  DTK_ENC_SENTENCE: one unit per row of the sentence table (dtk_sentence_view above), in its batch-wide
+ *      order; the unit's tokens are the row's [sen_tok_end[i - 1], sen_tok_end[i]) of its document, so a document without
+ *      a token has no unit.  DTK_ENC_DOCUMENT: one unit per document, tokens [tok_off[d], tok_off[d + 1]); a document
+ *      without a token is a unit of zero pieces.  A unit is a contiguous token range and therefore a contiguous range
+ *      [P0, P0 + n) of piece_id.
+ *        WINDOWS.  The unit makes w rows: w = 1 if n <= body or DTK_ENC_FIRST_WINDOW is set (plain truncation), else
+ *      w = 1 + ceil((n - body) / step).  Window k holds the unit's pieces [k * step, min(k * step + body, n)).  Every unit
+ *      makes at least one row; a unit without a piece makes the row of the specials alone.  (This is the rule of the
+ *      `tokenizers` package's enable_truncation(max_length, stride): the first encoding followed by .overflowing.)
+ *        ROWS.  Row r = unit_row_off[u] + k is window k of unit u: cls_id if it exists, the window's piece_ids, sep_id if
+ *      it exists, pad_id up to max_len.
+ *        The outputs: n_units, n_rows; n_cut, the units with n > body; max_len; unit_row_off[n_units + 1], CSR;
+ *      input_ids[n_rows * max_len], row-major; row_len[n_rows], the positions in front of the padding, specials included
+ *      (the attention mask is pos < row_len); row_piece0[n_rows], the batch-wide index into piece_id of the row's first
+ *      body piece: position p of the body is piece row_piece0[r] + p - has_cls, from which piece_off gives the token and
+ *      piece_bend the bytes; and with DTK_ENC_WORD_IDS word_id[n_rows * max_len], the document-relative index of the
+ *      token the position's piece belongs to, -1 at specials and padding (NULL without the flag).  All of it is exact.
+ *      Rows of documents with a status bit follow the same rule on whatever token rows and pieces were delivered.
+ *        dtk_encode_rows_mem needs no device and runs the code the kernels run: a spec, piece_off[n_tok + 1], piece_id,
+ *      the units as an ascending array of batch-wide token ends (unit u's tokens are [unit_tok_end[u - 1],
+ *      unit_tok_end[u]), from 0), and -- only read with DTK_ENC_WORD_IDS -- tok_off[n_docs + 1].  It fills
+ *      unit_row_off[n_units + 1] and, for up to cap_rows rows, the other arrays; *n_rows is the row count, and with
+ *      cap_rows below it the call returns DTK_E_CAPACITY and no row array is complete.
+ *        Out of scope: dtk_stream_* (a sentence can span a cut, and the pieces of the slice before it are gone),
+ *      dtk_multi_*, pairs of sequences and token_type_ids, truncation and padding on the left. ---- */
+enum { DTK_ENC_SENTENCE = 0, DTK_ENC_DOCUMENT = 1 };
+enum { DTK_ENC_FIRST_WINDOW = 1, DTK_ENC_WORD_IDS = 2 };
+typedef struct {
+  uint32_t max_len;
+  int32_t cls_id, sep_id, pad_id;
+  uint32_t unit;     /* DTK_ENC_SENTENCE / DTK_ENC_DOCUMENT */
+  uint32_t stride;
+  uint32_t flags;    /* DTK_ENC_FIRST_WINDOW | DTK_ENC_WORD_IDS */
+} dtk_encode_spec;
+typedef struct {
+  uint64_t n_units, n_rows, n_cut;
+  uint32_t max_len;
+  const uint64_t *unit_row_off;
+  const int32_t *input_ids;
+  const uint32_t *row_len;
+  const uint64_t *row_piece0;
+  const int32_t *word_id;
+} dtk_encode_view;
+int dtk_encode_rows_mem(const dtk_encode_spec *spec, const uint64_t *piece_off, uint64_t n_tok, const int32_t *piece_id,
+                        const uint64_t *unit_tok_end, uint64_t n_units, const uint64_t *tok_off, uint32_t n_docs,
+                        uint64_t cap_rows, uint64_t *unit_row_off, int32_t *input_ids, uint32_t *row_len,
+                        uint64_t *row_piece0, int32_t *word_id, uint64_t *n_rows, uint64_t *n_cut);
+/* spec == NULL: off (the default).  The stage runs behind the split of dtk_batch_set_wordpiece, which must be attached
+ * too, on the download stream; for the sentence unit it builds the sentence table if nobody has.  rows_home has the
+ * meaning of pieces_home: != 0 brings the rows to page-locked memory with the other result copies, 0 leaves them in HBM
+ * until dtk_batch_encoded_host asks.  dtk_batch_download_begin enqueues the stage without waiting: the output block is
+ * sized by n_rows <= n_units + n_pieces / step; a run whose split or whose sentence table had to be redone, or whose
+ * rows exceed the block, wrote no row and is encoded again when its rows are asked for -- no view ever shows a partial
+ * table.  (With documents in exact_doc the sentence table is finished on the host: the sentence unit then starts only
+ * when its rows are asked for.)
+ *   dtk_batch_encoded_device returns device pointers and dtk_batch_encoded_host page-locked host pointers, decided by
+ * the call alone; both are valid until the batch's next run, its next dtk_batch_set_encode / dtk_batch_set_wordpiece or
+ * its free.  A new spec or a new split makes a finished run be encoded anew when it is asked for.  DTK_E_STATE before a
+ * run, without an encoding, without a split, and after a run with DTK_NO_BYTE_OFFSETS. */
+int dtk_batch_set_encode(dtk_batch *b, const dtk_encode_spec *spec, int rows_home);
+int dtk_batch_encoded_device(dtk_batch *b, dtk_encode_view *out);
+int dtk_batch_encoded_host(dtk_batch *b, dtk_encode_view *out);
+
 /* bit of position 0 of document d in the bitmaps of dtk_result_view.ev_bits */
 #define DTK_EVENT_BIT(doc_off_d, d) (((uint64_t)(doc_off_d)) + (uint64_t)(d))
 
@@ -596,6 +667,9 @@ int dtk_pipeline_set_vocab(dtk_pipeline *p, const dtk_vocab *v, dtk_tally *t, in
  * over when its split has finished. */
 int dtk_pipeline_set_wordpiece(dtk_pipeline *p, const dtk_vocab *v, const uint8_t *prefix, uint32_t prefix_len,
                                int32_t unk_id, uint32_t max_runes, int pieces_home);
+/* dtk_batch_set_encode for every slice: a slice is handed over when its encode has finished, and `fn` reads it through
+ * dtk_batch_encoded_host.  Units and row_piece0 count from 0 in every slice, as piece_off does. */
+int dtk_pipeline_set_encode(dtk_pipeline *p, const dtk_encode_spec *spec, int rows_home);
 int dtk_pipeline_run(dtk_pipeline *p, const dtk_model *m, const uint8_t *text, const uint64_t *doc_off,
                      uint32_t n_docs, uint32_t flags, dtk_slice_fn fn, void *user);
 /* ---- one stream of any length: the reference tokenizes whatever its reader delivers (bufio.Reader, matrix.go:373;

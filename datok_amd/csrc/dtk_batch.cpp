@@ -73,9 +73,7 @@ dtk_batch::~dtk_batch() {
   if (stream) (void)hipStreamSynchronize(stream);
   if (up_stream) (void)hipStreamSynchronize(up_stream);
   if (dl_begun && !dl_waited) (void)hipEventSynchronize(ev_dl);
-  (void)ids_wait(this);
-  (void)wp_wait(this);
-  (void)enc_wait(this);
+  (void)derived_wait(this);
 }
 
 extern "C" void dtk_batch_free(dtk_batch *b) { delete b; }
@@ -115,9 +113,7 @@ extern "C" int dtk_batch_set_input(dtk_batch *b, const uint8_t *text, const uint
   if (total > b->max_bytes || total + n_docs + 64 >= (1ull << 32)) return DTK_E_CAPACITY;  // 32-bit position bits
   if (total && !text) return DTK_E_ARG;
   { int rc = wait_own(b); if (rc != DTK_OK) return rc; }  // the previous run may still read the buffers
-  { int rc = ids_wait(b); if (rc != DTK_OK) return rc; }  // (and its lookup on the download stream, the text)
-  { int rc = wp_wait(b); if (rc != DTK_OK) return rc; }
-  { int rc = enc_wait(b); if (rc != DTK_OK) return rc; }
+  { int rc = derived_wait(b); if (rc != DTK_OK) return rc; }  // (and its derived tables on the download stream, the text)
   hipStream_t us = b->up_stream ? b->up_stream : b->stream;
   if (total) HIP_TRY(hipMemcpyAsync(b->d_text_own, text, total, hipMemcpyHostToDevice, us));
   memcpy(b->h_off_pin.p, doc_off, ((size_t)n_docs + 1) * 8);
@@ -148,9 +144,7 @@ extern "C" int dtk_batch_set_input_device(dtk_batch *b, const void *d_text, cons
   // their own: a rejected call leaves the batch's input, its plan and its host offsets as they were.
   std::vector<uint64_t> off((size_t)n_docs + 1);
   HIP_TRY(hipMemcpy(off.data(), d_doc_off, ((size_t)n_docs + 1) * 8, hipMemcpyDeviceToHost));
-  { const int rc = ids_wait(b); if (rc != DTK_OK) return rc; }  // (a lookup still reads the input it belongs to)
-  { const int rc = wp_wait(b); if (rc != DTK_OK) return rc; }
-  { const int rc = enc_wait(b); if (rc != DTK_OK) return rc; }
+  { const int rc = derived_wait(b); if (rc != DTK_OK) return rc; }  // (a derived table still reads the input it belongs to)
   if (off[0] != 0 || off[n_docs] != total_bytes) return DTK_E_ARG;
   for (uint32_t d = 0; d < n_docs; d++)
     if (off[d + 1] < off[d] || off[d + 1] - off[d] >= 0x7FFFFFF0ull) return DTK_E_ARG;
@@ -452,13 +446,13 @@ extern "C" int dtk_batch_run(const dtk_model *m, dtk_batch *b, uint32_t flags) {
   b->dl_begun = false;
   b->blk_pending = b->blk_failed = 0;
   b->evl_pending = false; b->evl_need = 0;
-  b->sen_built = b->sen_home = b->sen_done = false; b->sen_need = 0; b->sen_waited = true;
-  { const int rc_ = ids_wait(b); if (rc_ != DTK_OK) return rc_; }
-  b->ids_built = false;
-  { const int rc_ = wp_wait(b); if (rc_ != DTK_OK) return rc_; }
-  b->wp_built = false;
-  { const int rc_ = enc_wait(b); if (rc_ != DTK_OK) return rc_; }
-  b->enc_built = false; b->enc_need = 0;
+  // (the last run's derived tables read the result arrays this one writes.  Each is waited for by its own event: one
+  //  enqueued without a wait has ev_dl or another table's event behind it, and this does not rely on that)
+  { const int rc_ = derived_wait(b); if (rc_ != DTK_OK) return rc_; }
+  b->sen.new_run(); b->sen.done = false;
+  b->ids.new_run();
+  b->pieces.new_run(true);  // (need is kept: what a run of this batch needed, the next ones start with)
+  b->enc.new_run();
   if (b->up_pending) {  // the kernels wait for the input's upload on the other stream
     HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_up, 0));
     b->up_pending = false;

@@ -1,4 +1,4 @@
-// dtk_host.h -- what the host units of libdatok_gpu.so (dtk_model, dtk_foma, dtk_batch, dtk_results, dtk_slice .cpp) share:
+// dtk_host.h -- what the host units of libdatok_gpu.so (dtk_model, dtk_foma, dtk_batch, dtk_results, dtk_derived, dtk_slice .cpp) share:
 // the model and batch objects, the error state, the test hooks, and helpers (hidden, not exported).  No .hip unit includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -289,81 +289,63 @@ struct dtk_batch {
   uint64_t evl_copied = 0;         // rows the last enqueued copies of the list hold
   uint64_t evl_need = 0;           // nonzero: this run's list has that many rows, more than the bound (dtk_batch_result_host saw it)
   bool evl_pending = false;        // a list is on its way whose count nobody has looked at yet
-  // DTK_R_SENTENCES / dtk_batch_sentences_*: the sentence table (dtk_sentences.hip), built on the download stream into
-  // one block of dtk_mirror.h -- one copy brings all of it.  Sized for n_sent rows; the count word says whether that
-  // was enough (sen_need), as with the event list.
-  struct Sen : MirrorBlock {
+  // The derived tables (dtk_derived.cpp): four blocks of dtk_mirror.h, each computed on the download stream behind
+  // finish() and kept by the one protocol of DerivedBlock.
+  // DTK_R_SENTENCES / dtk_batch_sentences_*: the sentence table (dtk_sentences.hip) -- one copy brings all of it.  Sized
+  // for n_sent rows; the count word says whether that was enough (need), as with the event list.
+  struct Sen : DerivedBlock {
     Piece<uint64_t> off;                   // documents + 1
     Piece<uint32_t> tok_end, bstart, bend; // rows
     Piece<int32_t> rstart, rend;
     Piece<uint32_t> tse, cnt;              // texts; the count word
+    bool done = false;                     // the count has been looked at and fits (and exact documents are spliced in)
+    uint64_t n = 0;                        // rows of the finished table
   } sen;
   DevArray<uint32_t> d_sen_ws;     // device only: a row's bit | document | first token, and the tiles' two words
-  Event ev_sen;                    // behind the table's kernels and its last enqueued copy
-  bool sen_built = false;          // the kernels have been enqueued for this run, for cap(sen.tok_end) rows
-  bool sen_home = false;           // ... and the copy of the whole block (else at most the count word's)
-  bool sen_waited = true;          // ev_sen has been waited for: what was enqueued is there
-  bool sen_done = false;           // the count has been looked at and fits (and exact documents are spliced in)
-  uint64_t sen_n = 0;              // rows of the finished table
-  uint64_t sen_need = 0;           // nonzero: this run's table has that many rows, more than the bound
-  uint32_t sen_gen = 0;            // counts the table's launches and splices (dtk_batch_set_encode reads the table)
-  // dtk_batch_set_vocab: every token of a run looked up in a vocabulary (dtk_tokenid.hip), on the download stream behind
-  // finish().  One block of dtk_mirror.h: the unknown counter, then one id per token; the counter always comes home,
-  // the ids with ids_home or when dtk_batch_token_ids_host asks.  The kernel runs once per run, so a tally gets a run's
-  // tokens once however often the ids are asked for or copied.
+  // dtk_batch_set_vocab: every token of a run looked up in a vocabulary (dtk_tokenid.hip).  The unknown counter, then one
+  // id per token; the counter always comes home, the ids with ids_home or when dtk_batch_token_ids_host asks.  The
+  // kernel runs once per run, so a tally gets a run's tokens once however often the ids are asked for or copied.
   const dtk_vocab *vocab = nullptr;
   dtk_tally *tally = nullptr;
   bool ids_home = false;
-  struct Ids : MirrorBlock {
+  struct Ids : DerivedBlock {
     Piece<uint64_t> cnt;
     Piece<int32_t> id;
   } ids;
-  Event ev_ids;                    // behind the lookup and the last enqueued copy of its block
-  bool ids_built = false;          // the lookup has been enqueued for this run
-  bool ids_waited = true;          // ev_ids has been waited for
-  // dtk_batch_set_wordpiece: every token of a run split into WordPiece ids (dtk_wordpiece.hip), on the download stream
-  // behind finish(), once per run.  One block of dtk_mirror.h: the two counters (pieces, unknown tokens), piece_off, then
-  // the pieces' ids and ends at a capacity the host states before the count is known (wp_cap_of); the counters always
-  // come home, and a run with more pieces than that is split again into a block that holds them (wp_finish).
+  // dtk_batch_set_wordpiece: every token of a run split into WordPiece ids (dtk_wordpiece.hip), once per run.  The two
+  // counters (pieces, unknown tokens), piece_off, then the pieces' ids and ends at a capacity the host states before the
+  // count is known (wp_cap_of); the counters always come home, and a run with more pieces than that is split again into
+  // a block that holds them (wp_finish).  need is the most pieces a run of this batch had beyond what its first block
+  // held, and is kept for the next runs.
   const dtk_vocab *wp_vocab = nullptr;
   DtkWpRule wp_rule{};
   bool wp_home = false;
-  struct Pieces : MirrorBlock {
+  struct Pieces : DerivedBlock {
     Piece<uint64_t> cnt;           // [n_pieces, n_unknown]
     Piece<uint64_t> off;           // n_tok + 1
-    Piece<int32_t> id;             // wp_cap
-    Piece<uint32_t> bend;          // wp_cap
+    Piece<int32_t> id;             // the block's capacity in pieces
+    Piece<uint32_t> bend;          // the same
   } pieces;
   DevArray<uint64_t> d_wp_ws;      // the scan's tile sums (tiles + 1), then 8 bytes per token between the two passes
-  uint64_t wp_cap = 0;             // pieces the block holds
-  uint64_t wp_need = 0;            // the most pieces a run of this batch had beyond what its first block held (kept for the next runs)
-  Event ev_wp;                     // behind the split and the last enqueued copy of its block
-  bool wp_built = false;           // the split has been enqueued for this run
-  bool wp_waited = true;           // ev_wp has been waited for
-  uint32_t wp_gen = 0;             // counts the split's launches: what was computed from the pieces knows which it read
-  // dtk_batch_set_encode: the run's sentences or documents as model input rows (dtk_encode.hip), on the download stream
-  // behind the split and, for the sentence unit, behind the sentence table.  One block of dtk_mirror.h, sized by a bound
-  // the host states before any count is known (enc_enqueue); the counter block travels beside it and always comes home.
-  // A run whose pieces or sentence table were made anew since (wp_gen, sen_gen), or whose rows outgrew the block, wrote
-  // no row and is encoded again (enc_finish).
+  // dtk_batch_set_encode: the run's sentences or documents as model input rows (dtk_encode.hip), behind the split and,
+  // for the sentence unit, behind the sentence table.  Sized by a bound the host states before any count is known
+  // (enc_enqueue).  A run whose pieces or sentence table were made anew since (read), or whose rows outgrew the block,
+  // wrote no row and is encoded again (enc_finish).
   bool enc_on = false;
   DtkEncRule enc_rule{};
   bool enc_home = false;
-  struct Enc : MirrorBlock {
-    Piece<int32_t> ids, word;      // rows_cap * max_len each (word: 0 without DTK_ENC_WORD_IDS); 16-byte aligned
-    Piece<uint64_t> piece0;        // rows_cap
+  struct Enc : DerivedBlock {
+    Piece<int32_t> ids, word;      // rows * max_len each (word: 0 without DTK_ENC_WORD_IDS); 16-byte aligned
+    Piece<uint64_t> piece0;        // rows
     Piece<uint64_t> off;           // units_cap + 1
-    Piece<uint32_t> len;           // rows_cap
+    Piece<uint32_t> len;           // rows: the block's capacity
+    DerivedReads read;             // of the enqueued encode: pieces.gen, and sen.gen (sentence unit, else 0)
   } enc;
-  DevArray<uint64_t> d_enc_cnt;    // [n_rows, n_cut, n_units, ok]
+  // [n_rows, n_cut, n_units, ok], beside the block and no piece of it: the counters always come home, and a block whose
+  // rows stay on the device has no page-locked copy (fit(false)) for them to land in
+  DevArray<uint64_t> d_enc_cnt;
   PinBuf h_enc_cnt;
   DevArray<uint64_t> d_enc_ws;     // the scan's tile sums (tiles + 1), then a DtkEncUnit per unit
-  uint64_t enc_rows_cap = 0;       // rows the block holds
-  uint64_t enc_need = 0;           // nonzero: this run has that many rows, more than the bound
-  uint32_t enc_wp_gen = 0, enc_sen_gen = 0;  // what the enqueued encode read
-  Event ev_enc;                    // behind the encode and the last enqueued copy of its block
-  bool enc_built = false;          // the encode has been enqueued for this run
-  bool enc_waited = true;          // ev_enc has been waited for
   uint64_t max_doc_bytes = 0;     // of the current input (what decides whether the narrow form exists)
   bool max_doc_valid = false;
   Stream dl_stream;                 // created with the first download, unless the caller lends one (a pipeline's slices share one:
@@ -397,9 +379,12 @@ DtkSym sym_of(const dtk_batch *b);
 DtkWalkArgs walk_args(dtk_batch *b);
 int finish(dtk_batch *b);
 int launch_to_host(dtk_batch *b);
-int ids_wait(dtk_batch *b);  // what the last lookup enqueued has finished (the text and the block may be touched again)
-int wp_wait(dtk_batch *b);   // ... and the last WordPiece split
-int enc_wait(dtk_batch *b);  // ... and the last encode
+// dtk_derived.cpp: what the four derived tables last enqueued has finished -- the input, the result arrays and the tables'
+// blocks may be touched again.  Every stage is waited for even after a failure; the first failure is returned.
+int derived_wait(dtk_batch *b);
+// ... and what the next download enqueues of them, each in its own state (dtk_batch_download_begin)
+int derived_enqueue(dtk_batch *b);
+int sen_enqueue(dtk_batch *b, bool home);  // DTK_R_SENTENCES: the table's kernels and the copy of its block
 bool enc_rule_of(const dtk_encode_spec *s, DtkEncRule *r);  // dtk_encode.cpp: a spec checked and made into the rule (false: DTK_E_ARG)
 // The next runs of a one-document batch walk a slice of a stream: open_slice (0: the window ends where the stream
 // does) and the record to start from (null: the stream's beginning).  batch_cut: the last run's cut block, behind finish().

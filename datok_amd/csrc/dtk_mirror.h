@@ -1,9 +1,11 @@
 // dtk_mirror.h -- a block in device memory and its page-locked copy, of one byte layout that is fixed before anything is
 // enqueued: the tables a download computes on its stream and brings home (a slice's bytes, offsets and sentence rows,
-// dtk_slice.cpp; the batch's sentence table, dtk_results.cpp).  The first copies are sized by a bound the host can state
+// dtk_slice.cpp; the batch's derived tables, dtk_derived.cpp).  The first copies are sized by a bound the host can state
 // early; a trailer or count word in the block says whether the bound held, and what is missing comes at delivery.
 #pragma once
 #include <stdint.h>
+
+#include "../../include/datok_gpu.h"
 
 #include <algorithm>
 #include <vector>
@@ -48,7 +50,43 @@ struct MirrorLayout {
     joins_at = n == q.cap ? q.at + ((q.cap * q.size + 7u) & ~7ull) : ~0ull;
     q.home = n;
   }
+  void all_home() {  // the host has written the page-locked copy itself: nothing is missing, nothing is asked for
+    for (Part &q : parts) q.home = q.cap;
+    pending.clear();
+  }
 };
+
+// The state of a derived table, the part without a HIP call: a table that is computed once per
+// run into a block sized by a bound, with a count word that says whether the bound held.
+struct DerivedState {
+  bool built = false;  // the kernels have been enqueued for this run, into the block as it is described
+  uint32_t gen = 0;    // counts launches and rewrites: what is computed from the table knows which state it read
+  uint64_t need = 0;   // nonzero: a run had that many elements, more than the bound
+  void launched() { built = true; gen++; }
+  void new_run(bool keep_need = false) { built = false; if (!keep_need) need = 0; }
+};
+
+// What a table computed from two others read of them: stale exactly when either has moved since.
+struct DerivedReads {
+  uint32_t a = 0, b = 0;
+  bool stale(uint32_t a_now, uint32_t b_now) const { return a != a_now || b != b_now; }
+};
+
+// Completes a table.  step(): enqueues what is missing and waits for it; fits(n): the count as it came home -- true, or n
+// elements are needed and nothing was written.  Then once more, into a block of that size: a run's count cannot grow, so a
+// second overflow is an error.
+template <class Step, class Fits>
+int derived_complete(DerivedState &s, Step step, Fits fits) {
+  for (int round = 0;; round++) {
+    const int rc = step();
+    if (rc != DTK_OK) return rc;
+    uint64_t n = 0;
+    if (fits(n)) return DTK_OK;
+    if (round) return DTK_E_STATE;
+    s.need = n;
+    s.built = false;
+  }
+}
 
 #ifndef DTK_MIRROR_LAYOUT_ONLY
 #include "dtk_own.h"
@@ -77,6 +115,30 @@ struct MirrorBlock : MirrorLayout, NoCopy {
     return DTK_OK;
   }
   void landed() { in_flight = false; }  // the caller has waited for the stream, or for an event behind the copies
+};
+
+// A derived table: its blocks, its state, and the event behind what was last enqueued for it.  Nobody touches the
+// table's inputs or its blocks before wait().
+struct DerivedBlock : MirrorBlock, DerivedState {
+  Event ev;
+  bool waited = true;  // ev has been waited for: what was enqueued is there
+  // Copies the pending ranges and records behind them and behind what the caller has just enqueued (`launched`: kernels
+  // that asked for no copy).  Nothing of either: no HIP call.
+  int record(hipStream_t s, bool launched = false) {
+    if (pending.empty() && !launched) return DTK_OK;
+    int rc;
+    if ((rc = issue(s)) != DTK_OK || (rc = ev.ensure(hipEventDisableTiming)) != DTK_OK) return rc;
+    HIP_TRY(hipEventRecord(ev, s));
+    waited = false;
+    return DTK_OK;
+  }
+  int wait() {
+    if (waited) return DTK_OK;
+    HIP_TRY(hipEventSynchronize(ev));
+    waited = true;
+    landed();
+    return DTK_OK;
+  }
 };
 #endif
 

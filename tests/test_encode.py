@@ -14,9 +14,9 @@ import wordpiece
 from conftest import MODELS
 from encode import Spec
 from test_event_list import _pipeline_documents
-from test_sentences import _crafted
-from test_token_ids import DeviceInput, _from_device
-from test_wordpiece import _corpus_vocab, _memory_type, _runtime
+from test_sentences import _assert_table, _crafted
+from test_token_ids import DeviceInput, _assert_ids, _from_device
+from test_wordpiece import _assert_pieces, _corpus_vocab, _memory_type, _runtime
 
 NO_BYTE_OFFSETS = 512
 MODELS_DE = ("tokenizer_de.matok", "tokenizer_de.datok")
@@ -269,6 +269,40 @@ def test_exact_pass_documents_under_sentence(tmp_path, rows_home):
     words = [b"[UNK]", b"a", b"b", b"##a", b"##b", b".", b"ab"]
     e, r, p, ns = _run(tok, docs, datok_amd.Vocab(words), Spec(6, 1, 2, 0, 2, word_ids=True), "sentence", rows_home=rows_home)
     assert 0 < len(r.exact) < len(docs) and e.n_cut > 0
+
+
+# ------------------------------------------------------------- 7b: a new input right behind a begun download
+@pytest.mark.gpu
+def test_new_input_behind_a_begun_download(gpu, german):
+    """Ids, pieces, sentence table and rows of one run are enqueued by download_begin() alone, with nothing of them coming
+    home, and nobody asks for any of them: the next set_input and run, of other text in documents of the same lengths,
+    follow at once.  Only the batch's wait for its derived tables stands between the first run's kernels on the download
+    stream and the overwriting of what they read.  The second run's four tables are its own."""
+    from datok_amd import corpus
+    first = german["docs"][:6]
+    other = [d.decode("utf-8", "ignore").encode() for d in (x[:len(f)] for x, f in zip(german["docs"][6:12], first))]
+    second = [d + b" " * (len(f) - len(d)) for d, f in zip(other, first)]
+    assert [len(d) for d in second] == [len(d) for d in first] and second != first
+    spec = Spec(16, CLS, SEP, PAD, 4, word_ids=True)
+    tok = gpu(MODELS_DE[0])
+    text1, off1 = corpus.concat_docs(first)
+    text2, off2 = corpus.concat_docs(second)
+    assert np.array_equal(off1, off2)
+    with _B()(len(text1), len(first)) as b:
+        b.set_vocab(german["vocab"], ids_home=False)
+        b.set_wordpiece(german["vocab"], pieces_home=False)
+        b.set_encode(unit="sentence", rows_home=False, **spec.kw())
+        b.set_input(text1, off1)
+        b.run(tok, 0)
+        b.download_begin()
+        b.set_input(text2, off2)
+        b.run(tok, 0)
+        e, r, p, ns = _check(b, spec, "sentence", "second run")
+        ids, n_unknown = b.token_ids()
+        _assert_ids(ids, n_unknown, r, text2, off2, german["words"])
+        _assert_pieces(p, r, text2, off2, german["words"])
+        _assert_table(b.sentences(), r, off2)
+        assert e.n_rows >= e.n_units > len(second) and p.n_pieces > len(ids) > 0
 
 
 # ----------------------------------------------------------------------------------------------- 8: pipeline

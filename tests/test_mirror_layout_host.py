@@ -2,7 +2,9 @@
 behaviour sanitizers on) describes the tables that are built on it -- a slice's offsets in both forms, its sentence rows,
 the batch's sentence table -- and prints where the pieces lie and which byte ranges the first copies and the late
 requests ask for.  The test checks them against the rules stated here, in Python: pieces on multiples of 8, one home count
-per piece, ranges that join only across a piece's end, and the number of first copies a slice enqueues."""
+per piece, ranges that join only across a piece's end, and the number of first copies a slice enqueues.  The same program
+drives the plain-data part of a derived table's protocol (DerivedState, DerivedReads, derived_complete) and prints what it
+did: the lines tagged X."""
 import os
 import subprocess
 
@@ -44,7 +46,49 @@ template <class T> void late(MirrorLayout &L, Piece<T> p) {   // two more elemen
 }
 template <class... P> void late_all(MirrorLayout &L, P... p) { (late(L, p), ...); }
 
+// A stage as dtk_derived.cpp drives one: step() launches where nothing is built, into a block of max(need, bound)
+// elements; the count word then reads counts[launch - 1].
+namespace { struct Stage { DerivedState s; int launches = 0; uint64_t cap = 0; }; }
+static void complete(const char *tag, Stage &g, uint64_t bound, std::vector<uint64_t> counts, int step_rc = 0) {
+  int reads = 0;
+  const int rc = derived_complete(
+      g.s, [&] { if (!g.s.built) { g.cap = std::max(g.s.need, bound); g.s.launched(); g.launches++; } return step_rc; },
+      [&](uint64_t &n) { reads++; n = counts[g.launches - 1]; return n <= g.cap; });
+  std::printf("X %s %d %d %d %d %llu %llu %u\n", tag, rc, g.launches, reads, (int)g.s.built, (ull)g.s.need, (ull)g.cap, g.s.gen);
+}
+static void protocol() {
+  { Stage g; complete("fits", g, 4, {3}); complete("fits_again", g, 4, {3}); }
+  { Stage g; complete("overflow", g, 4, {10, 10}); }
+  { Stage g; complete("overflow_twice", g, 4, {10, 20}); }
+  { Stage g; complete("step_fails", g, 4, {3}, -5); }
+  for (int keep = 0; keep < 2; keep++) {   // a new run: the need resets, or (the pieces) survives
+    Stage g; complete(keep ? "run1_keep" : "run1_reset", g, 4, {10, 10});
+    g.s.new_run(keep != 0);
+    std::printf("X %s %d %llu %u\n", keep ? "new_run_keep" : "new_run_reset", (int)g.s.built, (ull)g.s.need, g.s.gen);
+    g.launches = 0; complete(keep ? "run2_keep" : "run2_reset", g, 4, {10, 10});
+  }
+  const DerivedReads r{3, 7};                // what a consumer recorded: (g_wp, g_sen)
+  std::printf("X stale %d %d %d %d\n", (int)r.stale(3, 7), (int)r.stale(4, 7), (int)r.stale(3, 8), (int)r.stale(4, 8));
+  // the batch's sentence table as sen_enqueue asks for it: the pieces in the block's order, the count word last
+  for (int mode = 0; mode < 3; mode++) {     // 0: whole block at build; 1: count only; 2: count at build, the block later
+    MirrorLayout L;
+    Piece<uint64_t> off; Piece<uint32_t> tok_end, bstart, bend; Piece<int32_t> rs, re; Piece<uint32_t> tse, cnt;
+    L.add(off, 4); L.add(tok_end, 5); L.add(bstart, 5); L.add(bend, 5); L.add(rs, 5); L.add(re, 5); L.add(tse, 3); L.add(cnt, 1);
+    auto block = [&] { L.bring(off, 4); L.bring(tok_end, 5); L.bring(bstart, 5); L.bring(bend, 5); L.bring(rs, 5); L.bring(re, 5); L.bring(tse, 3); };
+    if (mode == 0) block();
+    L.bring(cnt, 1);
+    std::printf("X sen%d %llu %llu", mode, (ull)L.at(cnt), (ull)L.bytes);
+    ranges("", L);
+    if (mode == 2) { block(); L.bring(cnt, 1); std::printf("X sen2_later %llu %llu", (ull)L.at(tse), (ull)L.at(cnt)); ranges("", L); }
+    if (mode == 1) {                         // the host wrote the whole copy itself (the splice): nothing is missing
+      L.all_home(); block(); L.bring(cnt, 1);
+      std::printf("X sen1_all_home %llu %llu", (ull)L.home(tok_end), (ull)L.home(cnt)); ranges("", L);
+    }
+  }
+}
+
 int main() {
+  protocol();
   const uint64_t tokens[] = {0, 1, 63, 64, 65}, caps[] = {0, 1, 7};
   const int homes[] = {0, 1, -1};
   for (uint64_t nt : tokens) for (uint64_t cap : caps) for (int hm : homes) {
@@ -163,6 +207,14 @@ def _parse(lines):
     return cases
 
 
+_PROTOCOL = {}   # the X lines of the program's one run: tag -> fields
+
+
+@pytest.fixture(scope="module")
+def protocol(cases):
+    return {k: [int(x) if ":" not in x else tuple(int(y) for y in x.split(":")) for x in v] for k, v in _PROTOCOL.items()}
+
+
 @pytest.fixture(scope="module")
 def cases(tmp_path_factory):
     d = tmp_path_factory.mktemp("mirror")
@@ -172,7 +224,8 @@ def cases(tmp_path_factory):
                            "-fno-sanitize-recover=all", "-I", CSRC, str(src), "-o", str(exe)])
     out = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert out.returncode == 0 and not out.stderr, out.stderr.decode()
-    got = _parse(out.stdout.decode().splitlines())
+    got = _parse(l for l in out.stdout.decode().splitlines() if not l.startswith("X "))
+    _PROTOCOL.update({f[1]: f[2:] for f in (l.split() for l in out.stdout.decode().splitlines()) if f[0] == "X"})
     assert len(got) == len(TOKENS) * len(CAPS) * len(HOMES) * 5
     return got
 
@@ -250,3 +303,39 @@ def test_late_requests_bring_exactly_the_missing_elements_once(cases):
                 assert first == [] and q["H"] == 0, (c, q)                      # a piece of no element: nothing
         if c["C"] is not None:
             assert c["C"] == (0, 0, 0)                                          # clear(): a new description starts empty
+
+
+E_STATE = -8   # DTK_E_STATE
+
+
+def test_a_table_that_overflows_is_launched_exactly_once_more(protocol):
+    # fields: rc, launches, count reads, built, need, capacity, gen
+    assert protocol["fits"] == [0, 1, 1, 1, 0, 4, 1]
+    assert protocol["fits_again"] == [0, 1, 1, 1, 0, 4, 1]               # complete already: no launch, this call reads the count once
+    assert protocol["overflow"] == [0, 2, 2, 1, 10, 10, 2]               # need is the count, the second block holds it
+    assert protocol["overflow_twice"] == [E_STATE, 2, 2, 1, 10, 10, 2]   # a run's count cannot grow: no third launch
+    assert protocol["step_fails"] == [-5, 1, 0, 1, 0, 4, 1]              # the step's error comes out, no count is read
+
+
+def test_a_new_run_clears_built_and_the_resetting_need_and_keeps_the_surviving_one(protocol):
+    assert protocol["run1_reset"] == protocol["run1_keep"] == [0, 2, 2, 1, 10, 10, 2]
+    assert protocol["new_run_reset"] == [0, 0, 2]                        # built, need, gen (launches are still counted)
+    assert protocol["new_run_keep"] == [0, 10, 2]
+    assert protocol["run2_reset"] == [0, 2, 2, 1, 10, 10, 4]             # the bound again, and the overflow again
+    assert protocol["run2_keep"] == [0, 1, 1, 1, 10, 10, 3]              # the run starts with the block the last one needed
+
+
+def test_a_consumer_is_stale_exactly_when_a_generation_it_read_has_moved(protocol):
+    assert protocol["stale"] == [0, 1, 1, 1]
+
+
+def test_sentence_table_bring_order_gives_one_range(protocol):
+    at_cnt, size = protocol["sen0"][:2]
+    assert size == at_cnt + 8
+    assert protocol["sen0"][2:] == [(0, at_cnt + 4)]                     # the whole block at build: one copy, the count word its end
+    assert protocol["sen1"][2:] == [(at_cnt, at_cnt + 4)]                # the count only: 4 bytes
+    assert protocol["sen2"][2:] == [(at_cnt, at_cnt + 4)]
+    at_tse, at_cnt2 = protocol["sen2_later"][:2]
+    assert at_cnt2 == at_cnt and at_tse + 3 * 4 <= at_cnt
+    assert protocol["sen2_later"][2:] == [(0, at_tse + 3 * 4)]           # the block later: one range that stops short of the count word
+    assert protocol["sen1_all_home"] == [5, 1]                           # all_home(): every piece whole, and nothing more to ask for

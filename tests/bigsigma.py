@@ -73,6 +73,71 @@ def oracle_of(blob):
     return _cache[id(blob)][1]
 
 
+# ---- device models by name, for the fixtures of the stream and batch-reader tests
+# name              what is loaded
+# <file>            the fixture file as it is
+# <file>:pairs      ... with the hook NO_DENSE: a double array walked as pairs
+# <file>:entries    ... with the hook SYM16: the stream holds the 16-bit entries, walked by the lean loop
+# <file>:entries-general   ... with SYM16 and GENERAL16: 16-bit entries on the general loop
+# de64.matok        enlarged_de(64): a model that has more than 255 entries by itself
+_HOOKS = {"": (), "pairs": ("NO_DENSE",), "entries": ("SYM16",), "entries-general": ("SYM16", "GENERAL16")}
+_LOOP_SWITCHES = ("DATOK_NO_FUSED", "DATOK_FORCE_WIDE", "DATOK_NO_DENSE", "DATOK_GENERAL16")
+
+
+def has_code_twin():
+    """False where the whole suite runs under DATOK_SYM16: then no load gives a stream of codes to compare with."""
+    return not os.environ.get("DATOK_SYM16")
+
+
+def device_model(name):
+    """(device tokenizer, oracle model) of `name`.  The hooks are read at model load only (dtk_model.cpp, build_images):
+    they are set around the load alone and put back to what the environment says, so that no later load in the process
+    sees them -- and a suite that runs whole under one of the switches stays under it."""
+    import tempfile
+    import datok_amd
+    from oracle import oracle as O
+    fname, _, how = name.partition(":")
+    configure = datok_amd.lib().dtk_debug_configure
+    for hook in _HOOKS[how]:
+        assert configure(hook.encode(), b"1") == 0
+    try:
+        if fname == "de64.matok":
+            blob = enlarged_de(64)
+            with tempfile.TemporaryDirectory() as where:
+                path = os.path.join(where, fname)
+                with open(path, "wb") as f:
+                    f.write(blob)
+                tok = datok_amd.load_tokenizer_file(path)
+            om = oracle_of(blob)
+        else:
+            path = os.path.join(MODELS, fname)
+            tok, om = datok_amd.load_tokenizer_file(path), O.Model(path)
+    finally:
+        for hook in _HOOKS[how]:
+            assert configure(hook.encode(), os.environ.get("DATOK_" + hook, "0").encode()) == 0
+    assert tok is not None, name
+    lean = not any(os.environ.get(k) for k in _LOOP_SWITCHES)      # (those switches select the general loop)
+    if how == "pairs":
+        assert tok.info["dense_states"] == 0, tok.info
+    elif how == "entries":
+        assert tok.info["stream_codes"] == 0 and (tok.info["lean_walk"] == 1 or not lean), tok.info
+    elif how == "entries-general":
+        assert tok.info["stream_codes"] == 0 and tok.info["lean_walk"] == 0, tok.info
+    elif fname == "de64.matok":
+        assert tok.info["stream_codes"] == 0, tok.info
+    return tok, om
+
+
+def invalid_documents():
+    """Documents for enlarged_de(64) with the new letters beside bytes that do not decode: two letters on either side of
+    an \\xff; tokens that end in \\xd0, the new alphabet's lead byte, without its continuation; one letter between two
+    \\xff; the first document again with a literal U+FFFD in the bad byte's place; valid text; an empty document; other
+    truncated sequences beside a letter."""
+    a, b, c, d, e = (x.encode() for x in LETTERS[:5])
+    return [a + b + b"\xff" + c + d + b" ef", b"Preis" + a + b"\xd0 hier und " + b + b"\xd0", b"\xff" + c + b"\xff gut",
+            a + b + "�".encode() + c + d + b" da", b"ganz normal", b"", b"x\xc3 " + e + b"\xf0\x9f\x98 z\x80" + e]
+
+
 # The window-edge documents put an item at every document-relative position 0 .. 2 W + 1 for a row of W entries.  The
 # library ships rows of 16 entries; rows of 32 are the variant it was measured against (DESIGN section 3).  The tests do
 # not ask the build which it is: they cover the longer one, which contains the other's positions.

@@ -3,15 +3,14 @@ GPU tier: the kernels of dtk_encode.hip and their plumbing through batch and pip
 tables with the definition of tests/encode.py applied to the SAME run's delivered tok_off, sentence table and pieces.
 The result is exact: every comparison is an equality."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+import bigsigma
 import craft
 import encode
 import wordpiece
-from conftest import MODELS
 from encode import Spec
 from test_event_list import _pipeline_documents
 from test_sentences import _assert_table, _crafted
@@ -31,9 +30,9 @@ def gpu():
     cache = {}
 
     def get(name):
+        """name: a fixture file, "<file>:entries" for its stream as 16-bit entries, or "de64.matok" (bigsigma.device_model)"""
         if name not in cache:
-            cache[name] = datok_amd.load_tokenizer_file(os.path.join(MODELS, name))
-            assert cache[name] is not None
+            cache[name] = bigsigma.device_model(name)[0]
         return cache[name]
     return get
 
@@ -254,7 +253,15 @@ def test_homes_and_word_ids(gpu, german, rows_home, pieces_home):
 @pytest.mark.gpu
 @pytest.mark.parametrize("unit", UNITS)
 def test_device_input_of_exactly_total_bytes(gpu, german, unit):
-    _run(gpu(MODELS_DE[0]), german["docs"], german["vocab"], Spec(65, CLS, SEP, PAD, 3, word_ids=True), unit, device_input=True)
+    """... and the same chain -- walk, split, rows -- where the stream holds 16-bit entries and two documents have bytes
+    that do not decode (the encode reads only pieces; the split beneath it reads the stream)."""
+    spec = Spec(65, CLS, SEP, PAD, 3, word_ids=True)
+    _run(gpu(MODELS_DE[0]), german["docs"], german["vocab"], spec, unit, device_input=True)
+    docs = german["docs"] + [b"ab\xffcd ef", b"x\xc3 y\xf0\x9f\x98 z\x80"]
+    e, r, p, ns = _run(gpu(MODELS_DE[0] + ":entries"), docs, german["vocab"], spec, unit, device_input=True)
+    from datok_amd import corpus
+    _assert_pieces(p, r, *corpus.concat_docs(docs), german["words"])
+    assert not r.status.any() and len(r.tok_off) == len(docs) + 1 and int(r.tok_off[-1] - r.tok_off[-3]) == 5
 
 
 # ------------------------------------------------------------------------------------ 7: exact-pass documents

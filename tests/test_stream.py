@@ -8,6 +8,7 @@ import sys
 
 import pytest
 
+import bigsigma
 import craft
 import streamcorpus as sc
 from conftest import MODELS, ROOT
@@ -20,27 +21,14 @@ _FATAL = 1 | 4 | 16 | 32 | 8
 
 @pytest.fixture(scope="module")
 def models():
-    """name -> (device tokenizer, oracle model); "tokenizer_de.datok:pairs": the double array walked as pairs."""
-    import datok_amd
-    from oracle import oracle as O
+    """name -> (device tokenizer, oracle model), as bigsigma.device_model names them: "tokenizer_de.datok:pairs" is the
+    double array walked as pairs, "<file>:entries" a stream of 16-bit entries on the lean loop, "<file>:entries-general"
+    the same stream on the general loop, "de64.matok" the enlarged model, which has such a stream by itself."""
     cache = {}
 
     def get(name):
         if name not in cache:
-            fname, _, how = name.partition(":")
-            path = os.path.join(MODELS, fname)
-            forced = os.environ.get("DATOK_NO_DENSE", "0")     # (the suite also runs whole under that switch)
-            if how == "pairs":
-                assert datok_amd.lib().dtk_debug_configure(b"NO_DENSE", b"1") == 0
-            try:
-                tok = datok_amd.load_tokenizer_file(path)
-            finally:
-                if how == "pairs":
-                    assert datok_amd.lib().dtk_debug_configure(b"NO_DENSE", forced.encode()) == 0
-            assert tok is not None
-            if how == "pairs":
-                assert tok.info["dense_states"] == 0
-            cache[name] = (tok, O.Model(path))
+            cache[name] = bigsigma.device_model(name)
         return cache[name]
     return get
 
@@ -94,10 +82,12 @@ def assert_stream(st, tok, om, raw, expect=None, read_size=None, slice_bytes=S):
 
 
 MODELS_1 = ["tokenizer_de.matok", "tokenizer_de.datok", "tokenizer_de.datok:pairs", "tokenizer_en.matok"]
+# the same automata over a stream of 16-bit entries: the lean loop, the double array's dense layout, the general loop
+MODELS_ENTRIES = ["tokenizer_de.matok:entries", "tokenizer_de.datok:entries", "tokenizer_de.matok:entries-general"]
 
 
 # ---- 1. the stream itself
-@pytest.mark.parametrize("name", MODELS_1)
+@pytest.mark.parametrize("name", MODELS_1 + MODELS_ENTRIES)
 def test_stream_calls_equal_the_oracles(models, whole, name):
     import datok_amd
     tok, om = models(name)
@@ -106,9 +96,30 @@ def test_stream_calls_equal_the_oracles(models, whole, name):
     with datok_amd.Stream(S) as st:
         slices = assert_stream(st, tok, om, raw, (calls, ost))
         assert len(slices) >= 12
+        if name in MODELS_ENTRIES:           # (how the reader hands out bytes and the depth do not meet the stream's format)
+            return
         assert_stream(st, tok, om, raw, (calls, ost), read_size=5000)        # short reads are retried
     with datok_amd.Stream(S, depth=2) as st:
         assert_stream(st, tok, om, raw, (calls, ost))
+
+
+def test_stream_calls_of_the_enlarged_model(models, whole):
+    """A model with more than 255 entries (bigsigma.enlarged_de): slices cut at verified sync points and the state
+    carried from slice to slice over 16-bit entries, on German text with the new characters spliced in -- letters, sentence
+    ends and blanks among them -- and on the same kind of text with bytes that do not decode."""
+    import datok_amd
+    import numpy as np
+    from test_stream_render import invalid_stream_spliced
+    tok, om = models("de64.matok")
+    german = whole("de", "tokenizer_de.matok", models("tokenizer_de.matok")[1])[0]
+    spliced = bigsigma.splice(german.replace(b"\x04", b" "), np.random.default_rng(3), limit=4 * S)
+    assert sum(spliced.count(c.encode()) for c in bigsigma.CHARS) >= 1000
+    with datok_amd.Stream(S) as st:
+        for raw in (spliced, invalid_stream_spliced()):
+            calls, ost = sc.oracle_calls(om, raw)
+            assert ost == 0
+            slices = assert_stream(st, tok, om, raw, (calls, ost))
+            assert len(slices) >= 4
 
 
 @pytest.mark.parametrize("name", MODELS_1)
@@ -137,14 +148,18 @@ def test_mirrors_write_the_oracles_bytes_in_every_mode(models, whole, name):
 
 
 # ---- 2. every alignment of a cut
-@pytest.mark.parametrize("name", ["tokenizer_de.matok", "tokenizer_de.datok", "tokenizer_de.datok:pairs"])
-@pytest.mark.parametrize("construct", list(sc.CONSTRUCTS))
+CUT_CASES = ([(c, n) for c in sc.CONSTRUCTS for n in ("tokenizer_de.matok", "tokenizer_de.datok", "tokenizer_de.datok:pairs")]
+             + [(c, "tokenizer_de.matok:entries") for c in ("token300", "token4000")])
+
+
+@pytest.mark.parametrize("construct,name", CUT_CASES)
 def test_every_alignment_of_a_cut(models, name, construct):
+    """(Over 16-bit entries: the two long tokens, whose carried position lies far into the tail, at three shifts.)"""
     import datok_amd
     from datok_amd import host
     tok, om = models(name)
     with datok_amd.Stream(S) as st:
-        for shift in range(41):
+        for shift in (range(41) if ":entries" not in name else (0, 1, 39)):
             raw = sc.construct_stream(construct, shift)
             slices = assert_stream(st, tok, om, raw)
             if construct == "token5000":

@@ -17,7 +17,7 @@ from streampos import CARRY0
 from test_stream import models, whole  # noqa: F401  (fixtures: the device and oracle models, the 200 KB streams)
 from test_stream_offsets_host import FIVE, assert_joined
 from test_stream_positions_host import empty_text_streams
-from test_stream_render import invalid_stream
+from test_stream_render import INVALID_MODELS, code_twin, invalid_stream_of
 
 pytestmark = pytest.mark.gpu
 
@@ -248,15 +248,26 @@ def test_dense_sentences_blanks_and_the_empty_stream(models, name):
 
 
 # ---- 7. bytes that do not decode
-def test_invalid_utf8_counts_as_one_rune_a_byte(models):
+@pytest.mark.parametrize("name", INVALID_MODELS)
+def test_invalid_utf8_counts_as_one_rune_a_byte(models, name):
     import datok_amd
-    tok, om = models("tokenizer_de.matok")
-    raw = invalid_stream()
+    tok, om = models(name)
+    raw = invalid_stream_of(name)
     assert om.transduce_doc(raw, 0).status == 0
+    mine = {}
     with datok_amd.Stream(S) as st:
         for nl, form in ((0, PLAIN), (NL, BLOCKED)):
-            slices = assert_offsets(st, tok, om, raw, nl, form)
-        assert len(slices) == 5
+            slices = mine[form] = assert_offsets(st, tok, om, raw, nl, form)
+        assert len(slices) == 5 if name != "de64.matok" else len(slices) >= 4
+        # (no bytes are rendered here: the arrays count an invalid byte as one rune, dtk_sym_is_start's two branches)
+        assert all(sl.out is None for sl in slices)
+    twin = code_twin(models, name)
+    if twin is not None:          # the same automaton and the same stream: any difference is the stream format's
+        with datok_amd.Stream(S) as st:
+            for nl, form in ((0, PLAIN), (NL, BLOCKED)):
+                for a, b in zip(assert_offsets(st, twin, om, raw, nl, form), mine[form]):
+                    assert all(np.array_equal(x, y) for x, y in zip(slice_parts(a), slice_parts(b)))
+                    assert a.r_carry_out == b.r_carry_out
 
 
 # ---- 8. later work on a slice

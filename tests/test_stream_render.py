@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import bigsigma
 import streamcorpus as sc
 from conftest import MODELS, ROOT
 from streamrender import FFFD, render_slice_ref
@@ -92,13 +93,17 @@ def test_rendered_stream_equals_the_oracles_bytes(models, whole, name):
 
 
 # ---- 2. every alignment of a cut
-@pytest.mark.parametrize("name", ["tokenizer_de.matok", "tokenizer_de.datok"])
-@pytest.mark.parametrize("construct", list(sc.CONSTRUCTS))
+CUT_CASES = ([(c, n) for c in sc.CONSTRUCTS for n in ("tokenizer_de.matok", "tokenizer_de.datok")]
+             + [(c, "tokenizer_de.matok:entries") for c in ("token300", "token4000")])
+
+
+@pytest.mark.parametrize("construct,name", CUT_CASES)
 def test_cut_alignment(models, name, construct):
+    """(Over 16-bit entries: the two long tokens, at three shifts.)"""
     import datok_amd
     tok, om = models(name)
     with datok_amd.Stream(S) as st:
-        for shift in (0, 1, 2, 3, 39):
+        for shift in ((0, 1, 2, 3, 39) if ":entries" not in name else (0, 1, 39)):
             raw = sc.construct_stream(construct, shift)
             slices = assert_rendered(st, tok, om, raw, 3)
             if construct == "token5000":
@@ -141,10 +146,10 @@ def test_dense_tokens_blanks_and_the_empty_stream(models, name):
 
 
 # ---- 4. bytes that do not decode
-def invalid_stream():
-    """Running text with \\xff, \\xc3 + blank and a truncated \\xe2\\x82 sown into tokens every 97 bytes; an \\xff as the last
-    byte in front of every window's byte S."""
-    b = bytearray(sc.running_text(5 * S, seed=21).replace(b"\x04", b" "))
+def _sow_invalid(text, leads=(0xC3,)):
+    """`text` with \\xff, a lead byte + blank (`leads` in turn) and a truncated \\xe2\\x82 sown into tokens every 97 bytes;
+    an \\xff as the last byte in front of every window's byte S."""
+    b = bytearray(text)
     n = len(b)
 
     def letter(i):
@@ -155,7 +160,7 @@ def invalid_stream():
             while j < n - 4 and not (letter(j) and letter(j - 1) and b[j + 1] == 0x20):
                 j += 1
             if j < n - 4:
-                b[j] = 0xC3
+                b[j] = leads[(k // 3) % len(leads)]
         else:
             while j < n - 4 and not (letter(j) and letter(j + 1) and letter(j + 2)):
                 j += 1
@@ -170,21 +175,68 @@ def invalid_stream():
     return bytes(b)
 
 
-def test_invalid_utf8_prints_as_replacement_runes(models):
+_invalid = {}
+
+
+def invalid_stream():
+    """Running text with \\xff, \\xc3 + blank and a truncated \\xe2\\x82 sown into tokens every 97 bytes; an \\xff as the last
+    byte in front of every window's byte S."""
+    if "plain" not in _invalid:
+        _invalid["plain"] = _sow_invalid(sc.running_text(5 * S, seed=21).replace(b"\x04", b" "))
+    return _invalid["plain"]
+
+
+def invalid_stream_spliced():
+    """The same text with the characters of the enlarged model spliced in (bigsigma.splice) before the same bytes are sown
+    by the same rule; every second lead byte in front of a blank is \\xd0, the lead byte of the new alphabet, left without
+    its continuation.  For "de64.matok"."""
+    if "spliced" not in _invalid:
+        text = sc.running_text(5 * S, seed=21).replace(b"\x04", b" ")
+        _invalid["spliced"] = _sow_invalid(bigsigma.splice(text, np.random.default_rng(7), limit=5 * S), leads=(0xC3, 0xD0))
+    return _invalid["spliced"]
+
+
+# the models of the tests of invalid bytes, here and in the three modules beside this one: codes; the same two automata
+# over 16-bit entries; a model that has such a stream by itself, on the stream that holds its characters
+INVALID_MODELS = ["tokenizer_de.matok", "tokenizer_de.matok:entries", "tokenizer_de.datok:entries", "de64.matok"]
+
+
+def invalid_stream_of(name):
+    return invalid_stream_spliced() if name == "de64.matok" else invalid_stream()
+
+
+def code_twin(models, name):
+    """The device model of the same file over a stream of codes, for an ":entries" name; else None.  Skips where the
+    suite runs whole under the switch that gives every model 16-bit entries (bigsigma.has_code_twin)."""
+    if ":entries" not in name:
+        return None
+    if not bigsigma.has_code_twin():
+        pytest.skip("DATOK_SYM16 is set: no load in this process gives the stream of codes to compare with")
+    return models(name.partition(":")[0])[0]
+
+
+@pytest.mark.parametrize("name", INVALID_MODELS)
+def test_invalid_utf8_prints_as_replacement_runes(models, name):
     import datok_amd
-    tok, om = models("tokenizer_de.matok")
-    raw = invalid_stream()
+    tok, om = models(name)
+    raw = invalid_stream_of(name)
     exp, est = om.transduce(raw, 3)
     assert est == 0 and exp.count(FFFD) >= 100 and raw.count(FFFD) == 0
     with datok_amd.Stream(S) as st:
         slices = assert_rendered(st, tok, om, raw, 3, exp=exp)
-        assert_rendered(st, tok, om, raw, 1)
+        ones = assert_rendered(st, tok, om, raw, 1)
+    assert len(slices) == 5 if name != "de64.matok" else len(slices) >= 4
     assert sum(sl.out.count(FFFD) for sl in slices) == exp.count(FFFD)
     # one as the last byte in front of a cut, and one in a wave's 64th token
     assert any(not sl.last and sl.cut == S and sl.text[S - 1] == 0xFF for sl in slices)
-    bad = set(b"\xff\xc3\xe2\x82")
+    bad = set(b"\xff\xc3\xd0\xe2\x82")
     assert any(k % 64 == 63 and bad & set(sl.text[int(a):int(z)])
                for sl in slices for k, (a, z) in enumerate(zip(sl.tok_bstart, sl.tok_bend)))
+    twin = code_twin(models, name)
+    if twin is not None:          # the same automaton and the same stream: any difference is the stream format's
+        with datok_amd.Stream(S) as st:
+            for mode, mine in ((3, slices), (1, ones)):
+                assert [sl.out for sl in assert_rendered(st, twin, om, raw, mode)] == [sl.out for sl in mine], mode
 
 
 # ---- 5. later work on a slice

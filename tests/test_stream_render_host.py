@@ -87,3 +87,29 @@ def test_set_render_checks_its_arguments():
         for bits in (4, 8, 7, 32, 1 << 31):
             assert L.dtk_stream_set_render(h, 1, bits) == _lib.E_ARG
         L.dtk_stream_free(h)
+
+
+def test_spliced_invalid_stream_is_what_its_tests_need():
+    """test_stream_render.invalid_stream_spliced, the input of every "de64.matok" case of the stream tests, on the oracle
+    of the enlarged model alone: in contract in the SIMPLE and in the position modes, with bytes that do not decode, the
+    new characters, and places where one touches the other."""
+    import bigsigma
+    from datok_amd import host
+    from streamrender import FFFD
+    from test_stream_render import invalid_stream, invalid_stream_spliced
+    raw = invalid_stream_spliced()
+    assert raw is invalid_stream_spliced() and raw != invalid_stream()
+    assert 5 * sc.S - 4 <= len(raw) <= 5 * sc.S and raw.count(FFFD) == 0
+    om = bigsigma.oracle_of(bigsigma.enlarged_de(64))
+    exp, status = om.transduce(raw, 3)
+    assert status == 0 and om.transduce(raw, 15)[1] == 0
+    assert exp.count(FFFD) >= 100
+    runes = host._decode_runes(raw)                       # (no literal U+FFFD in it: every 0xFFFD here is a byte that does not decode)
+    new = {ord(c) for c in bigsigma.CHARS}
+    n_new = sum(r in new for r in runes)
+    touching = sum(1 for i, r in enumerate(runes) if r in new and 0xFFFD in runes[max(i - 1, 0):i + 2])
+    print("%d bytes, %d new characters, %d U+FFFD in the SIMPLE output, %d new characters beside a bad byte"
+          % (len(raw), n_new, exp.count(FFFD), touching))
+    assert n_new >= 1000 and touching >= 50
+    assert any(raw[w * sc.S - 1] == 0xFF for w in range(1, 5))
+    assert raw.count(b"\xd0 ") >= 20                      # the new alphabet's lead byte without its continuation

@@ -19,7 +19,7 @@ from test_stream import models, whole  # noqa: F401  (fixtures: the device and o
 from test_stream_offsets import oracle_prefix, run_offsets, slice_parts
 from test_stream_offsets_host import FIVE, assert_joined
 from test_stream_positions_host import empty_text_streams
-from test_stream_render import invalid_stream
+from test_stream_render import INVALID_MODELS, code_twin, invalid_stream_of
 
 pytestmark = pytest.mark.gpu
 
@@ -195,15 +195,25 @@ def test_dense_sentences_blanks_and_the_empty_stream(models, name):
 
 
 # ---- 6. bytes that do not decode
-def test_invalid_utf8_counts_as_one_rune_a_byte(models):
+@pytest.mark.parametrize("name", INVALID_MODELS)
+def test_invalid_utf8_counts_as_one_rune_a_byte(models, name):
     import datok_amd
-    tok, om = models("tokenizer_de.matok")
-    raw = invalid_stream()
+    tok, om = models(name)
+    raw = invalid_stream_of(name)
     assert om.transduce_doc(raw, 0).status == 0
+    mine = {}
     with datok_amd.Stream(S) as st:
         for nl, offs in ((0, None), (NL, BLOCKED)):
-            slices = assert_sentences(st, tok, om, raw, nl, offs)
-        assert len(slices) == 5
+            slices = mine[offs] = assert_sentences(st, tok, om, raw, nl, offs)
+        assert len(slices) == 5 if name != "de64.matok" else len(slices) >= 4
+        assert all(sl.out is None for sl in slices)       # (no bytes are rendered here: the rows' rune spans read the stream)
+    twin = code_twin(models, name)
+    if twin is not None:          # the same automaton and the same stream: any difference is the stream format's
+        with datok_amd.Stream(S) as st:
+            for nl, offs in ((0, None), (NL, BLOCKED)):
+                for a, b in zip(assert_sentences(st, twin, om, raw, nl, offs), mine[offs]):
+                    assert all(np.array_equal(x, y) for x, y in zip(sen_parts(a), sen_parts(b)))
+                    assert (a.s_carry_in, a.s_carry_out) == (b.s_carry_in, b.s_carry_out)
 
 
 # ---- 7. later work on a slice

@@ -101,7 +101,9 @@ print("SYM16 OK")
 
 def test_stream_of_16_bit_entries_with_the_sigma_in_lds(tmp_path):
     """DATOK_SYM16=1 makes a shipped model's stream hold the 16-bit entries: the instantiation the crafted model takes,
-    but with the sigma's runes in LDS.  The switch is read once per process: a fresh child."""
+    but with the sigma's runes in LDS.  The environment is forwarded to the library once, when a process first loads it,
+    so a switch set here reaches a fresh child only.  (The hook behind the switch is read at every model load: set through
+    dtk_debug_configure around one load, it gives that model the same stream in this process -- bigsigma.device_model.)"""
     script = tmp_path / "sym16.py"
     script.write_text(_SYM16_SCRIPT)
     e = dict(os.environ); e["DATOK_SYM16"] = "1"

@@ -4,21 +4,21 @@ delivered ids equal the definition of tests/tokenids.py applied to the SAME run'
 tok_off and text, for all documents; and for unflagged documents the keys equal the oracle's surfaces.  The result is
 exact: every comparison is an equality."""
 import ctypes as C
-import os
 from contextlib import contextmanager
 
 import numpy as np
 import pytest
 
+import bigsigma
 import blocked
 import streamcorpus
 import tokenids
-from conftest import MODELS
 from test_event_list import _edge_documents, _pipeline_documents
 from tokenids import LAST_BYTE, PREFIXES
 
 NO_BYTE_OFFSETS = 512
 MODELS_DE = ("tokenizer_de.matok", "tokenizer_de.datok")
+MODELS_ENTRIES = ("tokenizer_de.matok:entries", "tokenizer_de.datok:entries")    # the same automata, the stream as 16-bit entries
 REPL = b"\xef\xbf\xbd"
 
 
@@ -29,9 +29,9 @@ def gpu():
     cache = {}
 
     def get(name):
+        """name: a fixture file, "<file>:entries" for its stream as 16-bit entries, or "de64.matok" (bigsigma.device_model)"""
         if name not in cache:
-            cache[name] = datok_amd.load_tokenizer_file(os.path.join(MODELS, name))
-            assert cache[name] is not None
+            cache[name] = bigsigma.device_model(name)[0]
         return cache[name]
     return get
 
@@ -254,7 +254,7 @@ def test_collisions_on_the_device(gpu, bits):
 
 # -------------------------------------------------------------------------------------------- 4: invalid UTF-8
 @pytest.mark.gpu
-@pytest.mark.parametrize("model", MODELS_DE)
+@pytest.mark.parametrize("model", MODELS_DE + MODELS_ENTRIES)
 def test_invalid_utf8(gpu, model):
     """A lone 0xFF, a truncated E2 82 and a literal U+FFFD inside tokens.  The vocabulary holds the keys (every invalid
     byte as EF BF BD) and the raw bytes of the same tokens: only the replaced forms match, the truncated sequence gives
@@ -290,6 +290,41 @@ def test_invalid_utf8(gpu, model):
         ids, n_unknown, r, text, off = _run(tok, valid, vocab, batch=b)
         keys, exp = _assert_ids(ids, n_unknown, r, text, off, words)
         assert (ids >= 0).sum() >= 4 and n_unknown >= 1
+
+
+@pytest.mark.gpu
+def test_invalid_utf8_beside_the_letters_of_an_enlarged_model(gpu):
+    """bigsigma.enlarged_de(64), whose stream holds 16-bit entries by itself: its new letters on both sides of an \\xff, in
+    front of \\xd0 (their lead byte, left alone) and between two \\xff, and a literal U+FFFD.  The vocabulary holds the
+    replaced and the raw form of every such token: only the replaced forms match."""
+    import datok_amd
+    from datok_amd import corpus
+    docs = bigsigma.invalid_documents()
+    om = bigsigma.oracle_of(bigsigma.enlarged_de(64))
+    tok = gpu("de64.matok")
+    text, off = corpus.concat_docs(docs)
+    raw_text = bytes(text)
+    l = [x.encode() for x in bigsigma.LETTERS[:5]]
+    with _B()(4096, 8) as b:
+        b.set_input(text, off)
+        b.run(tok, 0)
+        r = b.result()
+        keys = tokenids.keys_of_batch(text, off, r.tok_off, r.tok_bstart, r.tok_bend)
+        d_of = np.repeat(np.arange(len(docs)), np.diff(r.tok_off.astype(np.int64)))
+        raws = [raw_text[int(off[d]) + int(s):int(off[d]) + int(e)] for d, s, e in zip(d_of, r.tok_bstart, r.tok_bend)]
+        changed = [(k, w) for k, w in zip(keys, raws) if k != w]
+        for want in (l[0] + l[1] + REPL + l[2] + l[3], b"Preis" + l[0] + REPL, l[1] + REPL, REPL + l[2] + REPL, l[4] + 3 * REPL,
+                     b"z" + REPL + l[4]):
+            assert want in [k for k, _ in changed], want
+        words = [w for _, w in changed] + sorted(set(keys)) + [b"\xff", b"\xd0", l[1] + b"\xd0"]
+        vocab = datok_amd.Vocab(words)
+        ids, n_unknown, r, text, off = _run(tok, docs, vocab, batch=b)
+        surfaces = oracle_surfaces(om, "de64 invalid", docs)
+        keys2, exp = _assert_ids(ids, n_unknown, r, text, off, words, surfaces)
+        assert keys2 == keys and n_unknown == 0
+        assert (ids >= len(changed)).all()                         # no raw form matched
+        same = [int(ids[i]) for i, k in enumerate(keys) if k == l[0] + l[1] + REPL + l[2] + l[3]]
+        assert len(same) == 2 and same[0] == same[1]               # the invalid byte and the literal U+FFFD
 
 
 # --------------------------------------------------------------------------------------------------- 5: tally

@@ -3,17 +3,16 @@ kernels of dtk_wordpiece.hip and their plumbing through batch, pipeline and stre
 piece_bend and both counters equal the definition of tests/wordpiece.py applied to the SAME run's delivered tok_bstart /
 tok_bend / tok_off and text.  The result is exact: every comparison is an equality."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+import bigsigma
 import streamcorpus
 import tokenids
 import wordpiece
-from conftest import MODELS
 from test_event_list import _pipeline_documents
-from test_token_ids import DeviceInput, _from_device, _runtime
+from test_token_ids import MODELS_ENTRIES, DeviceInput, _from_device, _runtime
 from wordpiece import FAMILIES, REPL, family_ids
 
 NO_BYTE_OFFSETS = 512
@@ -27,9 +26,9 @@ def gpu():
     cache = {}
 
     def get(name):
+        """name: a fixture file, "<file>:entries" for its stream as 16-bit entries, or "de64.matok" (bigsigma.device_model)"""
         if name not in cache:
-            cache[name] = datok_amd.load_tokenizer_file(os.path.join(MODELS, name))
-            assert cache[name] is not None
+            cache[name] = bigsigma.device_model(name)[0]
         return cache[name]
     return get
 
@@ -160,7 +159,7 @@ def test_families_in_german_documents(gpu, model, pieces_home):
 
 # -------------------------------------------------------------------------------------------- 2: invalid UTF-8
 @pytest.mark.gpu
-@pytest.mark.parametrize("model", MODELS_DE)
+@pytest.mark.parametrize("model", MODELS_DE + MODELS_ENTRIES)
 def test_invalid_utf8_and_source_byte_spans(gpu, model):
     """A lone 0xFF, a truncated E2 82 and a literal U+FFFD inside tokens: a replaced byte is one source byte and three
     key bytes, and piece_bend counts source bytes.  The same batch then runs valid text."""
@@ -189,6 +188,41 @@ def test_invalid_utf8_and_source_byte_spans(gpu, model):
         p, r, text, off = _run(tok, valid, datok_amd.Vocab(words), batch=b)
         _assert_pieces(p, r, text, off, words)
         assert 14 in p.piece_id and 15 in p.piece_id and 0 < p.n_unknown < len(p.piece_off) - 1
+
+
+@pytest.mark.gpu
+def test_invalid_utf8_beside_the_letters_of_an_enlarged_model(gpu):
+    """bigsigma.enlarged_de(64), whose stream holds 16-bit entries by itself: pieces that end and begin at a replaced
+    byte beside the new two-byte letters.  A replaced byte is one source byte; the raw forms are in the vocabulary and
+    never match."""
+    import datok_amd
+    l = [x.encode() for x in bigsigma.LETTERS[:5]]
+    words = [b"[UNK]", l[0] + l[1], b"##" + REPL, b"##" + l[2] + l[3], REPL, b"Preis", b"##" + l[0] + REPL, l[1] + REPL,
+             b"##" + l[2], b"x", b"z", b"##" + REPL + l[4], l[4], b"##" + REPL + REPL, b"ef", b"hier",
+             b"##\xff", b"##" + l[0] + b"\xd0", l[1] + b"\xd0", b"\xff", b"##\xf0\x9f\x98"]
+    n_replaced_forms = 16
+    docs = bigsigma.invalid_documents()
+    with _B()(4096, 8) as b:
+        p, r, text, off = _run(gpu("de64.matok"), docs, datok_amd.Vocab(words), batch=b)
+        _assert_pieces(p, r, text, off, words)
+        keys = tokenids.keys_of_batch(text, off, r.tok_off, r.tok_bstart, r.tok_bend)
+
+        def pieces(key, start=0):
+            i = keys.index(key, start)
+            a, z = int(p.piece_off[i]), int(p.piece_off[i + 1])
+            return i, p.piece_id[a:z].tolist(), p.piece_bend[a:z].tolist()
+        whole = l[0] + l[1] + REPL + l[2] + l[3]
+        i, ids, bend = pieces(whole)                                  # document 0: two letters, FF, two letters: source bytes 0..9
+        assert (int(r.tok_bstart[i]), int(r.tok_bend[i])) == (0, 9) and (ids, bend) == ([1, 2, 3], [4, 5, 9])
+        j, ids, bend = pieces(whole, i + 1)                           # document 3: the literal U+FFFD, three source bytes
+        assert (ids, bend) == ([1, 2, 3], [4, 7, 11])
+        assert pieces(b"Preis" + l[0] + REPL)[1:] == ([5, 6], [5, 8])  # a piece that ends in the lone lead byte
+        assert pieces(l[1] + REPL)[1] == [7]
+        assert pieces(REPL + l[2] + REPL)[1:] == ([4, 8, 2], [1, 3, 4])   # one letter between two replaced bytes
+        k, ids, bend = pieces(b"z" + REPL + l[4])
+        assert ids == [10, 11] and bend[1] - bend[0] == 3
+        assert pieces(l[4] + 3 * REPL)[1] == [12, 13, 2]
+        assert (p.piece_id < n_replaced_forms).all()                  # no raw form matched
 
 
 # ------------------------------------------------------------------------------- 3: block and scan-tile edges

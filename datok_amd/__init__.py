@@ -25,6 +25,8 @@ HIP kernels behind the C-ABI of libdatok_gpu.so (include/datok_gpu.h):
                                            vocabulary on the device, type ids and a frequency list (addition)
     --                                   Batch.set_wordpiece / pieces, wordpiece_probe: every token split into WordPiece
                                            ids over a Vocab on the device, what a BERT-style model takes (addition)
+    --                                   Fold, Batch.set_fold, fold_apply, bert_uncased_mapping: token keys folded rune by
+                                           rune where they are read, for uncased vocabularies (addition)
     --                                   Batch.set_encode / encoded, encode_rows: sentences or documents as fixed-length
                                            model input rows (input_ids, row_len, word_id) on the device (addition)
     --                                   Pipeline: a corpus larger than a batch, uploads overlapped (addition)
@@ -38,4 +40,4 @@ from .host import (NEWLINE_AFTER_EOT, NO_BYTE_OFFSETS, NO_RUNE_OFFSETS, OFFSETS_
                    BatchResult, MultiPipeline, PinnedBuffer, Pipeline, TokenWriter, Tokenizer, foma_to_datok, foma_to_matok, load_foma_file,
                    load_tokenizer_file, model_info, new_token_writer, replay, replay_list, unpack_blocked,
                    SentenceTable, SliceView, Stream, replay_slice, slice_calls, Tally, Vocab, Pieces, wordpiece_probe,
-                   Encoded, encode_rows)
+                   Encoded, encode_rows, Fold, fold_apply, bert_uncased_mapping)

@@ -47,6 +47,8 @@ EXPORTS = [
     "dtk_pipeline_set_wordpiece", "dtk_stream_set_wordpiece", "dtk_stream_pieces",
     "dtk_encode_rows_mem", "dtk_batch_set_encode", "dtk_batch_encoded_device", "dtk_batch_encoded_host",
     "dtk_pipeline_set_encode",
+    "dtk_fold_create", "dtk_fold_free", "dtk_fold_apply_mem", "dtk_wordpiece_probe_fold_mem",
+    "dtk_batch_set_fold", "dtk_pipeline_set_fold", "dtk_stream_set_fold",
 ]
 ID_UNKNOWN = -1   # DTK_ID_UNKNOWN
 
@@ -311,6 +313,14 @@ def lib():
     L.dtk_batch_pieces_device.argtypes = [vp, C.POINTER(PieceView)]
     L.dtk_batch_pieces_host.argtypes = [vp, C.POINTER(PieceView)]
     L.dtk_stream_pieces.argtypes = [vp, C.POINTER(PieceView)]
+    L.dtk_fold_create.argtypes = [vp, vp, vp, u32, C.POINTER(vp)]
+    L.dtk_fold_free.argtypes = [vp]
+    L.dtk_fold_free.restype = None
+    L.dtk_fold_apply_mem.argtypes = [vp, vp, vp, u32, vp, sz, vp, sz, C.POINTER(sz)]
+    L.dtk_wordpiece_probe_fold_mem.argtypes = [vp, vp, u32, vp, u32, C.c_int32, u32, vp, vp, vp, u32, vp, sz, vp, vp, u32,
+                                               C.POINTER(u32)]
+    for f in (L.dtk_batch_set_fold, L.dtk_pipeline_set_fold, L.dtk_stream_set_fold):
+        f.argtypes = [vp, vp]
     u64 = C.c_uint64
     L.dtk_encode_rows_mem.argtypes = [C.POINTER(EncodeSpec), vp, u64, vp, vp, u64, vp, u32, u64, vp, vp, vp, vp, vp,
                                       C.POINTER(u64), C.POINTER(u64)]

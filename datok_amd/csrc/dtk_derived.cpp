@@ -1,6 +1,6 @@
 // dtk_derived.cpp -- the tables a finished run's download derives from its result arrays, on the download stream behind
 // finish(): the sentence table, the tokens' ids, their WordPiece pieces and the model input rows.  Each is a DerivedBlock
-// (dtk_mirror.h; the protocol: DESIGN.md section 2.12) with an *_enqueue, which never waits, and a *_finish, which does.
+// (dtk_mirror.h; the protocol: DESIGN.md section 2.13) with an *_enqueue, which never waits, and a *_finish, which does.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -146,6 +146,7 @@ int ids_enqueue(dtk_batch *b, bool home) {
     a.tok_off = b->d_tok_off; a.tok_bstart = b->d_bstart; a.tok_bend = b->d_bend; a.n_tok = nt;
     if (b->n_invalid) { const DtkSym s = sym_of(b); a.sym_base = s.base; a.sym_lut = s.lut; }
     a.vocab = b->vocab->dev;
+    if (b->fold) a.fold = b->fold->dev;
     a.tok_id = L.dev(L.id);
     a.n_unknown = reinterpret_cast<unsigned long long *>(L.dev(L.cnt));
     a.tally = b->tally ? b->tally->d_counts.p : nullptr;
@@ -201,6 +202,7 @@ int wp_enqueue(dtk_batch *b, bool home) {
     if (b->n_invalid) { const DtkSym s = sym_of(b); a.sym_base = s.base; a.sym_lut = s.lut; }
     a.vocab = b->wp_vocab->dev;
     a.rule = b->wp_rule;
+    if (b->fold) a.fold = b->fold->dev;
     a.tile_base = b->d_wp_ws.p;
     a.first = reinterpret_cast<DtkWpFirst *>(b->d_wp_ws.p + tiles + 1);
     a.cnt = reinterpret_cast<unsigned long long *>(L.dev(L.cnt));
@@ -458,6 +460,18 @@ extern "C" int dtk_batch_set_wordpiece(dtk_batch *b, const dtk_vocab *v, const u
   // (the finished run, if any, is split anew under the new rule when its pieces are asked for)
   b->pieces.built = false;
   b->wp_vocab = v; b->wp_rule = rule; b->wp_home = v && pieces_home != 0;
+  return DTK_OK;
+}
+
+extern "C" int dtk_batch_set_fold(dtk_batch *b, const dtk_fold *f) {
+  if (!b || (f && f->device != b->device)) return DTK_E_ARG;
+  int rc;
+  // (a lookup or a split under way reads the fold that was attached)
+  if ((rc = b->ids.wait()) != DTK_OK || (rc = b->pieces.wait()) != DTK_OK) return rc;
+  // (the finished run, if any, is looked up and split anew under the new fold when its ids or pieces are asked for; the
+  //  rows follow their pieces)
+  if (f != b->fold) b->ids.built = b->pieces.built = false;
+  b->fold = f;
   return DTK_OK;
 }
 

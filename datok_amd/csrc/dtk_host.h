@@ -109,6 +109,25 @@ struct dtk_tally {
   DevArray<unsigned long long> d_counts;  // n_words + 1, the last: unknown
 };
 
+// ------------------------------------------------------ fold (dtk_fold.cpp)
+//
+// The tables of dtk_fold_core.h in one array of 32-bit words: the entry blocks, the multi array, the page table.
+struct FoldImage {
+  std::vector<uint32_t> words;
+  size_t multi_at = 0, page_at = 0;  // where the two begin, in words
+  DtkFoldDev view(const uint32_t *base) const {
+    return DtkFoldDev{base, reinterpret_cast<const uint16_t *>(base + page_at), base + multi_at};
+  }
+};
+// a fold's arguments checked (DTK_E_ARG) and made into the tables
+int fold_image(const uint32_t *from, const uint32_t *to_off, const uint32_t *to, uint32_t n, FoldImage &img);
+// The tables on one device, immutable after creation.
+struct dtk_fold {
+  int device = 0;
+  DevArray<uint32_t> d_words;
+  DtkFoldDev dev{};
+};
+
 // ------------------------------------------------------ a stream slice's device outputs
 //
 // What the next download of a batch that is a slot of a stream (dtk_streamer.cpp) computes beside the result arrays, on
@@ -290,7 +309,7 @@ struct dtk_batch {
   uint64_t evl_need = 0;           // nonzero: this run's list has that many rows, more than the bound (dtk_batch_result_host saw it)
   bool evl_pending = false;        // a list is on its way whose count nobody has looked at yet
   // The derived tables (dtk_derived.cpp): four blocks of dtk_mirror.h, each computed on the download stream behind
-  // finish() and kept by the one protocol of DerivedBlock (DESIGN.md section 2.12).
+  // finish() and kept by the one protocol of DerivedBlock (DESIGN.md section 2.13).
   // DTK_R_SENTENCES / dtk_batch_sentences_*: the sentence table (dtk_sentences.hip) -- one copy brings all of it.  Sized
   // for n_sent rows; the count word says whether that was enough (need), as with the event list.
   struct Sen : DerivedBlock {
@@ -318,6 +337,8 @@ struct dtk_batch {
   // a block that holds them (wp_finish).  need is the most pieces a run of this batch had beyond what its first block
   // held, and is kept for the next runs.
   const dtk_vocab *wp_vocab = nullptr;
+  // dtk_batch_set_fold: the fold both of them read their keys through, or null
+  const dtk_fold *fold = nullptr;
   DtkWpRule wp_rule{};
   bool wp_home = false;
   struct Pieces : DerivedBlock {

@@ -99,4 +99,17 @@ struct ReplacedKey {
   }
 };
 
+// Either of them under a fold (dtk_batch_set_fold): the rule's own DtkFoldedKey, read through Inner::at -- for RawKey
+// the aligned words, so nothing behind the word of the key's last byte is read whatever that byte folds to.  `ascii` is
+// the block's LDS copy of the fold's ASCII page (stage_fold_ascii).
+template <class Inner>
+using FoldedKey = DtkFoldedKey<Inner>;
+
+// The fold's ASCII page into the block's LDS, once per block: the entry of an ASCII byte -- nearly every byte of running
+// text -- then costs an LDS read and no dependent global load.  Every thread of the block calls it.
+__device__ __forceinline__ void stage_fold_ascii(const DtkFoldDev &F, uint32_t *ascii) {
+  for (uint32_t j = threadIdx.x; j < DTK_FOLD_PAGE; j += blockDim.x) ascii[j] = F.entry[j];
+  __syncthreads();
+}
+
 }  // namespace

@@ -56,7 +56,7 @@ struct MirrorLayout {
   }
 };
 
-// The state of a derived table (DESIGN.md section 2.12), the part without a HIP call: a table that is computed once per
+// The state of a derived table (DESIGN.md section 2.13), the part without a HIP call: a table that is computed once per
 // run into a block sized by a bound, with a count word that says whether the bound held.
 struct DerivedState {
   bool built = false;  // the kernels have been enqueued for this run, into the block as it is described

@@ -114,6 +114,15 @@ extern "C" int dtk_pipeline_set_wordpiece(dtk_pipeline *p, const dtk_vocab *v, c
   return DTK_OK;
 }
 
+extern "C" int dtk_pipeline_set_fold(dtk_pipeline *p, const dtk_fold *f) {
+  if (!p) return DTK_E_ARG;
+  for (dtk_batch *b : p->slots) {
+    const int rc = dtk_batch_set_fold(b, f);
+    if (rc != DTK_OK) return rc;
+  }
+  return DTK_OK;
+}
+
 extern "C" int dtk_pipeline_set_encode(dtk_pipeline *p, const dtk_encode_spec *spec, int rows_home) {
   if (!p) return DTK_E_ARG;
   for (dtk_batch *b : p->slots) {

@@ -202,6 +202,15 @@ extern "C" int dtk_stream_set_wordpiece(dtk_stream *s, const dtk_vocab *v, const
   return DTK_OK;
 }
 
+extern "C" int dtk_stream_set_fold(dtk_stream *s, const dtk_fold *f) {
+  if (!s) return DTK_E_ARG;
+  for (dtk_batch *b : s->slots) {
+    const int rc = dtk_batch_set_fold(b, f);
+    if (rc != DTK_OK) return rc;
+  }
+  return DTK_OK;
+}
+
 extern "C" int dtk_stream_pieces(dtk_stream *s, dtk_piece_view *o) {
   if (!s || !o) return DTK_E_ARG;
   if (!s->cur.pieces_set) return DTK_E_STATE;

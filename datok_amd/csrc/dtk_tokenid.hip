@@ -8,7 +8,8 @@
 // A run without invalid UTF-8 never touches the symbol stream: its keys are the text's bytes, read as aligned 32-bit
 // words (the last word read is the one that holds the key's last byte).  With invalid bytes in the run the key is
 // produced a byte at a time under the renderers' rule (sym_invalid_byte).  Both key types live in dtk_key.h, which the
-// WordPiece kernels (dtk_wordpiece.hip) share.
+// WordPiece kernels (dtk_wordpiece.hip) share.  With a fold attached (dtk_batch_set_fold) the key is F(K): either key type
+// read through FoldedKey, rune by rune, with the fold's ASCII page in LDS.
 //
 // Counts: the unknowns of a wave go to the batch's counter with one atomic per wave.  With a tally attached every
 // token adds 1 to its id's 64-bit counter.  Natural text is Zipfian and vocabularies come sorted by frequency, so the
@@ -40,8 +41,13 @@ __device__ __forceinline__ int32_t lookup(const DtkVocabDev &V, const Key &key) 
       nullptr);
 }
 
+// FOLD: the launch has a fold attached (dtk_batch_set_fold) and every key is read through it; chosen per launch, so
+// the kernel of a run without a fold is the one it was.
+template <bool FOLD>
 __global__ __launch_bounds__(DTK_TOKID_THREADS) void k_token_ids(const DtkTokenIdArgs a) {
   __shared__ uint32_t hot[DTK_TALLY_HOT];
+  __shared__ uint32_t fold_ascii[FOLD ? DTK_FOLD_PAGE : 1u];
+  if constexpr (FOLD) stage_fold_ascii(a.fold, fold_ascii);
   const bool tally = a.tally != nullptr;
   if (tally) {
     for (uint32_t j = threadIdx.x; j < DTK_TALLY_HOT; j += DTK_TOKID_THREADS) hot[j] = 0u;
@@ -71,7 +77,12 @@ __global__ __launch_bounds__(DTK_TOKID_THREADS) void k_token_ids(const DtkTokenI
         if (bs > be) bs = be;
         const uint8_t *p = a.text + d0 + bs;
         const uint32_t n = (uint32_t)(be - bs);
-        id = a.sym_base ? lookup(a.vocab, ReplacedKey{p, n, S, d0 + bs}) : lookup(a.vocab, RawKey{p, n});
+        if constexpr (FOLD) {
+          id = a.sym_base ? lookup(a.vocab, FoldedKey<ReplacedKey>{ReplacedKey{p, n, S, d0 + bs}, a.fold, fold_ascii})
+                          : lookup(a.vocab, FoldedKey<RawKey>{RawKey{p, n}, a.fold, fold_ascii});
+        } else {
+          id = a.sym_base ? lookup(a.vocab, ReplacedKey{p, n, S, d0 + bs}) : lookup(a.vocab, RawKey{p, n});
+        }
       }
       a.tok_id[i] = id;
     }
@@ -99,6 +110,7 @@ extern "C" int dtk_launch_token_ids(const DtkTokenIdArgs *a, void *stream) {
   if (a->n_tok == 0) return 0;
   const uint64_t tiles = (a->n_tok + DTK_TOKID_THREADS - 1u) / DTK_TOKID_THREADS;
   const uint32_t blocks = (uint32_t)(tiles < DTK_TOKID_MAX_BLOCKS ? tiles : DTK_TOKID_MAX_BLOCKS);
-  hipLaunchKernelGGL(k_token_ids, dim3(blocks), dim3(DTK_TOKID_THREADS), 0, (hipStream_t)stream, *a);
+  if (a->fold.entry) hipLaunchKernelGGL(k_token_ids<true>, dim3(blocks), dim3(DTK_TOKID_THREADS), 0, (hipStream_t)stream, *a);
+  else hipLaunchKernelGGL(k_token_ids<false>, dim3(blocks), dim3(DTK_TOKID_THREADS), 0, (hipStream_t)stream, *a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

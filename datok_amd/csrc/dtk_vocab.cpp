@@ -91,6 +91,45 @@ extern "C" int dtk_wordpiece_probe_mem(const uint8_t *bytes, const uint64_t *off
   return n > cap ? DTK_E_CAPACITY : DTK_OK;
 }
 
+// K is valid UTF-8 (what the replacement leaves)
+static bool valid_key(const uint8_t *key, uint32_t n) {
+  for (uint32_t i = 0; i < n;) {
+    const uint32_t c = key[i];
+    if (c < 0x80u) { i++; continue; }
+    if (c < 0xC0u) return false;
+    const uint32_t cp = dtk_utf8_lead([&](uint32_t j) { return (uint32_t)key[j]; }, i, n, c);
+    if (cp == 0xFFFDu && !(n - i >= 3u && c == 0xEFu && key[i + 1] == 0xBFu && key[i + 2] == 0xBDu)) return false;  // (U+FFFD itself is fine)
+    i += cp < 0x800u ? 2u : cp < 0x10000u ? 3u : 4u;
+  }
+  return true;
+}
+
+extern "C" int dtk_wordpiece_probe_fold_mem(const uint8_t *bytes, const uint64_t *off, uint32_t n_words, const uint8_t *prefix,
+                                            uint32_t prefix_len, int32_t unk_id, uint32_t max_runes, const uint32_t *from,
+                                            const uint32_t *to_off, const uint32_t *to, uint32_t n_fold, const uint8_t *key,
+                                            size_t key_len, int32_t *ids, uint32_t *ends, uint32_t cap, uint32_t *n_out) {
+  if (!n_out || (key_len && !key) || key_len >= (1ull << 32) || (cap && (!ids || !ends))) return DTK_E_ARG;
+  VocabImage img;
+  FoldImage fold;
+  DtkWpRule rule;
+  int rc = build_image(bytes, off, n_words, img);
+  if (rc != DTK_OK || (rc = wordpiece_rule(n_words, prefix, prefix_len, unk_id, max_runes, &rule)) != DTK_OK ||
+      (rc = fold_image(from, to_off, to, n_fold, fold)) != DTK_OK)
+    return rc;
+  if (!valid_key(key, (uint32_t)key_len)) return DTK_E_ARG;
+  const DtkFoldDev F = fold.view(fold.words.data());
+  const DtkFoldedKey<DtkWpBytesKey> folded{DtkWpBytesKey{key, (uint32_t)key_len}, F, F.entry};
+  uint32_t n = dtk_wp_split(img.view, rule, folded, [&](uint32_t k, int32_t id, uint32_t end) {
+    if (k < cap) { ids[k] = id; ends[k] = end; }
+  });
+  if (n == DTK_WP_BAD) {
+    n = 1;
+    if (cap) { ids[0] = unk_id; ends[0] = (uint32_t)key_len; }
+  }
+  *n_out = n;
+  return n > cap ? DTK_E_CAPACITY : DTK_OK;
+}
+
 extern "C" int dtk_vocab_probe_mem(const uint8_t *bytes, const uint64_t *off, uint32_t n_words, const uint8_t *key,
                                    size_t key_len, int32_t *id) {
   if (!id || (key_len && !key)) return DTK_E_ARG;

@@ -9,11 +9,7 @@
 #pragma once
 #include <stdint.h>
 
-#ifdef __HIP__
-#define DTK_VH __host__ __device__ __forceinline__
-#else
-#define DTK_VH inline
-#endif
+#include "dtk_fold_core.h"  // (DTK_VH, and the fold of the lookup's arguments)
 
 struct DtkVocabDev {
   const uint64_t *slots;  // mask + 1
@@ -74,6 +70,7 @@ struct DtkTokenIdArgs {
   const void *sym_base;          // the run's symbol stream (DtkSym), non-null only if the run saw invalid UTF-8
   const uint16_t *sym_lut;
   struct DtkVocabDev vocab;
+  struct DtkFoldDev fold;        // entry == null: no fold
   int32_t *tok_id;               // n_tok
   unsigned long long *n_unknown; // device word, cleared in front of the launch
   unsigned long long *tally;     // n_words + 1 counters (the last: unknown), or null

@@ -1,6 +1,7 @@
 // dtk_wordpiece.hip -- every token of a finished run split into WordPiece ids (dtk_batch_set_wordpiece, include/datok_gpu.h):
 // greedy longest-match-first over the token's key, continuation pieces looked up behind the prefix.  The rule itself is
 // dtk_wp_split of dtk_wordpiece_core.h, the code the host probe runs; the keys are those of dtk_tokenid.hip (dtk_key.h).
+// With a fold attached (dtk_batch_set_fold) the keys are read through FoldedKey; piece ends stay in source bytes.
 // Runs on the download stream behind finish(), so the token count is final and repairs and the exact pass are done.
 //
 // Three launches, blocks of 256 threads over tiles of 256 tokens, one lane per token:
@@ -49,16 +50,27 @@ __device__ __forceinline__ WpRow wp_row(const DtkWordPieceArgs &a, uint64_t i) {
   return WpRow{d0, (uint32_t)bs, (uint32_t)be, key};
 }
 
-template <class Emit>
-__device__ __forceinline__ uint32_t wp_split(const DtkWordPieceArgs &a, const WpRow &r, Emit emit) {
+// FOLD: the launch has a fold attached (dtk_batch_set_fold) and every key is read through it, with the fold's ASCII
+// page in the block's LDS (ascii); chosen per launch, so the kernels of a run without a fold are the ones they were.
+template <bool FOLD, class Emit>
+__device__ __forceinline__ uint32_t wp_split(const DtkWordPieceArgs &a, const WpRow &r, const uint32_t *ascii, Emit emit) {
   const uint8_t *p = a.text + r.d0 + r.bs;
   const uint32_t n = r.be - r.bs;
+  if constexpr (FOLD) {
+    if (a.sym_base)
+      return dtk_wp_split(a.vocab, a.rule,
+                          FoldedKey<ReplacedKey>{ReplacedKey{p, n, DtkSym{a.sym_base, a.sym_lut}, r.d0 + r.bs}, a.fold, ascii}, emit);
+    return dtk_wp_split(a.vocab, a.rule, FoldedKey<RawKey>{RawKey{p, n}, a.fold, ascii}, emit);
+  }
   if (a.sym_base) return dtk_wp_split(a.vocab, a.rule, ReplacedKey{p, n, DtkSym{a.sym_base, a.sym_lut}, r.d0 + r.bs}, emit);
   return dtk_wp_split(a.vocab, a.rule, RawKey{p, n}, emit);
 }
 
+template <bool FOLD>
 __global__ __launch_bounds__(DTK_WP_TILE) void k_wp_count(const DtkWordPieceArgs a) {
   __shared__ uint64_t wave_tot[DTK_WP_TILE / WAVE];
+  __shared__ uint32_t fold_ascii[FOLD ? DTK_FOLD_PAGE : 1u];
+  if constexpr (FOLD) stage_fold_ascii(a.fold, fold_ascii);
   const uint64_t tiles = dtk_wp_tiles(a.n_tok);
   for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {  // (block-uniform: the scan and the ballot take every lane)
     const uint64_t i = t * DTK_WP_TILE + threadIdx.x;
@@ -70,7 +82,7 @@ __global__ __launch_bounds__(DTK_WP_TILE) void k_wp_count(const DtkWordPieceArgs
       int32_t id0 = 0;
       uint32_t end0 = 0;
       c = DTK_WP_BAD;
-      if (r.key) c = wp_split(a, r, [&](uint32_t k, int32_t id, uint32_t end) { if (k == 0u) { id0 = id; end0 = end; } });
+      if (r.key) c = wp_split<FOLD>(a, r, fold_ascii, [&](uint32_t k, int32_t id, uint32_t end) { if (k == 0u) { id0 = id; end0 = end; } });
       unknown = c == DTK_WP_BAD;
       if (unknown) c = 1u;
       // (what a token of one piece delivers: the word and where it ends, or unk_id and the clamped tok_bend)
@@ -96,7 +108,10 @@ __global__ __launch_bounds__(256) void k_wp_scan(const DtkWordPieceArgs a) {
   }
 }
 
+template <bool FOLD>
 __global__ __launch_bounds__(DTK_WP_TILE) void k_wp_write(const DtkWordPieceArgs a) {
+  __shared__ uint32_t fold_ascii[FOLD ? DTK_FOLD_PAGE : 1u];
+  if constexpr (FOLD) stage_fold_ascii(a.fold, fold_ascii);
   const uint64_t tiles = dtk_wp_tiles(a.n_tok);
   const bool fits = a.tile_base[tiles] <= a.cap;
   for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
@@ -123,7 +138,7 @@ __global__ __launch_bounds__(DTK_WP_TILE) void k_wp_write(const DtkWordPieceArgs
     }
     // (two pieces and more: the split is good and has a key)
     const WpRow r = wp_row(a, i);
-    wp_split(a, r, [&](uint32_t k, int32_t id, uint32_t end) {
+    wp_split<FOLD>(a, r, fold_ascii, [&](uint32_t k, int32_t id, uint32_t end) {
       if (k < c) {  // (always: the first pass counted the same rule on the same bytes)
         a.piece_id[o + k] = id;
         a.piece_bend[o + k] = r.bs + end;
@@ -137,8 +152,11 @@ extern "C" int dtk_launch_wordpiece(const DtkWordPieceArgs *a, void *stream) {
   const uint64_t tiles = dtk_wp_tiles(a->n_tok);
   const uint32_t blocks = (uint32_t)(tiles < DTK_WP_MAX_BLOCKS ? tiles : DTK_WP_MAX_BLOCKS);
   hipStream_t s = (hipStream_t)stream;
-  if (blocks) hipLaunchKernelGGL(k_wp_count, dim3(blocks), dim3(DTK_WP_TILE), 0, s, *a);
+  const bool fold = a->fold.entry != nullptr;
+  if (blocks && fold) hipLaunchKernelGGL(k_wp_count<true>, dim3(blocks), dim3(DTK_WP_TILE), 0, s, *a);
+  else if (blocks) hipLaunchKernelGGL(k_wp_count<false>, dim3(blocks), dim3(DTK_WP_TILE), 0, s, *a);
   hipLaunchKernelGGL(k_wp_scan, dim3(1), dim3(256), 0, s, *a);
-  if (blocks) hipLaunchKernelGGL(k_wp_write, dim3(blocks), dim3(DTK_WP_TILE), 0, s, *a);
+  if (blocks && fold) hipLaunchKernelGGL(k_wp_write<true>, dim3(blocks), dim3(DTK_WP_TILE), 0, s, *a);
+  else if (blocks) hipLaunchKernelGGL(k_wp_write<false>, dim3(blocks), dim3(DTK_WP_TILE), 0, s, *a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

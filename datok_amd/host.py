@@ -622,10 +622,84 @@ def _pieces_of(v, copy=True) -> Pieces:
                   arr(v.piece_bend, n_pieces, np.uint32), n_pieces, int(v.n_unknown))
 
 
-def wordpiece_probe(words, key: bytes, prefix=b"##", unk_id=0, max_runes=0, cap=None):
+def _pack_fold(mapping):
+    """A dict from code point to str (or to a sequence of code points) as dtk_fold_create takes it: (from, to_off, to, n)."""
+    items = [(int(cp), [ord(c) for c in t] if isinstance(t, str) else [int(c) for c in t]) for cp, t in mapping.items()]
+    frm = np.array([cp for cp, _ in items] or [0], np.uint32)
+    to_off = np.zeros(len(items) + 1, np.uint32)
+    if items:
+        to_off[1:] = np.cumsum([len(t) for _, t in items], dtype=np.uint64)
+    to = np.array([c for _, t in items for c in t] or [0], np.uint32)
+    return frm, to_off, to, len(items)
+
+
+class Fold:
+    """dtk_fold: a finite map from a code point to 0..4 code points on the device, applied rune by rune to every token's
+    key where the lookup (set_vocab) and the split (set_wordpiece) read it; offsets and piece ends stay in source bytes.
+    `mapping`: a dict from code point to str; code points it does not list fold to themselves.  Immutable and shareable
+    between batches.  The vocabulary is not folded: it must be in folded form already."""
+
+    def __init__(self, mapping):
+        frm, to_off, to, n = _pack_fold(mapping)
+        self._h = C.c_void_p()
+        check(lib().dtk_fold_create(frm.ctypes.data, to_off.ctypes.data, to.ctypes.data, n, C.byref(self._h)), "dtk_fold_create")
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            lib().dtk_fold_free(h)
+
+    __del__ = close
+
+
+def _set_fold(fn, name, owner, fold):
+    check(fn(owner._h, fold._h if fold is not None else None), name)
+    owner._fold = fold   # (it must outlive the owner's use of it)
+
+
+def fold_apply(mapping, key: bytes) -> bytes:
+    """dtk_fold_apply_mem: the folded key F(K) of `key` under `mapping` (a dict from code point to str), computed on the
+    host with the tables the kernels use; bytes of `key` that do not decode fold as U+FFFD.  Needs no device."""
+    frm, to_off, to, n = _pack_fold(mapping)
+    key = bytes(key)
+    kb = np.frombuffer(key, dtype=np.uint8) if key else np.zeros(1, np.uint8)
+    out = np.zeros(max(16 * len(key), 1), np.uint8)
+    n_out = C.c_size_t(0)
+    check(lib().dtk_fold_apply_mem(frm.ctypes.data, to_off.ctypes.data, to.ctypes.data, n, kb.ctypes.data, len(key),
+                                   out.ctypes.data, len(out), C.byref(n_out)), "dtk_fold_apply_mem")
+    return out[:int(n_out.value)].tobytes()
+
+
+_BERT_UNCASED = None
+
+
+def bert_uncased_mapping():
+    """The fold of BERT's uncased BasicTokenizer as a mapping for Fold, from the standard library's Unicode tables: for
+    every scalar value c, F(c) is NFD(c.lower()) without the characters of category Mn; only c with F(c) != c are
+    listed.  Per rune, like the `tokenizers` package: a final sigma, which str.lower() on a whole token treats by its
+    context, folds like any other.  Built once and cached; the caller must not change it."""
+    global _BERT_UNCASED
+    if _BERT_UNCASED is None:
+        import unicodedata
+        m = {}
+        for cp in range(0x110000):
+            if 0xD800 <= cp <= 0xDFFF:
+                continue
+            c = chr(cp)
+            f = "".join(x for x in unicodedata.normalize("NFD", c.lower()) if unicodedata.category(x) != "Mn")
+            if f != c:
+                m[cp] = f
+        _BERT_UNCASED = m
+    return _BERT_UNCASED
+
+
+def wordpiece_probe(words, key: bytes, prefix=b"##", unk_id=0, max_runes=0, cap=None, fold=None):
     """dtk_wordpiece_probe_mem: `key` (its bytes after replacement) split over `words` on the host with the table and the
     rule the kernels use: (ids, ends), ends in key bytes.  Needs no device.  cap: room for that many pieces (default:
-    enough); with more the call raises DatokGpuError E_CAPACITY whose .needed is the count."""
+    enough); with more the call raises DatokGpuError E_CAPACITY whose .needed is the count.  fold: a mapping as Fold
+    takes it (dtk_wordpiece_probe_fold_mem): the key, valid UTF-8, is read through it; ends stay in bytes of `key`."""
+    if fold is not None:
+        return _wordpiece_probe_fold(words, key, prefix, unk_id, max_runes, cap, fold)
     blob, off, n = _pack_words(words)
     key, prefix = bytes(key), bytes(prefix)
     kb = np.frombuffer(key, dtype=np.uint8) if key else np.zeros(1, np.uint8)
@@ -638,6 +712,26 @@ def wordpiece_probe(words, key: bytes, prefix=b"##", unk_id=0, max_runes=0, cap=
                                        C.byref(n_out))
     if rc != _lib.OK:
         e = _lib.DatokGpuError(rc, "dtk_wordpiece_probe_mem")
+        e.needed = int(n_out.value) if rc == _lib.E_CAPACITY else None
+        raise e
+    k = int(n_out.value)
+    return ids[:k].copy(), ends[:k].copy()
+
+
+def _wordpiece_probe_fold(words, key, prefix, unk_id, max_runes, cap, fold):
+    blob, off, n = _pack_words(words)
+    frm, to_off, to, n_fold = _pack_fold(fold)
+    key, prefix = bytes(key), bytes(prefix)
+    kb = np.frombuffer(key, dtype=np.uint8) if key else np.zeros(1, np.uint8)
+    pb = np.frombuffer(prefix, dtype=np.uint8) if prefix else np.zeros(1, np.uint8)
+    room = len(key) + 1 if cap is None else int(cap)
+    ids, ends = np.zeros(max(room, 1), np.int32), np.zeros(max(room, 1), np.uint32)
+    n_out = C.c_uint32(0)
+    rc = lib().dtk_wordpiece_probe_fold_mem(blob.ctypes.data, off.ctypes.data, n, pb.ctypes.data, len(prefix), int(unk_id),
+                                            int(max_runes), frm.ctypes.data, to_off.ctypes.data, to.ctypes.data, n_fold,
+                                            kb.ctypes.data, len(key), ids.ctypes.data, ends.ctypes.data, room, C.byref(n_out))
+    if rc != _lib.OK:
+        e = _lib.DatokGpuError(rc, "dtk_wordpiece_probe_fold_mem")
         e.needed = int(n_out.value) if rc == _lib.E_CAPACITY else None
         raise e
     k = int(n_out.value)
@@ -899,6 +993,12 @@ class Batch:
         a = np.frombuffer((C.c_char * (n * 4)).from_address(v.tok_id), dtype=np.int32)
         return (a.copy() if copy else a), int(v.n_unknown)
 
+    def set_fold(self, fold):
+        """dtk_batch_set_fold: the ids (set_vocab) and the split (set_wordpiece) read every key through `fold`
+        (a Fold; None: off, the default).  A finished run's ids, pieces and rows are computed anew under it when they
+        are next asked for."""
+        _set_fold(lib().dtk_batch_set_fold, "dtk_batch_set_fold", self, fold)
+
     def set_wordpiece(self, v, prefix=b"##", unk_id=0, max_runes=0, pieces_home=True):
         """Every token of the next runs is split into WordPiece ids over the Vocab `v` (None: off) behind the run, on the
         download stream: greedy longest-match-first, continuation pieces looked up behind `prefix` (0..16 bytes), a token
@@ -1036,6 +1136,10 @@ class Pipeline:
         has run when the slice is handed over, so a Tally holds the whole corpus when run() returns."""
         _set_vocab(lib().dtk_pipeline_set_vocab, "dtk_pipeline_set_vocab", self, v, tally, ids_home)
 
+    def set_fold(self, fold):
+        """Batch.set_fold for every slice."""
+        _set_fold(lib().dtk_pipeline_set_fold, "dtk_pipeline_set_fold", self, fold)
+
     def set_wordpiece(self, v, prefix=b"##", unk_id=0, max_runes=0, pieces_home=True):
         """Batch.set_wordpiece for every slice: on_slice reads a slice's pieces with batch.pieces(); a slice is handed
         over when its split has finished."""
@@ -1118,6 +1222,10 @@ class Stream:
         the ids of the stream as one document) and n_unknown; `tally` gets every slice's tokens once.  ids_home=False:
         tok_id stays None (a tally alone: nothing per token leaves the device).  None turns it off."""
         _set_vocab(lib().dtk_stream_set_vocab, "dtk_stream_set_vocab", self, v, tally, ids_home)
+
+    def set_fold(self, fold):
+        """Batch.set_fold for every slice of the stream."""
+        _set_fold(lib().dtk_stream_set_fold, "dtk_stream_set_fold", self, fold)
 
     def set_wordpiece(self, v, prefix=b"##", unk_id=0, max_runes=0, pieces_home=True):
         """Every SliceView brings its tokens' pieces (piece_off from 0 in every slice, piece_id, piece_bend relative to the

@@ -33,6 +33,7 @@
 #include <ostream>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "datok_gpu.h"
@@ -649,6 +650,43 @@ inline bool set_wordpiece(dtk_batch *b, const Vocab *v, const WordPiece &o = Wor
 inline bool pieces(dtk_batch *b, dtk_piece_view *out, bool device = false) {
   const int rc = device ? dtk_batch_pieces_device(b, out) : dtk_batch_pieces_host(b, out);
   if (rc != DTK_OK) std::fprintf(stderr, "datok: pieces: %s\n", dtk_strerror(rc));
+  return rc == DTK_OK;
+}
+
+// ---- token keys folded on the device (dtk_fold, datok_gpu.h): a finite map from a code point to 0..DTK_FOLD_MAX code
+// points, applied rune by rune where the lookup (Vocab) and the split (WordPiece) read a token's key -- lower-casing and
+// accent stripping for uncased vocabularies -- with every offset still counted in source bytes.  The vocabulary is not
+// folded: it must be in folded form already.  The map is data; code points it does not list fold to themselves.
+class Fold {
+ public:
+  // ok() is false, with a log line, when the fold could not be made (no device, a surrogate or a duplicate source, more
+  // than DTK_FOLD_MAX targets, a target that is no scalar value).
+  explicit Fold(const std::vector<std::pair<uint32_t, std::u32string>> &mapping) {
+    std::vector<uint32_t> from, to_off(1, 0), to;
+    for (const auto &m : mapping) {
+      from.push_back(m.first);
+      for (char32_t c : m.second) to.push_back((uint32_t)c);
+      to_off.push_back((uint32_t)to.size());
+    }
+    from.push_back(0); to.push_back(0);  // (never read: the arrays are not null for an empty mapping)
+    const int rc = dtk_fold_create(from.data(), to_off.data(), to.data(), (uint32_t)mapping.size(), &f_);
+    if (rc != DTK_OK) std::fprintf(stderr, "datok: fold: %s\n", dtk_strerror(rc));
+  }
+  ~Fold() { dtk_fold_free(f_); }
+  Fold(const Fold &) = delete;
+  Fold &operator=(const Fold &) = delete;
+  bool ok() const { return f_ != nullptr; }
+  const dtk_fold *get() const { return f_; }
+
+ private:
+  dtk_fold *f_ = nullptr;
+};
+
+// Attaches the fold to a batch's ids and split (f == nullptr: off); the finished run's ids, pieces and rows are computed
+// anew under it when they are next asked for.  false + log line for a fold of another device.
+inline bool set_fold(dtk_batch *b, const Fold *f) {
+  const int rc = dtk_batch_set_fold(b, f ? f->get() : nullptr);
+  if (rc != DTK_OK) std::fprintf(stderr, "datok: fold: %s\n", dtk_strerror(rc));
   return rc == DTK_OK;
 }
 

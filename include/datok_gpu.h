@@ -501,9 +501,10 @@ int dtk_batch_token_ids_host(dtk_batch *b, dtk_token_id_view *out);
  *          compared as bytes; of equal words the lowest index wins, as in dtk_vocab).  If there is no such end the whole
  *          token is the single piece unk_id (BERT's is_bad: no partial result, no backtracking).  Otherwise that word's
  *          index is the next piece and start = end.
- *      The text is taken as it is: no lower-casing, no accent stripping, no CJK splitting -- what BERT's BasicTokenizer
- *      does in front of WordPiece is the caller's.  A word that ends or begins inside a rune can never match, because
- *      cuts lie on rune boundaries only; neither can an empty word or the bare prefix.
+ *      Without a fold (dtk_batch_set_fold below) the text is taken as it is.  With one, lower-casing and accent
+ *      stripping -- what BERT's BasicTokenizer does in front of WordPiece -- happen where the key is read; CJK and
+ *      punctuation splitting and whitespace cleaning stay with the caller.  A word that ends or begins inside a rune can
+ *      never match, because cuts lie on rune boundaries only; neither can an empty word or the bare prefix.
  *        The outputs, in the batch-wide token order that tok_off indexes: piece_off[n_tok + 1], CSR; piece_id[n_pieces];
  *      piece_bend[n_pieces], the piece's end as a byte offset in its document, in SOURCE bytes (a replaced byte is one
  *      source byte and three key bytes): a piece begins at tok_bstart[i] or at its predecessor's end, and an unk_id piece
@@ -540,6 +541,52 @@ typedef struct {
 } dtk_piece_view;
 int dtk_batch_pieces_device(dtk_batch *b, dtk_piece_view *out);
 int dtk_batch_pieces_host(dtk_batch *b, dtk_piece_view *out);
+
+/* ---- token keys folded on the device: uncased vocabularies and accent stripping, for the ids and the split above.
+ *      A FOLD F is a finite map from a code point to a sequence of 0..DTK_FOLD_MAX (= 4) code points.  Code points not
+ *      in the map fold to themselves.  Surrogates, values above U+10FFFF, duplicate sources and targets that are not
+ *      scalar values are DTK_E_ARG, as are offsets that do not ascend from 0.  The map is data: the library embeds no
+ *      Unicode tables.
+ *        Let K be the key as defined above: the surface, with every undecodable byte as U+FFFD; K is valid UTF-8.  The
+ *      FOLDED KEY is F(K): the UTF-8 of the folds of K's runes, in order; an invalid byte folds as U+FFFD.  Vocabulary
+ *      words are NOT folded: the caller supplies a vocabulary that is already in folded form.
+ *        Ids (dtk_batch_set_vocab) with a fold attached: tok_id[i] is the lowest index of the word equal to F(K), or
+ *      DTK_ID_UNKNOWN.  An empty F(K) matches an empty word, as an empty key does without a fold.
+ *        Split (dtk_batch_set_wordpiece) with a fold attached: the rule above stays, with these changes and nothing else:
+ *        - cuts lie on rune boundaries of K, that is, on source runes;
+ *        - the candidate for [start, end) is F(K[start:end)) when start == 0, or prefix + F(K[start:end)) otherwise;
+ *        - a candidate whose fold is empty never matches, even if the vocabulary contains "" or the bare prefix;
+ *        - "the largest end" is still taken: runes that fold to nothing behind a match therefore belong to that piece;
+ *        - the last piece of a split token still ends at the clamped tok_bend;
+ *        - max_runes counts the runes of F(K), which is what BERT's WordPiece sees;
+ *        - a non-empty K with no such end is the single piece unk_id -- a token made only of stripped marks, or a
+ *          remainder that folds to nothing with no preceding piece -- and counts in n_unknown;
+ *        - piece_bend stays in SOURCE bytes, exactly as without a fold; no row gets zero pieces except an empty K;
+ *        - the vocabulary's longest word bounds the FOLDED length of a candidate, never its source length.
+ *      With no fold attached, every result is bit for bit what it is without this section.
+ *        The object is built on the host and copied to the device of the calling thread; immutable afterwards and
+ *      shareable between batches and threads, like a dtk_vocab.  Without a device dtk_fold_create returns
+ *      DTK_E_NO_DEVICE.  dtk_fold_apply_mem needs no device: it writes F(K) of `key` -- any bytes, the undecodable ones
+ *      as U+FFFD -- to out[cap]; *n_out is its length, and with more than cap bytes the call returns DTK_E_CAPACITY.
+ *      dtk_wordpiece_probe_fold_mem is dtk_wordpiece_probe_mem under the fold given as arrays: `key` is K (valid UTF-8,
+ *      else DTK_E_ARG) and `ends` are offsets in the bytes of the given key. ---- */
+#define DTK_FOLD_MAX 4u
+typedef struct dtk_fold dtk_fold;
+/* source from[i] folds to to[to_off[i] .. to_off[i+1]); to_off[0] == 0 */
+int dtk_fold_create(const uint32_t *from, const uint32_t *to_off, const uint32_t *to, uint32_t n, dtk_fold **out);
+void dtk_fold_free(dtk_fold *f);
+int dtk_fold_apply_mem(const uint32_t *from, const uint32_t *to_off, const uint32_t *to, uint32_t n,
+                       const uint8_t *key, size_t key_len, uint8_t *out, size_t cap, size_t *n_out);
+int dtk_wordpiece_probe_fold_mem(const uint8_t *bytes, const uint64_t *off, uint32_t n_words,
+                                 const uint8_t *prefix, uint32_t prefix_len, int32_t unk_id, uint32_t max_runes,
+                                 const uint32_t *from, const uint32_t *to_off, const uint32_t *to, uint32_t n,
+                                 const uint8_t *key, size_t key_len, int32_t *ids, uint32_t *ends, uint32_t cap,
+                                 uint32_t *n_out);
+/* f == NULL: off (the default).  The fold applies to the batch's ids and to its split, must outlive the batch's use of
+ * it and live on the batch's device (else DTK_E_ARG).  Setting or clearing it makes the finished run's ids, pieces and
+ * model input rows stale: the next dtk_batch_token_ids_*, dtk_batch_pieces_* or dtk_batch_encoded_* call computes them
+ * anew for that run (a tally attached to the ids then counts the run's tokens once more). */
+int dtk_batch_set_fold(dtk_batch *b, const dtk_fold *f);
 
 /* ---- sentences or documents as fixed-length model input rows, on the device: the matrix input_ids[n_rows x max_len]
  *      a BERT-style model takes, built behind the WordPiece split from what is resident in HBM.
@@ -667,6 +714,8 @@ int dtk_pipeline_set_vocab(dtk_pipeline *p, const dtk_vocab *v, dtk_tally *t, in
  * over when its split has finished. */
 int dtk_pipeline_set_wordpiece(dtk_pipeline *p, const dtk_vocab *v, const uint8_t *prefix, uint32_t prefix_len,
                                int32_t unk_id, uint32_t max_runes, int pieces_home);
+/* dtk_batch_set_fold for every slice. */
+int dtk_pipeline_set_fold(dtk_pipeline *p, const dtk_fold *f);
 /* dtk_batch_set_encode for every slice: a slice is handed over when its encode has finished, and `fn` reads it through
  * dtk_batch_encoded_host.  Units and row_piece0 count from 0 in every slice, as piece_off does. */
 int dtk_pipeline_set_encode(dtk_pipeline *p, const dtk_encode_spec *spec, int rows_home);
@@ -865,6 +914,8 @@ int dtk_stream_token_ids(dtk_stream *s, dtk_token_id_view *out);
  *      pieces_home == 0 the three pointers are NULL and the counts are still there. ---- */
 int dtk_stream_set_wordpiece(dtk_stream *s, const dtk_vocab *v, const uint8_t *prefix, uint32_t prefix_len,
                              int32_t unk_id, uint32_t max_runes, int pieces_home);
+/* dtk_batch_set_fold for every slice of the stream. */
+int dtk_stream_set_fold(dtk_stream *s, const dtk_fold *f);
 int dtk_stream_pieces(dtk_stream *s, dtk_piece_view *out);
 /* flags: DTK_NEWLINE_AFTER_EOT is accepted and changes nothing here (it only moves the writer's rune offsets), except
  * that with position rendering on it must be the bit dtk_stream_set_position_render got.  Short

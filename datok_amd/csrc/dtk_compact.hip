@@ -762,12 +762,6 @@ __global__ __launch_bounds__(256) void k_compact_small(DtkCompactArgs A, uint32_
 // ---- long documents: what each segment adds (k_seg_sum), then per document an exclusive scan of
 //      the segments (k_seg_scan) -> the carries k_compact starts a segment with
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // rune starts among the input bytes [g0, g1) (bit g of rs_bits = byte g), all lanes take part
 __device__ __forceinline__ uint32_t runes_between(const uint32_t *__restrict__ bits, uint64_t g0, uint64_t g1) {
   uint32_t n = 0;
@@ -861,25 +855,6 @@ __global__ __launch_bounds__(WAVE) void k_seg_scan(DtkCompactArgs A, const uint3
 // Turns the per-document counts into CSR row offsets (totals at [n_docs]) and counts flagged documents.
 
 #define SCAN_TB 256u
-
-// exclusive prefix sum of one 64-bit value per thread over a block of SCAN_TB threads; total = the block's sum.
-// sh: one word per wave (a second call may reuse it at once)
-__device__ __forceinline__ uint64_t scan_block_excl(uint64_t v, uint64_t *sh, uint64_t &total) {
-  const uint32_t lane = lane_id(), wid = threadIdx.x >> 6;
-  const uint64_t x = wave_incl_scan64(v);
-  if (lane == WAVE - 1) sh[wid] = x;
-  __syncthreads();
-  uint64_t base = 0, tot = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < SCAN_TB / WAVE; w++) {
-    const uint64_t s = sh[w];
-    if (w < wid) base += s;
-    tot += s;
-  }
-  __syncthreads();
-  total = tot;
-  return base + x - v;
-}
 
 // Up to DTK_SCAN_TILES_MAX_DOCS documents, one launch: tile t (a block of 256 threads, one wave slot per SIMD: it
 // finds a place while other batches' walks fill the chip) owns documents [256 t, 256 t + 256), one per thread, and
@@ -1100,7 +1075,9 @@ extern "C" int dtk_launch_seg_prepare(const DtkCompactArgs *args, const uint32_t
   return (int)hipGetLastError();
 }
 
-// Many documents: the same scan in three launches (tile sums, scan of the sums, tiles).
+// Many documents: the same scan in three launches (tile sums, scan of the sums, tiles).  ws[4 t + j] is sum j of tile t
+// (the three counts, the flagged documents): a tile's four sums share a cache line, which the middle and the last
+// launch wait for once (profiles/render_shared.txt).
 #define SCAN_PER 8u
 #define SCAN_TILE (SCAN_TB * SCAN_PER)
 
@@ -1113,7 +1090,7 @@ __global__ __launch_bounds__(SCAN_TB) void k_scan3_sums(const uint64_t *ca, cons
   for (uint32_t i = i0; i < i0 + SCAN_PER && i < n; i++) { s[0] += ca[i]; s[1] += cb[i]; s[2] += cc[i]; s[3] += status[i] != 0; }
   for (int j = 0; j < 4; j++) {
     uint64_t tot;
-    (void)scan_block_excl(s[j], sh, tot);
+    (void)block_excl_scan64(s[j], sh, tot);
     if (threadIdx.x == 0) ws[4u * blockIdx.x + j] = tot;
   }
 }
@@ -1129,7 +1106,7 @@ __global__ __launch_bounds__(SCAN_TB) void k_scan3_mid(uint64_t *ws, uint32_t nb
     uint64_t sm = 0;
     for (uint32_t i = lo; i < hi; i++) sm += ws[4u * i + j];
     uint64_t tot;
-    uint64_t run = scan_block_excl(sm, sh, tot);
+    uint64_t run = block_excl_scan64(sm, sh, tot);
     for (uint32_t i = lo; i < hi; i++) { const uint64_t v = ws[4u * i + j]; ws[4u * i + j] = run; run += v; }
     if (tid == 0) {
       totals[j] = tot;
@@ -1152,7 +1129,7 @@ __global__ __launch_bounds__(SCAN_TB) void k_scan3_apply(const uint64_t *ca, con
     uint64_t v[SCAN_PER], sm = 0;
     for (uint32_t q = 0; q < SCAN_PER; q++) { v[q] = i0 + q < n ? src[j][i0 + q] : 0; sm += v[q]; }
     uint64_t tot;
-    uint64_t run = ws[4u * blockIdx.x + j] + scan_block_excl(sm, sh, tot);
+    uint64_t run = ws[4u * blockIdx.x + j] + block_excl_scan64(sm, sh, tot);
     for (uint32_t q = 0; q < SCAN_PER; q++) {
       if (i0 + q < n) dst[j][i0 + q] = run;
       run += v[q];

@@ -1,6 +1,7 @@
-// dtk_device.h -- what the kernel units share: wave helpers, the windows macro of the walk kernels, the block scan, the
-// search and the list reads of a stream slice's units, the per-document repair step (used by the verification's fix
-// kernel and by the one-launch scan).
+// dtk_device.h -- what the kernel units share: the wave helpers (scans, folds, the sum), one block scan of 256 threads
+// per width and the in-place row scans on top of it, the searches, the list reads of a stream slice's units, the U+FFFD rule of
+// the two renderers (which bytes print as the replacement character, how a surface is written with them expanded) and
+// the per-document repair step (used by the verification's fix kernel and by the one-launch scan).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -72,8 +73,15 @@ __device__ __forceinline__ int32_t wave_max(int32_t v) {
   return __builtin_amdgcn_readlane(x, WAVE - 1);
 }
 
+// sum over the 64 lanes, in every lane
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
 // exclusive prefix sum of a 32-bit value over the block's 256 threads (four waves: wave_excl_scan, the wave totals
-// through LDS); wave_tot: 256 / WAVE words of LDS (dtk_evlist.hip, dtk_sentences.hip)
+// through LDS); wave_tot: 256 / WAVE words of LDS
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wave_tot, uint32_t &total) {
   uint32_t wt;
   const uint32_t x = wave_excl_scan(v, wt);
@@ -91,9 +99,6 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wave_t
   }
   return before + x;
 }
-
-// ---- what the kernels of a stream slice's outputs share (dtk_streamrender, dtk_streampos, dtk_streamoffs .hip): blocks
-// of 256 threads over tiles of 256 tokens or list entries
 
 // exclusive prefix sum of a 64-bit value over the block's 256 threads; wave_tot: 256 / WAVE words of LDS
 __device__ __forceinline__ uint64_t block_excl_scan64(uint64_t v, uint64_t *wave_tot, uint64_t &total) {
@@ -113,18 +118,36 @@ __device__ __forceinline__ uint64_t block_excl_scan64(uint64_t v, uint64_t *wave
   return before + inc - v;
 }
 
-// exclusive scan of base[0 .. n) in place by one block of 256 threads; returns the sum
-__device__ __forceinline__ uint64_t scan_row64(uint64_t *base, uint32_t n, uint64_t *wave_tot) {
-  uint64_t carry = 0;
+// exclusive scan of base[0 .. n) in place by one block of 256 threads, in rounds of 256 consecutive entries with a
+// carry; returns the sum.  T: 32 or 64 bits, the width of the block scan
+template <class T>
+__device__ __forceinline__ T scan_row_in_place(T *base, uint32_t n, T *wave_tot) {
+  T carry = 0;
   for (uint32_t i0 = 0; i0 < n; i0 += 256u) {  // (block-uniform trip count)
     const uint32_t i = i0 + threadIdx.x;
-    const uint64_t v = i < n ? base[i] : 0u;
-    uint64_t total;
-    const uint64_t x = block_excl_scan64(v, wave_tot, total);
+    const T v = i < n ? base[i] : 0u;
+    T total, x;
+    if constexpr (sizeof(T) == 8) x = block_excl_scan64(v, wave_tot, total); else x = block_excl_scan(v, wave_tot, total);
     if (i < n) base[i] = carry + x;
     carry += total;
   }
   return carry;
+}
+__device__ __forceinline__ uint64_t scan_row64(uint64_t *base, uint32_t n, uint64_t *wave_tot) {
+  return scan_row_in_place(base, n, wave_tot);
+}
+__device__ __forceinline__ uint32_t scan_row(uint32_t *base, uint32_t n, uint32_t *wave_tot) {
+  return scan_row_in_place(base, n, wave_tot);
+}
+
+// first i in [lo, hi) for which pred(i) is false, else hi; pred is monotone: true on a prefix of the range, false behind
+template <class I, class P>
+__device__ __forceinline__ I first_false(I lo, I hi, P pred) {
+  while (lo < hi) {
+    const I mid = lo + ((hi - lo) >> 1);
+    if (pred(mid)) lo = mid + 1u; else hi = mid;
+  }
+  return lo;
 }
 
 // first i in [0, n) with a[i] >= x, else n
@@ -144,10 +167,34 @@ __device__ __forceinline__ uint32_t evl_entries(const A &a) {
   return n > a.evl_cap ? 0xFFFFFFFFu : n;
 }
 
-// byte i of the text did not decode: it prints as U+FFFD (as is_invalid_byte of dtk_render.hip)
+// ---- the U+FFFD rule of the renderers (dtk_render.hip, dtk_streamrender.hip): string(buf[offset:]) re-encodes the
+// window's runes (token_writer.go:85), so a byte that did not decode leaves as EF BF BD.  Such bytes are the rune starts
+// of width 1 whose rune is >= 256 in the symbol stream.
 __device__ __forceinline__ bool sym_invalid_byte(const DtkSym &S, uint64_t i) {
   const uint32_t e = dtk_sym_entry(S, i);
   return DTK_SYM_WIDTH(e) == 1u && ((e >> DTK_SYM_CLS_SHIFT) & 3u) >= 2u;
+}
+
+// how many of the text's bytes [i0, i0 + n) print as U+FFFD: each makes its surface two bytes longer
+__device__ __forceinline__ uint32_t sym_invalid_count(const DtkSym &S, uint64_t i0, uint32_t n) {
+  uint32_t c = 0;
+  for (uint32_t q = 0; q < n; q++) c += sym_invalid_byte(S, i0 + q) ? 1u : 0u;
+  return c;
+}
+
+// the surface text[i0 .. i0 + n) to out[o ..) with those bytes expanded, nothing stored at or behind `cap`: a
+// replacement only if its three bytes fit, a plain byte only if it fits; the offset advances either way
+__device__ __forceinline__ void sym_expand(const DtkSym &S, const uint8_t *__restrict__ text, uint64_t i0, uint32_t n,
+                                           uint8_t *__restrict__ out, uint64_t o, uint64_t cap) {
+  for (uint32_t q = 0; q < n; q++) {
+    if (sym_invalid_byte(S, i0 + q)) {
+      if (o + 3u <= cap) { out[o] = 0xEF; out[o + 1] = 0xBF; out[o + 2] = 0xBD; }
+      o += 3u;
+    } else {
+      if (o < cap) out[o] = text[i0 + q];
+      o += 1u;
+    }
+  }
 }
 
 // 64-bit words that hold n 32-bit ones (a workspace is laid out in 64-bit words)

@@ -79,16 +79,8 @@ __global__ __launch_bounds__(256) void k_evl_count(DtkEvListArgs A) {
 
 __global__ __launch_bounds__(256) void k_evl_scan(DtkEvListArgs A) {
   __shared__ uint32_t wave_tot[EVL_THREADS / WAVE];
-  uint32_t carry = 0;
-  for (uint32_t i0 = 0; i0 < A.n_tiles; i0 += EVL_THREADS) {  // (block-uniform trip count)
-    const uint32_t i = i0 + threadIdx.x;
-    const uint32_t v = i < A.n_tiles ? A.tile_base[i] : 0u;
-    uint32_t total;
-    const uint32_t x = block_excl_scan(v, wave_tot, total);
-    if (i < A.n_tiles) A.tile_base[i] = carry + x;
-    carry += total;
-  }
-  if (threadIdx.x == 0u) { A.evl_off[A.n_docs] = carry; *A.count = carry; }
+  const uint32_t all = scan_row(A.tile_base, A.n_tiles, wave_tot);
+  if (threadIdx.x == 0u) { A.evl_off[A.n_docs] = all; *A.count = all; }
 }
 
 __global__ __launch_bounds__(256) void k_evl_write(DtkEvListArgs A) {
@@ -144,12 +136,8 @@ __global__ __launch_bounds__(256) void k_evl_rows(DtkEvListArgs A) {
   const uint32_t d = blockIdx.x * EVL_THREADS + threadIdx.x;
   if (d >= A.n_docs) return;
   const uint64_t key = A.doc_off[d] + d;
-  uint32_t lo = 0, hi = n;  // the first row in [0, n) whose bit is >= key, or n
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if ((uint64_t)A.evl_bit[mid] < key) lo = mid + 1u; else hi = mid;
-  }
-  A.evl_off[d] = lo;
+  // the first row in [0, n) whose bit is >= key, or n
+  A.evl_off[d] = first_false(0u, n, [&](uint32_t r) { return (uint64_t)A.evl_bit[r] < key; });
 }
 
 }  // namespace

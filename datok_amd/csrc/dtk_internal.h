@@ -642,6 +642,7 @@ int dtk_launch_exact(const struct DtkTableDev *tab, const struct DtkExactArgs *a
 int dtk_launch_seg_prepare(const struct DtkCompactArgs *args, const uint32_t *doc_seg0, void *stream);
 int dtk_launch_render(const struct DtkRenderArgs *args, int stage, void *stream);
 uint32_t dtk_render_tiles(uint64_t n);
+uint64_t dtk_render_ws(struct DtkRenderArgs *args, uint64_t *ws);  // as dtk_streampos_ws, the eight spare words included
 int dtk_launch_clear2(void *a, uint64_t a_bytes, void *b, uint64_t b_bytes, void *stream);
 // Up to this many documents the row offsets come from one launch of independent 256-document tiles (k_scan3_tiles,
 // which can also do k_spec_fix's per-document step); above it from three launches.  Every tile adds up the counts

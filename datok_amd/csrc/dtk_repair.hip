@@ -196,12 +196,9 @@ __global__ __launch_bounds__(256) void k_redo_clear(DtkWalkArgs A, DtkSpecArgs S
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= A.bit_words) return;
   const uint64_t G0 = 32ull * j, G1 = G0 + 32ull;
-  // the last document that starts at or before bit G0
-  uint32_t lo = 0, hi = A.n_docs;
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (DTK_EV_BIT(A.doc_off[mid], mid) <= G0) lo = mid; else hi = mid;
-  }
+  // the last document that starts at or before bit G0: document 0 starts at bit 0, so the search is over [1, n_docs)
+  // (an empty range, n_docs == 0 included, gives its lower end: document 0)
+  const uint32_t lo = first_false(1u, A.n_docs, [&](uint32_t d) { return DTK_EV_BIT(A.doc_off[d], d) <= G0; }) - 1u;
   uint32_t m_all = 0, m_open = 0;
   for (uint32_t d = lo; d < A.n_docs; d++) {
     const uint64_t key = DTK_EV_BIT(A.doc_off[d], d);

@@ -316,23 +316,18 @@ static int render(dtk_batch *b, uint32_t bits) {
   bits &= 15u;
   if (b->render_flags == bits) return DTK_OK;
   hipStream_t s = b->stream;
-  const uint64_t nt = b->totals.n_tokens, ns = b->totals.n_sent, nx = b->totals.n_texts, nd = b->n_docs;
-  const uint64_t tt = dtk_render_tiles(nt), st = dtk_render_tiles(ns);
-  const uint64_t words = 2 * (nt + 1) + (ns + 1) + 2 * tt + st + (nd + 1) + 4 * (nx + 1) + 8;
-  if ((rc = b->d_rws.fit(words, words + words / 8)) != DTK_OK) return rc;
+  const uint64_t nx = b->totals.n_texts;
   DtkRenderArgs R{};
   R.text = b->d_text; R.doc_off = b->d_off; R.n_docs = b->n_docs; R.flags = bits;
   R.tok_off = b->d_tok_off; R.sent_off = b->d_sent_off; R.text_off = b->d_text_off;
-  R.n_tok = nt; R.n_sent = ns; R.n_text = nx;
+  R.n_tok = b->totals.n_tokens; R.n_sent = b->totals.n_sent; R.n_text = nx;
+  const uint64_t words = dtk_render_ws(&R, nullptr);
+  if ((rc = b->d_rws.fit(words, words + words / 8)) != DTK_OK) return rc;
+  (void)dtk_render_ws(&R, b->d_rws);
   R.rstart = b->d_rstart; R.rend = b->d_rend; R.sent = b->d_sent;
   R.bstart = b->d_bstart; R.bend = b->d_bend; R.sbefore = b->d_sbefore;
   R.ttok = b->d_ttok; R.tsent = b->d_tsent; R.ts_end = b->d_ts_end; R.doc_ns = b->d_doc_ns;
   R.sym = sym_of(b); if (!b->n_invalid) R.sym.base = nullptr;
-  uint64_t *q = b->d_rws;
-  R.A = q; q += nt + 1; R.P = q; q += nt + 1; R.Q = q; q += ns + 1;
-  R.blkA = q; q += tt; R.blkP = q; q += tt; R.blkQ = q; q += st;
-  R.ns_off = q; q += nd + 1;
-  R.tx_base = q; q += nx + 1; R.tx_stream = q; q += nx + 1; R.tx_pos = q; q += nx + 1; R.tx_sent = q; q += nx + 1;
   R.out_off = b->d_out_off;
   if (dtk_launch_render(&R, 0, s)) return hip_fail(hipGetLastError(), "render sizes");
   HIP_TRY(hipMemcpyAsync(&b->h_totals->render_total, R.tx_base + nx, 8, hipMemcpyDeviceToHost, s));

@@ -46,12 +46,7 @@ __device__ __forceinline__ bool sen_wide(const DtkSentencesArgs &A) {
 
 // the first d in [0, n_docs) whose bit 0 is at or behind g, else n_docs
 __device__ __forceinline__ uint32_t first_doc_from(const DtkSentencesArgs &A, uint64_t g) {
-  uint32_t lo = 0, hi = A.n_docs;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (A.doc_off[mid] + mid < g) lo = mid + 1u; else hi = mid;
-  }
-  return lo;
+  return first_false(0u, A.n_docs, [&](uint32_t d) { return A.doc_off[d] + d < g; });
 }
 
 // The thread's words, bits at or behind n_bits cleared, the document starts among them ORed into R.  Returns the

@@ -45,8 +45,7 @@ __device__ __forceinline__ SrTok sr_token(const DtkStreamRenderArgs &A, uint64_t
   t.bs = bs;
   t.len = (be > bs && be <= A.text_len) ? be - bs : 0u;  // (start > end: DTK_ST_BAD_OFFSET, out of contract)
   t.w = (uint64_t)t.len + 1u;
-  if (INV)
-    for (uint32_t q = 0; q < t.len; q++) t.w += sym_invalid_byte(A.sym, (uint64_t)bs + q) ? 2u : 0u;
+  if (INV) t.w += 2u * sym_invalid_count(A.sym, bs, t.len);
   return t;
 }
 
@@ -135,17 +134,7 @@ __global__ __launch_bounds__(256) void k_sr_copy(DtkStreamRenderArgs A) {
   const uint8_t *__restrict__ text = A.text;
   uint8_t *__restrict__ out = A.out;
   if (INV) {
-    if (!valid) return;
-    uint64_t o = off;
-    for (uint32_t q = 0; q < t.len; q++) {
-      if (sym_invalid_byte(A.sym, (uint64_t)t.bs + q)) {
-        if (o + 3u <= A.cap) { out[o] = 0xEF; out[o + 1] = 0xBF; out[o + 2] = 0xBD; }
-        o += 3u;
-      } else {
-        if (o < A.cap) out[o] = text[t.bs + q];
-        o += 1u;
-      }
-    }
+    if (valid) sym_expand(A.sym, text, t.bs, t.len, out, off, A.cap);
     return;
   }
   // ---- the wave's 64 tokens: the output range [base, base + range), staged from its 16-byte boundary `abase` on

@@ -11,6 +11,35 @@ from datok_amd.host import (EVL_SEOT, EVL_SEPS, EVL_TEOT, SENTENCES, TOKEN_POS, 
 FFFD = b"\xef\xbf\xbd"
 
 
+def invalid_flags(surface):
+    """Per byte of `surface`: it does not decode (Go's rune iteration gives it U+FFFD of width 1)."""
+    flags, i = [], 0
+    for r in _decode_runes(surface):
+        bad = r == 0xFFFD and surface[i:i + 3] != FFFD
+        w = 1 if bad else len(chr(r).encode("utf-8"))
+        flags += [bad] + [False] * (w - 1)
+        i += w
+    assert i == len(surface)
+    return flags
+
+
+def expand_ref(out, o, surface, invalid, cap):
+    """The byte rule both renderers share (sym_expand, dtk_device.h): writes `surface` into the bytearray `out` from
+    offset o on, a byte whose flag in `invalid` is set as U+FFFD, and stores nothing at or behind `cap` -- a replacement
+    only if its three bytes fit, a plain byte only if it fits.  Returns the offset behind the surface, which does not
+    depend on cap."""
+    for b, bad in zip(surface, invalid):
+        if bad:
+            if o + 3 <= cap:
+                out[o:o + 3] = FFFD
+            o += 3
+        else:
+            if o < cap:
+                out[o] = b
+            o += 1
+    return o
+
+
 def _exclusive(w):
     out = np.zeros(len(w) + 1, dtype=np.int64)
     np.cumsum(w, out=out[1:])
@@ -48,7 +77,12 @@ def render_slice_ref(is_matrix, sl, bits) -> bytes:
         tail = int(sl.tail)
         total += (sen if tail & 1 else 0) + (1 if tail & 2 else 0)
     out = bytearray(b"\n" * total)
-    for o, s in zip(off.tolist(), surf):
-        out[o:o + len(s)] = s
+    if tok:
+        for o, a, z, s in zip(off.tolist(), bs.tolist(), be.tolist(), surf):
+            piece = text[a:z]
+            if piece.isascii():        # (every byte decodes and fits: the rule's plain case, without the loop)
+                out[o:o + len(s)] = s
+                continue
+            assert expand_ref(out, o, piece, invalid_flags(piece), total) == o + len(s) and out[o:o + len(s)] == s
     assert len(out) == total
     return bytes(out)

@@ -47,7 +47,7 @@ __device__ __forceinline__ uint32_t lowmask(uint32_t n) { return n >= 32u ? 0xFF
 // (about half the registers, a third of the code).  FULL = true: the documents with one.  Which is which follows from
 // what the walk counted: a document has an EOT call iff it has more than one TextEnd or its only TextEnd is not the
 // tail's.  The first kernel tells the host that the second is needed (any_eot); a batch object whose last run
-// needed it launches it right away (dtk_batch.cpp).
+// needed it launches it right away (dtk_run.cpp).
 #ifdef DTK_PROBE
 // cycles per wave of k_compact_plain: prologue, tile loads + rune scan, counts + latch, token loop, sentence loop +
 // carries, tail; [6] waves, [7] tiles

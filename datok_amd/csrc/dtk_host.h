@@ -1,4 +1,4 @@
-// dtk_host.h -- what the host units of libdatok_gpu.so (dtk_model, dtk_foma, dtk_batch, dtk_results, dtk_derived, dtk_slice .cpp) share:
+// dtk_host.h -- what the host units of libdatok_gpu.so (dtk_model, dtk_foma, dtk_batch, dtk_run, dtk_results, dtk_derived, dtk_slice .cpp) share:
 // the model and batch objects, the error state, the test hooks, and helpers (hidden, not exported).  No .hip unit includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -396,6 +396,8 @@ struct dtk_batch {
 };
 
 int wait_own(dtk_batch *b);
+int wait_ran(dtk_batch *b);  // (dtk_batch.cpp, as alloc_outputs: what dtk_run.cpp needs of the object)
+int alloc_outputs(dtk_batch *b, uint64_t tok, uint64_t sent, uint64_t text);
 DtkSym sym_of(const dtk_batch *b);
 DtkWalkArgs walk_args(dtk_batch *b);
 int finish(dtk_batch *b);

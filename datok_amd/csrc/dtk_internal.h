@@ -629,13 +629,29 @@ int dtk_launch_symbolize(const uint8_t *text, const uint64_t *doc_off, uint32_t 
 #define DTK_SYM_BLOCK_BYTES 4096u  // input bytes per symbolise block (blk_doc granularity)
 #endif
 int dtk_launch_walk(const struct DtkTableDev *tab, const struct DtkWalkArgs *args, void *stream);
+// The launches of the speculative walk (dtk_launch_spec).  The first pass of a run is START, LINK, WALK, VERIFY or
+// START_WALK, LINK_VERIFY, then FIX unless the scan carries its step; a repair round (spec->redo_from set) is
+// SPREAD_RESET, dtk_launch_redo_clear, LINK, WALK, VERIFY, FIX (dtk_run.cpp: first_pass, repair_round).
+enum DtkSpecStage {
+  DTK_SPEC_START = 0,         // k_spec_start: the lanes' start records (first pass, split shape)
+  DTK_SPEC_LINK = 1,          // k_spec_link (first pass, split shape; every repair round)
+  DTK_SPEC_WALK = 2,          // k_spec_walk: the chunk walk (first pass, split shape; every repair round)
+  DTK_SPEC_VERIFY = 3,        // k_spec_verify (first pass, split shape; every repair round)
+  DTK_SPEC_FIX = 4,           // k_spec_fix: counts the broken documents (first pass, unless the scan does it; every repair round)
+  DTK_SPEC_SPREAD_RESET = 5,  // k_redo_spread, k_redo_reset (repair rounds only, first of the round)
+  DTK_SPEC_START_WALK = 6,    // k_spec_both: start records and chunk walk in one launch (first pass only, fused shape)
+  DTK_SPEC_LINK_VERIFY = 7,   // k_spec_verify with its link step (first pass only, fused shape)
+};
 int dtk_launch_spec(const struct DtkTableDev *tab, const struct DtkWalkArgs *args,
-                    const struct DtkSpecArgs *spec, int stage, uint32_t cmp_mask, uint32_t *redo_out,
+                    const struct DtkSpecArgs *spec, enum DtkSpecStage stage, uint32_t cmp_mask, uint32_t *redo_out,
                     uint32_t *n_bad, void *stream);
-int dtk_launch_spec_check(const struct DtkWalkArgs *args, const struct DtkSpecArgs *spec, int stage, uint32_t cmp_mask,
-                          uint32_t *redo_out, uint32_t *n_bad, void *stream);
+// (the stages that do not walk, dtk_repair.hip: LINK, VERIFY, LINK_VERIFY, FIX, SPREAD_RESET)
+int dtk_launch_spec_check(const struct DtkWalkArgs *args, const struct DtkSpecArgs *spec, enum DtkSpecStage stage,
+                          uint32_t cmp_mask, uint32_t *redo_out, uint32_t *n_bad, void *stream);
 int dtk_launch_redo_clear(const struct DtkWalkArgs *args, const struct DtkSpecArgs *spec, void *stream);
 int dtk_launch_stream_cut(const struct DtkStreamCutArgs *args, void *stream);
+// which kernels dtk_launch_compact launches: for the documents without an EOT call, for those with one, or both
+enum DtkCompactWhich { DTK_COMPACT_PLAIN = 1, DTK_COMPACT_EOT = 2, DTK_COMPACT_BOTH = 3 };
 int dtk_launch_compact(const struct DtkCompactArgs *args, uint32_t small_max, const uint32_t *big_docs, uint32_t n_big,
                        int which, void *stream);
 int dtk_launch_exact(const struct DtkTableDev *tab, const struct DtkExactArgs *args, void *stream);

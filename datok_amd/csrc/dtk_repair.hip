@@ -229,29 +229,31 @@ __global__ __launch_bounds__(256) void k_redo_clear(DtkWalkArgs A, DtkSpecArgs S
 
 // ---------------------------------------------------------------- launchers
 
-// the stages of dtk_launch_spec (dtk_walk.hip) that do not walk: 1 link, 3 verify, 7 link + verify, 4 fix, 5 spread + reset
-extern "C" int dtk_launch_spec_check(const DtkWalkArgs *args, const DtkSpecArgs *spec, int stage, uint32_t cmp_mask,
+// the stages of dtk_launch_spec (dtk_walk.hip) that do not walk: enum DtkSpecStage (dtk_internal.h)
+extern "C" int dtk_launch_spec_check(const DtkWalkArgs *args, const DtkSpecArgs *spec, DtkSpecStage stage, uint32_t cmp_mask,
                                      uint32_t *redo_out, uint32_t *n_bad, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   const uint32_t lane_blocks256 = (spec->n_lanes + 255) / 256;
   const uint32_t doc_blocks = (args->n_docs + 255) / 256;
   switch (stage) {
-    case 1:
+    case DTK_SPEC_LINK:
       hipLaunchKernelGGL(k_spec_link, dim3(lane_blocks256), dim3(256), 0, s, *spec);
       return (int)hipGetLastError();
-    case 3:
+    case DTK_SPEC_VERIFY:
       hipLaunchKernelGGL(k_spec_verify, dim3((spec->n_lanes + VERIFY_TB - 1u) / VERIFY_TB), dim3(VERIFY_TB), 0, s, *args, *spec, cmp_mask, 0u);
       return (int)hipGetLastError();
-    case 7:  // first pass behind k_spec_both: link + verify in one
+    case DTK_SPEC_LINK_VERIFY:  // behind k_spec_both
       hipLaunchKernelGGL(k_spec_verify, dim3((spec->n_lanes + VERIFY_TB - 1u) / VERIFY_TB), dim3(VERIFY_TB), 0, s, *args, *spec, cmp_mask, 1u);
       return (int)hipGetLastError();
-    case 4:
+    case DTK_SPEC_FIX:
       hipLaunchKernelGGL(k_spec_fix, dim3(doc_blocks), dim3(256), 0, s, *args, *spec, redo_out, n_bad);
       return (int)hipGetLastError();
-    case 5:  // repair round, before link / walk / verify / fix
+    case DTK_SPEC_SPREAD_RESET:
       hipLaunchKernelGGL(k_redo_spread, dim3(lane_blocks256), dim3(256), 0, s, *spec);
       hipLaunchKernelGGL(k_redo_reset, dim3(doc_blocks), dim3(256), 0, s, *args, *spec);
       return (int)hipGetLastError();
+    default:  // (the stages that walk: dtk_launch_spec)
+      break;
   }
   return -1;
 }

@@ -460,36 +460,35 @@ extern "C" int dtk_launch_walk(const DtkTableDev *tab, const DtkWalkArgs *args, 
   });
 }
 
-// stage: 6 start records + walk, 7 link + verify, 4 fix (first pass; or 0 start records, 1 link, 2 walk, 3 verify, 4);
-//        5 clear, 6 plan, 2 walk, 7 check (repair rounds, spec->redo_from set)
+// the stages and which pass uses them: enum DtkSpecStage (dtk_internal.h)
 extern "C" int dtk_launch_spec(const DtkTableDev *tab, const DtkWalkArgs *args, const DtkSpecArgs *spec,
-                               int stage, uint32_t cmp_mask, uint32_t *redo_out, uint32_t *n_bad,
+                               DtkSpecStage stage, uint32_t cmp_mask, uint32_t *redo_out, uint32_t *n_bad,
                                void *stream) {
   if (args->n_docs == 0 || spec->n_lanes == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   const uint32_t lane_blocks = (spec->n_lanes + WAVE - 1) / WAVE;
   switch (stage) {
-    case 0:
+    case DTK_SPEC_START:
       return with_trans(tab, args->sym.lut != nullptr, [&](auto tr, auto is_matrix) {
         using TR = decltype(tr);
         hipLaunchKernelGGL((k_spec_start<TR, decltype(is_matrix)::value>), dim3(lane_blocks), dim3(WAVE), 0, s,
                            tr, *args, *spec, tab->epsilon, tab->unknown, tab->identity);
       });
-    case 6:  // first pass: start records and chunk walk in one launch
+    case DTK_SPEC_START_WALK:
       return with_trans(tab, args->sym.lut != nullptr, [&](auto tr, auto is_matrix) {
         using TR = decltype(tr);
         hipLaunchKernelGGL((k_spec_both<TR, decltype(is_matrix)::value>), dim3(lane_blocks), dim3(WAVE),
                            3u * spec->lds_words * sizeof(uint32_t), s, tr, *args, *spec, tab->epsilon, tab->unknown,
                            tab->identity);
       });
-    case 2:
+    case DTK_SPEC_WALK:
       return with_trans(tab, args->sym.lut != nullptr, [&](auto tr, auto is_matrix) {
         using TR = decltype(tr);
         hipLaunchKernelGGL((k_spec_walk<TR, decltype(is_matrix)::value>), dim3(lane_blocks), dim3(WAVE),
                            3u * spec->lds_words * sizeof(uint32_t), s, tr, *args, *spec, tab->epsilon, tab->unknown,
                            tab->identity);
       });
-    case 1: case 3: case 7: case 4: case 5:  // link, verify, link + verify, fix, spread + reset: dtk_repair.hip
+    case DTK_SPEC_LINK: case DTK_SPEC_VERIFY: case DTK_SPEC_LINK_VERIFY: case DTK_SPEC_FIX: case DTK_SPEC_SPREAD_RESET:
       return dtk_launch_spec_check(args, spec, stage, cmp_mask, redo_out, n_bad, stream);
   }
   return -1;

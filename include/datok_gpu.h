@@ -237,7 +237,9 @@ void *dtk_batch_stream(dtk_batch *b); /* hipStream_t, for event timing by the ca
  * around each kernel of dtk_batch_run (no host synchronisation is added).
  * dtk_batch_stage_ms() synchronises and returns the milliseconds of the last
  * run: [0] clears [1] symbolise [2] start records [3] link [4] chunk walk (or
- * the one-lane-per-document walk) [5] verify [6] fix [7] scan [8] compaction. */
+ * the one-lane-per-document walk) [5] verify [6] fix [7] scan [8] compaction.
+ * That is the first pass as four launches; as two (the fused shape): [2] and
+ * [3] are empty, [4] is start records + walk, [5] is link + verify. */
 #define DTK_N_STAGES 9
 int dtk_batch_set_profiling(dtk_batch *b, int enable);
 int dtk_batch_stage_ms(dtk_batch *b, float ms[DTK_N_STAGES]);

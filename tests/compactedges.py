@@ -30,7 +30,7 @@ STEP = 256         # positions queued per light step of a heavy tile
 ROUND = 64         # queued positions per heavy round
 CQ_CAP = 512       # ring capacity in queued positions
 CT_CAP = 512       # rows of a fast tile staged in LDS
-# dtk_batch.cpp, the block that sets b->small_max: the lane kernel runs for a batch of at least LANE_MIN_DOCS documents
+# dtk_run.cpp, the block that sets b->small_max: the lane kernel runs for a batch of at least LANE_MIN_DOCS documents
 # of which at least LANE_MIN_SMALL are at most LANE_SMALL_BYTES long
 LANE_MIN_DOCS, LANE_MIN_SMALL, LANE_SMALL_BYTES = 2048, 16384, 160
 
@@ -41,7 +41,7 @@ ROW_ARRAYS = ("tok_off", "sent_off", "text_off", "status") + FIELDS
 @contextlib.contextmanager
 def small_max(n):
     """The hook SMALL_MAX: documents of at most n bytes go to the lane kernel, whatever the batch's shape (0: none).
-    Read when a batch plans its input -- plan_lanes() in dtk_batch.cpp, called by the first run after set_input -- and
+    Read when a batch plans its input -- plan_lanes() in dtk_run.cpp, called by the first run after set_input -- and
     a batch keeps its plan for equally shaped input: every setting gets a fresh Batch, with the hook around set_input
     and that run."""
     import datok_amd

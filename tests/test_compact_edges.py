@@ -98,7 +98,7 @@ def check_rows(om, pieces, pick, res, flags):
 @pytest.mark.parametrize("flags", FLAGS)
 @pytest.mark.parametrize("model", WAVE_MODELS)
 def test_lane_kernel_as_production_launches_it(tok, om, model, flags):
-    """No hook: the library itself sends the small documents to k_compact_small -- dtk_batch.cpp (the block that sets
+    """No hook: the library itself sends the small documents to k_compact_small -- dtk_run.cpp (the block that sets
     b->small_max) asks for at least LANE_MIN_DOCS = 2048 documents of which at least LANE_MIN_SMALL = 16 384 are at most
     LANE_SMALL_BYTES = 160 bytes long.  17 500 small documents from a pool of 3000 pieces (EOTs, runes of several
     bytes, every length modulo 32) among 300 larger ones, default chunking; rows, status and rendered bytes against the

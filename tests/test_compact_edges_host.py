@@ -258,7 +258,7 @@ def test_b5_the_sentence_latch(om, model):
 
 
 def test_production_batch_has_the_lane_kernels_shape(om):
-    """What dtk_batch.cpp asks before it launches k_compact_small by itself, and what the pool mixes in."""
+    """What dtk_run.cpp asks before it launches k_compact_small by itself, and what the pool mixes in."""
     pieces, pick = ce.production_batch()
     lens = np.array([len(pieces[i]) for i in pick])
     assert len(pick) >= ce.LANE_MIN_DOCS and int((lens <= ce.LANE_SMALL_BYTES).sum()) >= ce.LANE_MIN_SMALL

@@ -11,7 +11,7 @@ import pytest
 
 from conftest import MODELS, ROOT
 from goldens import failed_checks, golden_strings, load_cases, model_file
-from parity import assert_batch_equals_oracle, oracle_doc
+from parity import FIELDS, assert_batch_equals_oracle, oracle_doc
 
 pytestmark = pytest.mark.gpu
 C_byref = ctypes.byref
@@ -511,7 +511,7 @@ int main(int argc, char **argv) {
 def test_many_small_documents(gpu, oracle_models):
     """22 000 documents of 10..200 bytes (the row offsets then come from the multi-block scan; lanes
     are single chunks): every document against the oracle.  At least 16 384 of them are at most 160 bytes long, which
-    is what the batch asks before it compacts the small ones with one lane each (dtk_batch.cpp, b->small_max)."""
+    is what the batch asks before it compacts the small ones with one lane each (dtk_run.cpp, b->small_max)."""
     from datok_amd import corpus
     text, off = corpus.german_docs(640, 4096, seed=77)
     raw = text.tobytes()
@@ -611,9 +611,19 @@ from datok_amd import corpus
 from oracle import oracle as O
 from parity import assert_batch_equals_oracle, oracle_doc
 M = os.path.join(ROOT, "tests", "golden", "models")
-for name, (text, off) in (("tokenizer_de.matok", corpus.german_docs(96, 4096, seed=11)),
-                          ("tokenizer_en.matok", corpus.english_zipf_docs(64, seed=12, max_bytes=8192)),
-                          ("tokenizer_de.datok", corpus.german_docs(32, 2048, seed=13))):
+
+def timed_again(b, tok):
+    # the same run with stage events: every interval of dtk_batch_stage_ms is there in this launch shape, and the
+    # three that every shape has a launch for took time (no bound on any time)
+    b.set_profiling(True); b.run(tok, 0)
+    ms = b.stage_ms()
+    assert tuple(ms) == datok_amd.Batch.STAGES and len(ms) == 9, ms
+    assert all(np.isfinite(v) and v >= 0 for v in ms.values()), ms
+    assert ms["symbolize"] > 0 and ms["walk"] > 0 and ms["compact"] > 0, ms
+
+for i, (name, (text, off)) in enumerate((("tokenizer_de.matok", corpus.german_docs(96, 4096, seed=11)),
+                                         ("tokenizer_en.matok", corpus.english_zipf_docs(64, seed=12, max_bytes=8192)),
+                                         ("tokenizer_de.datok", corpus.german_docs(32, 2048, seed=13)))):
     tok = datok_amd.load_tokenizer_file(os.path.join(M, name)); om = O.Model(os.path.join(M, name))
     for chunk, warm in ((None, 48), (64, 8), (256, 48)):
         with datok_amd.Batch(len(text), len(off) - 1) as b:
@@ -623,6 +633,13 @@ for name, (text, off) in (("tokenizer_de.matok", corpus.german_docs(96, 4096, se
             res = b.result()
             assert not res.status.any()
             assert_batch_equals_oracle(om, res, text, off)
+            if i == 0:
+                timed_again(b, tok)
+    if i == 0:   # ... and with one lane per document
+        with datok_amd.Batch(len(text), len(off) - 1) as b:
+            b.set_chunking(0)
+            b.set_input(text, off)
+            timed_again(b, tok)
 print("VARIANT OK")
 """
 
@@ -647,6 +664,51 @@ def test_kernel_variants_forced_by_environment(env, tmp_path):
     e = dict(os.environ); e.update(env)
     r = subprocess.run([sys.executable, str(script), ROOT], capture_output=True, env=e, timeout=600)
     assert r.returncode == 0 and b"VARIANT OK" in r.stdout, r.stderr.decode()[-2000:]
+
+
+@pytest.mark.gpu
+def test_run_state_carries_between_runs(gpu, oracle_models):
+    """One batch object through what a run and its finish() hand to the next run (dtk_run.cpp, the table at its head).
+    A: eight German documents of 4096 bytes.  B: the first two of them and six documents of 2048 one-letter texts
+    ("a" EOT), 13 344 tokens, 24 714 sentence ints and 12 290 texts by the oracle -- more than the capacities the batch
+    starts with (10 946 / 4 128 / 544), so all three groups of output arrays grow.
+      1  A                       default chunking
+      2  B, chunks of 16 / warm 0  the two German documents mispredict (the recipe of test_fix_step_in_the_scan, which
+                                 also keeps the warm-up from moving back to a blank: extend 0; without that no run
+                                 repairs, with two, three or four German documents): repair rounds from the host,
+                                 growth and both compaction kernels in one finish()
+      3  B again                 two device-side rounds and both compaction kernels with the run
+      4  A, default chunking     (extend 240 is the library's default) no repair, no EOT
+      5  B                       the arrays are large enough and the last run had no EOT: the late EOT kernel alone
+    Two German documents are the fewest in B: the build before dtk_run.cpp reports repair_rounds 5 for run 2 with them."""
+    import datok_amd
+    from datok_amd import corpus
+    tok, om = gpu("tokenizer_de.matok"), oracle_models("tokenizer_de.matok")
+    text_a, off_a = corpus.german_docs(8, 4096, seed=9)
+    raw = text_a.tobytes()
+    text_b, off_b = corpus.concat_docs([raw[:4096], raw[4096:8192]] + [b"a\x04" * 2048] * 6)
+    assert len(text_a) == len(text_b) == 32768
+    names = ("tok_off", "sent_off", "text_off", "status") + tuple(FIELDS)
+    with datok_amd.Batch(32768, 8) as b:
+        def run(text, off, chunking=None):
+            if chunking is not None:
+                b.set_chunking(chunking[0], chunking[1], extend=chunking[2])
+            b.set_input(text, off)
+            b.run(tok, 0)
+            res, tot = b.result(), b.totals()
+            assert assert_batch_equals_oracle(om, res, text, off) == 8
+            return res, tot
+        r1, _ = run(text_a, off_a)
+        r2, t2 = run(text_b, off_b, (16, 0, 0))
+        r3, t3 = run(text_b, off_b)
+        r4, t4 = run(text_a, off_a, (datok_amd.Batch.AUTO_CHUNK, 8, 240))
+        r5, t5 = run(text_b, off_b)
+    assert (t2["n_tokens"], t2["n_sent"], t2["n_texts"]) == (13344, 24714, 12290) and t2["n_sent"] > 12288
+    assert t2["chunk_bytes"] == 16 and t2["repair_rounds"] >= 1 and t3["repair_rounds"] >= 1
+    for f in names:
+        assert np.array_equal(getattr(r3, f), getattr(r2, f)), ("run 3", f)
+        assert np.array_equal(getattr(r5, f), getattr(r2, f)), ("run 5", f)
+        assert np.array_equal(getattr(r4, f), getattr(r1, f)), ("run 4", f)
 
 
 @pytest.mark.gpu
